@@ -22,6 +22,12 @@ The reads sit in HBM in the north star's layout, packed 2 bits per base (--input
 `ascii_in`: the same steps fed ASCII, and the time of the device packer, so that the GPU and the CPU leg can be read from the same starting bytes,
 and `scale_anchor_n1`: the human data set of the N>1 lines streamed through this one GPU after the timed region — the N=1 point of the 1 -> 8 curve in the same record as the headline.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the headline (`value`, `ms_per_step`), the graph of
+the last timed step (counts and node digest) and the tile kernel's `roofline` from the HIP events of the timed steps.  Everything else the line can carry — the ASCII,
+HPC-input and syncmer legs, the edge stage, `cpu_baseline` and its parity check, the anchors, `n1_same_workload`, `exchange`, `stage_ms_last_step`, the figures from
+recorded profiles and the check against tests/golden/bench_counts.json — is measured with `--full` only.  `--dump-outputs DIR` writes the node table of the last
+timed step to DIR as float64 .npy files (dump_outputs below), so that two builds can be compared output for output on the same seeded reads.
+
 Prints ONE JSON line (rank 0).  `roofline` refers to the dominant kernel (sketch_bs_kernel) as fed in the timed region and
 is measured live with HIP events on the stream the kernel is launched on; `roofline_ascii` is the same kernel fed ASCII
 (b_in = 0.25 vs 1.0 byte per base), measured right after the timed region; `cpu_baseline` is the CPU oracle
@@ -75,9 +81,16 @@ def parse():
                          "cleared and refilled, nothing is sketched or — at N>1, where the ranks hold whole sketches — exchanged again); value counts every k's graph: bases x 7 / time")
     ap.add_argument("--watchdog-seconds", type=int, default=1500, help="a rank that is still running after this long dumps the tracebacks of all its threads to stderr and exits (a hang "
                     "in a collective would otherwise sit there until the caller's own limit, without a word); 0 = off")
-    ap.add_argument("--no-scale-anchor", action="store_true", help="default N=1 run: skip the human data set's pass through this GPU after the timed region (scale_anchor_n1)")
-    ap.add_argument("--no-anchor-oracle", action="store_true", help="default N=1 run: skip the CPU oracle's pass over one shard of the human data set (scale_anchor_n1.shard_vs_oracle, ~30 s)")
-    ap.add_argument("--plain", action="store_true", help="only the warm-up and the timed steps (no ASCII legs, no edge stage, no CPU leg): for profiler runs, where every launch should be one of the timed kind")
+    ap.add_argument("--no-scale-anchor", action="store_true", help="--full at N=1: skip the human data set's pass through this GPU after the timed region (scale_anchor_n1)")
+    ap.add_argument("--no-anchor-oracle", action="store_true", help="--full at N=1: skip the CPU oracle's pass over one shard of the human data set (scale_anchor_n1.shard_vs_oracle, ~30 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the ASCII, HPC-input and syncmer legs, the edge stage, the CPU baseline and its parity check, the "
+                         "scale anchor, the figures from recorded profiles, the stage timers, the exchange figures and anchors of the N>1 lines, and the check against "
+                         "tests/golden/bench_counts.json.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--plain", action="store_true", help="with --full: still only the warm-up and the timed steps (no ASCII legs, no edge stage, no CPU leg): for profiler runs, "
+                    "where every launch should be one of the timed kind")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the node table of the last step (a fixed seeded sample of its rows when large) as float64 .npy files into DIR")
     ap.add_argument("--force-dist", action="store_true", help="use the routed multi-GPU path even with one rank")
     ap.add_argument("--dist-mode", choices=["replicate", "route"], default="replicate",
                     help="multi-GPU mode: exchange of sketch hashes + key-partitioned table (default inside a node: 3.5x faster per rank and fewer bytes than records up to ~10 ranks, DESIGN.md 3.4), or all-to-all of k-min-mer records by key range (the north star's wording)")
@@ -92,6 +105,9 @@ def parse():
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    a.plain = a.plain or not a.full
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         self_launch(a.gpus, a.comm)            # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -100,6 +116,8 @@ def parse():
                          "torch.distributed.run --nproc-per-node N with the same N" % (a.gpus, world))
     if a.dist_mode == "route":
         a.dist_impl = "py"                     # the record routing exists in the Python harness only
+    if a.dump_outputs and (world > 1 or a.force_dist) and a.dist_impl != "c":
+        ap.error("--dump-outputs: the Python harness returns no node table (use --dist-impl c)")
     if a.workload == "auto":
         a.workload = "human" if world > 1 and a.dist_impl == "c" else "fly"      # (the Python harness drives one batch per step: fly)
     human = a.workload == "human"
@@ -161,8 +179,9 @@ def n1_same_workload(args):
 
 
 def self_launch(n, comm="rccl"):
-    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) under torch.distributed.run on this node and become
-    that launcher.  Fewer than N visible GPUs is an error, not an N=1 run."""
+    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) under torch.distributed.run on this node as a child process and
+    exit with its status.  Fewer than N visible GPUs is an error, not an N=1 run.  (Not exec: this process has opened the GPU to count the devices, and
+    replacing a process that holds the device with another program is not safe under the ROCm driver.)"""
     import socket
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -176,7 +195,9 @@ def self_launch(n, comm="rccl"):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.run(cmd).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)          # (killed by a signal: the shell's convention)
 
 
 def pmc_traffic(bases_per_launch, args, fmt=None):
@@ -247,6 +268,64 @@ def issue_roofline(args, roof, n_cus):
 def hex_digest(dg):
     """the order-free digest of a node table {(key, abundance)} (include/mdbg_hip.h, mdbg_nodes_digest; oracle/mdbg_oracle.cpp, orc_node_hash) as two hex words: sum, xor"""
     return None if dg is None else ["0x%016x" % (int(dg[0]) & 0xFFFFFFFFFFFFFFFF), "0x%016x" % (int(dg[1]) & 0xFFFFFFFFFFFFFFFF)]
+
+
+DUMP_BYTES = 60 << 20         # --dump-outputs: the sampled rows of the node table (the counts and the digest add a few hundred bytes: under 64 MB in all)
+DUMP_SEED = 20240521
+DUMP_CHUNK_BYTES = 64 << 20   # device memory copied to the host at a time while the sampled rows are gathered
+
+
+def dump_outputs(out_dir, nd, to_host, digest, counts, prefix="", budget=DUMP_BYTES, extra=None):
+    """--dump-outputs: the node table `nd` (mdbg_nodes, DEVICE pointers) as float64 .npy files in out_dir, rows in DbgEntry.index order (unique per node, so
+    the order does not depend on where the table put a row): every row, or a fixed seeded sample of the rows when they would exceed `budget` bytes.  A u64 key
+    is split into its high and low 32-bit halves (keys_hi32 / keys_lo32: exact in float64); the other u64 columns are read ordinals and offsets (< 2^53).
+    Beside them: node_digest = the table's order-free digest (sum, xor) as four 32-bit halves, node_counts = `counts`, and one file per entry of `extra`
+    (name -> small numeric array).  to_host(ptr, nbytes, dtype) copies device memory to a numpy array; digest() returns the (sum, xor) pair of the whole table."""
+    import ctypes
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, k = int(nd.n), int(nd.k)
+    cols = (("keys", nd.keys, k, np.uint64), ("index", nd.index, 1, np.uint32), ("abundance", nd.abundance, 1, np.uint16), ("seqlen", nd.seqlen, 1, np.uint32),
+            ("shift", nd.shift, 2, np.uint16), ("shift_full", nd.shift_full, 2, np.uint64), ("src_read", nd.src_read, 1, np.uint64),
+            ("src_start", nd.src_start, 1, np.uint64), ("src_end", nd.src_end, 1, np.uint64), ("reversed", nd.reversed, 1, np.uint8))
+    floats_per_row = 2 * k + sum(w for name, _, w, _ in cols if name != "keys")
+    cap = max(1, budget // (8 * floats_per_row))
+
+    def addr(p):
+        return ctypes.cast(p, ctypes.c_void_p).value
+
+    index = to_host(addr(nd.index), n * 4, np.uint32) if n else np.zeros(0, np.uint32)
+    chosen = np.argsort(index, kind="stable")              # device rows in index order
+    if n > cap:
+        chosen = chosen[np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))]
+    rows = np.sort(chosen)                                 # the same rows in device order: read chunk by chunk
+    back = np.argsort(index[rows], kind="stable")          # ... and put in index order
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    for name, p, w, dt in cols:
+        a = np.zeros((len(rows), w), dt)
+        row = w * np.dtype(dt).itemsize
+        step = max(1, DUMP_CHUNK_BYTES // row)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            i, j = np.searchsorted(rows, [lo, hi])
+            if i < j:
+                a[i:j] = to_host(addr(p) + lo * row, (hi - lo) * row, dt).reshape(hi - lo, w)[rows[i:j] - lo]
+        a = a[back]
+        if name == "keys":
+            save("keys_hi32", a >> np.uint64(32))
+            save("keys_lo32", a & np.uint64(0xFFFFFFFF))
+            continue
+        if dt == np.uint64 and len(a) and int(a.max()) >= 1 << 53:
+            raise ValueError("--dump-outputs: %s holds a value float64 cannot carry exactly" % name)
+        save(name, a[:, 0] if w == 1 else a)
+    s, x = (int(v) & 0xFFFFFFFFFFFFFFFF for v in digest())
+    save("node_digest", [s >> 32, s & 0xFFFFFFFF, x >> 32, x & 0xFFFFFFFF])
+    save("node_counts", counts)
+    for name, a in (extra or {}).items():
+        save(name, a)
 
 
 def cpu_baseline(m_ctx, d_bases, d_off, n_reads, n_bases, args):
@@ -445,12 +524,12 @@ def main():
             words = torch.zeros((nb + 31) // 32 + 2, dtype=torch.int64, device="cuda")
             exc = (torch.zeros(64, dtype=torch.int64, device="cuda"), torch.zeros(64, dtype=torch.uint8, device="cuda"))
             torch.cuda.synchronize()      # the fills above ran on torch's stream, the packer runs on the context's
-            for _ in range(2):            # (second pass timed: what the device packer costs on top of a step that starts from ASCII)
+            for _ in range(2 if args.full else 1):            # (--full: second pass timed: what the device packer costs on top of a step that starts from ASCII)
                 m.sync()
                 t1 = time.perf_counter()
                 assert m.pack_device(d_bases, nb, words.data_ptr(), exc[0].data_ptr(), exc[1].data_ptr(), 64) == 0      # synthetic reads are pure ACGT
                 m.sync()
-                pack_ms = (time.perf_counter() - t1) * 1e3
+                pack_ms = (time.perf_counter() - t1) * 1e3 if args.full else None
             keep += [words, exc]
             d_in = words.data_ptr()
         batches.append((d_in, d_off0, reads_per_gpu, nb, rank * reads_per_gpu))
@@ -514,8 +593,10 @@ def main():
                 if cdist is not None:
                     nd, _, ng = cdist.finalize()
                     cdist.last_local = int(nd.n)
+                    last_nd["dist"] = nd
                 else:
-                    ng = int(m.finalize_device().n)
+                    last_nd["local"] = m.finalize_device()
+                    ng = int(last_nd["local"].n)
                 per_k.append((k, int(ng)))
             return per_k[-1][1]
         if cdist is not None:
@@ -575,6 +656,22 @@ def main():
         total_bases, n_ranks = n_bases, 1
     if n_ranks != args.gpus:
         raise SystemExit("bench.py: --gpus %d but %d rank(s) took part in the all-reduce" % (args.gpus, n_ranks))
+    if args.dump_outputs:    # what the last timed step handed its caller: this rank's node table (a partition at N > 1), before anything below touches the context
+        nd = last_nd["dist" if cdist is not None else "local"]
+        if cdist is None:
+            to_host, digest = m.to_host, (lambda: m.nodes_digest(nd))
+        else:                          # (the partition belongs to the layer's own context: a copy waits for that context's stream)
+            ctx_h = cdist.L.mdbg_dist_ctx(cdist.h)
+
+            def to_host(p, nbytes, dt):
+                a = np.empty(nbytes // np.dtype(dt).itemsize, dt)
+                assert cdist.L.mdbg_copy_to_host(ctx_h, a.ctypes.data, p, a.nbytes) == 0
+                return a
+
+            def digest():
+                return cdist.nodes_digest(nd)
+        dump_outputs(args.dump_outputs, nd, to_host, digest, [n_nodes, nd.n, nd.n_distinct, nd.n_wrapped], prefix="rank%d_" % rank if world > 1 else "",
+                     budget=DUMP_BYTES // world, extra={"nodes_per_k": per_k} if args.multik else None)
     # outside the timed region: the order-free digest of the node table the last timed step left on the device — of every rank's partition at N > 1, folded over the
     # ranks (sum mod 2^64, XOR): the digest of the UNION of the partitions, comparable with the one-GPU table's and with the CPU oracle's (cpu_baseline)
     node_digest = None
@@ -601,7 +698,7 @@ def main():
         loc = int(allreduce([(cdist if cdist is not None else runner).last_local], torch.int64)[0])
         consistent = bool(loc == int(n_nodes))
     exchange = None
-    if cdist is not None:    # what went over the links in the last step, and how even the partition is (mdbg_dist_traffic; outside the timed region)
+    if cdist is not None and args.full:    # what went over the links in the last step, and how even the partition is (mdbg_dist_traffic; outside the timed region)
         try:
             b_in, b_out, n_q = cdist.traffic()
         except Exception as ex:          # (a side measurement; every rank still joins the all-reduces below)
@@ -629,7 +726,7 @@ def main():
                     "nodes_busiest_rank_over_mean": (float(tmax[1]) * world / float(tsum[1])) if int(tsum[1]) else None,
                     "transport": "host-staged over gloo (--comm host: DRY RUN, not RCCL)" if host_comm else "RCCL (grouped ncclSend / ncclRecv inside libmdbg_hip.so)"}
     anchor = None
-    if cdist is not None and not args.multik:    # outside the timed region: what the same ranks do WITHOUT the exchange — every rank pushes its own shards through one local context
+    if cdist is not None and not args.multik and args.full:    # outside the timed region: what the same ranks do WITHOUT the exchange — every rank pushes its own shards through one local context
         # (table not partitioned).  N x this rate is the ceiling on this node for this split of the data.
         t_loc = -1.0
         try:
@@ -651,12 +748,12 @@ def main():
         if t_min > 0:
             anchor = {"what": "the same %d rank(s), each pushing its own %d batch(es) through one local context: no exchange, table not partitioned (after the timed region; "
                               "slowest rank)" % (world, len(batches)), "value": total_bases / t_max / 1e9, "unit": "Gbases/s", "ms_per_step": t_max * 1e3}
-    # one more step with the stage timers on (outside the timed region): its stage times are the line's stage_ms_last_step
-    for ctx_ in ([m] + ([cdist] if cdist is not None else [])):
-        ctx_.set_timing(2)
-    if not args.multik and (cdist is not None or not routed):
-        step()
-        fence()
+    if args.full:            # one more step with the stage timers on (outside the timed region): its stage times are the line's stage_ms_last_step
+        for ctx_ in ([m] + ([cdist] if cdist is not None else [])):
+            ctx_.set_timing(2)
+        if not args.multik and (cdist is not None or not routed):
+            step()
+            fence()
     st = m.stats()          # stats of the last step only (reset clears the timers)
     if cdist is not None:
         m_stats = api_stats_of(cdist)
@@ -711,7 +808,7 @@ def main():
                 side_errors[name] = repr(ex)[:300]
                 print("bench.py: side measurement %s failed: %r" % (name, ex), file=sys.stderr)
                 return default
-        if roof:
+        if roof and args.full:
             roof["traffic"], roof["traffic_source"] = side("pmc_traffic", lambda: pmc_traffic(st["n_sketch_tile_bases"] / st["n_sketch_tile_launches"], args), (None, None))
             roof["issue"] = side("issue_roofline", lambda: issue_roofline(args, roof, torch.cuda.get_device_properties(device_index).multi_processor_count)) if packed else None
             sq = side("sq_counters", lambda: sq_counters(args))
@@ -812,7 +909,7 @@ def main():
                 if w3 and args.minabund == 2 and any(anchor1["graph"][f] != w3[0]["graph"][f] for f in w3[0]["graph"]):
                     raise SystemExit("bench.py: the graph of the scale anchor %r differs from the recorded one %r: no line printed" % (anchor1["graph"], w3[0]["graph"]))
         n1_same = None
-        if human and world > 1:
+        if human and world > 1 and args.full:
             # the N=1 point of the same curve: measured in THIS run on rank 0's GPU when the ranks have a device each (the whole data set streamed through one local context
             # while the other ranks wait: the same box, the same day, the same code as the N>1 value above it); a dry run on a shared device, or a failure, falls back to
             # the committed N=1 line of the same workload (another box: the pool's boxes differ by a few per cent)
@@ -833,7 +930,7 @@ def main():
             if not cpu["matches_gpu"]:
                 raise SystemExit("bench.py: the oracle finds %d nodes / %d windows / node digest %s on the whole workload, the GPU %d / %d / %s: no line printed"
                                  % (cpu["nodes"], cpu["windows"], cpu["node_digest"], graph["nodes"], graph["windows"], node_digest))
-        want = expected_graph(args, world, shard_reads, total_bases)
+        want = expected_graph(args, world, shard_reads, total_bases) if args.full else None
         if args.multik:
             graph["nodes_per_k"] = [list(x) for x in per_k]
         if want is not None and not os.environ.get("MDBG_STOP_PHASE") and any(graph[f] != want[f] for f in want):
@@ -864,7 +961,7 @@ def main():
                "dtype": "u64", "data": "synthetic",
                "config": {"workload": wl, "workload_key": args.workload + ("-multik" if args.multik else ""), "multik": MULTIK if args.multik else None, "k": args.k, "l": args.l, "density": args.density, "minabund": args.minabund,
                           "genome_mb": args.genome_mb, "coverage": args.coverage, "reads_per_gpu": reads_per_gpu,
-                          "bases_per_gpu": n_bases, "batches_per_step": len(batches), "total_bases": total_bases, "input_format": args.input, "plain": bool(args.plain),
+                          "bases_per_gpu": n_bases, "batches_per_step": len(batches), "total_bases": total_bases, "input_format": args.input, "plain": bool(args.plain), "full": bool(args.full),
                           "input": "2-bit packed (two 32-bit planes per 32 bases) resident in HBM" if packed else "ASCII resident in HBM", "parallelism": par,
                           "comm": None if not routed else ("host-staged over gloo: DRY RUN, not RCCL" if host_comm else "rccl")},
                "roofline": roof, "roofline_ascii": roof_ascii, "roofline_hpc_input": roof_hpc, "syncmers": sync_leg, "ascii_in": ascii_in,
@@ -872,7 +969,7 @@ def main():
                "cpu_baseline": cpu, "multik_graph_gbases_per_s": multik_graph_rate, "multik_graphs_per_s": (len(MULTIK) * args.steps / dt) if args.multik else None,
                "stage_ms_last_step": {"sketch": st["ms_sketch"], "sketch_bs_kernel": st["ms_sketch_tile"], "insert": st["ms_insert"], "finalize": st["ms_finalize"],
                                       "measured_in": "one further step after the timed region with the stage events on (mdbg_set_timing(2)); the timed steps record the tile kernel's events only"
-                                                     if timed_level == 1 else "the last timed step (stage events on in the timed region: MDBG_BENCH_STAGE_EVENTS)"},
+                                                     if timed_level == 1 else "the last timed step (stage events on in the timed region: MDBG_BENCH_STAGE_EVENTS)"} if args.full else None,
                "graph": {"minimizers": st["n_minimizers"], "windows": st["n_windows"], "distinct": st["n_distinct"], "nodes": int(n_nodes), "node_digest": node_digest,
                          "checked_against_recorded_counts": want is not None, "digest_checked_against_recorded": bool(want is not None and "node_digest" in want),
                          "slow_tiles": st["n_slow_tiles"], "tiles": st["n_tiles"], "table_capacity": st["table_capacity"],

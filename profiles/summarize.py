@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Condenses a rocprofv3 output set (gpurun_out/pN/{stats,fetch,write}) into the summaries committed under profiles/.
 
-  stats : rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 3 --warmup 1 --cpu-seconds 0
-  fetch : rocprofv3 --kernel-trace --pmc FETCH_SIZE ...   -- python bench.py --steps 1 --warmup 1 --cpu-seconds 0
+  stats : rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0
+  fetch : rocprofv3 --kernel-trace --pmc FETCH_SIZE ...   -- python bench.py --full --steps 1 --warmup 1 --cpu-seconds 0
   write : rocprofv3 --kernel-trace --pmc WRITE_SIZE ...   (separate pass: FETCH_SIZE takes 3 and WRITE_SIZE 2 of the 4 TCC slots)
 HBM bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: both counters are in KB, and on gfx950 FETCH_SIZE reports
 half of the bytes of a wide (16 B/lane) coalesced streaming read (MI355X_MICROARCH.md, HBM section).
@@ -28,7 +28,7 @@ def counters(path, name):
 
 def main(d, out):
     with open(out + "_kernel_stats.txt", "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --cpu-seconds 0   (durations in microseconds)\n")
+        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0   (durations in microseconds)\n")
         f.write("%-48s %6s %12s %12s %12s %7s\n" % ("kernel", "calls", "avg_us", "min_us", "max_us", "pct"))
         for r in csv.DictReader(open(d + "/stats/s_kernel_stats.csv")):
             f.write("%-48s %6s %12.1f %12.1f %12.1f %6s%%\n" % (r["Name"].split("(")[0].replace("void ", "")[:48], r["Calls"], float(r["AverageNs"]) / 1e3,

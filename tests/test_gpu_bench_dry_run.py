@@ -10,21 +10,43 @@ import pytest
 from conftest import ROOT
 
 
-def _bench(*flags, **extra_env):
+def _bench(*flags, full=True, **extra_env):
+    """one bench.py run -> its line; full: with --full (what the tests below read beside the headline is measured there only)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(flags), capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + list(flags), capture_output=True, text=True, env=env,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
 
 
+def _dumped(d, prefix=""):
+    """the .npy files a run wrote with --dump-outputs d (those of one rank: prefix) -> {name: array}"""
+    import numpy as np
+    out = {}
+    for f in sorted(os.listdir(d)):
+        if f.startswith(prefix) and f.endswith(".npy") and (prefix or not f.startswith("rank")):
+            out[f[len(prefix):-4]] = np.load(os.path.join(d, f))
+    return out
+
+
+def _digest_words(x):
+    """node_digest.npy (four 32-bit halves) -> (sum, xor)"""
+    h = [int(v) for v in x["node_digest"]]
+    return (h[0] << 32) | h[1], (h[2] << 32) | h[3]
+
+
+def _digest_hex(dg):
+    return ["0x%016x" % (int(v) & 0xFFFFFFFFFFFFFFFF) for v in dg]
+
+
 @pytest.mark.gpu
-def test_bench_two_ranks_dry_run_matches_one_rank():
+def test_bench_two_ranks_dry_run_matches_one_rank(tmp_path):
     small = ["--workload", "human", "--genome-mb", "40", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"]
     one = _bench("--gpus", "1", *small)
-    two = _bench("--gpus", "2", "--comm", "host", *small)
+    two = _bench("--gpus", "2", "--comm", "host", "--dump-outputs", str(tmp_path), *small)
     assert one["n_gpus"] == 1 and one["config"]["batches_per_step"] == 8 and one["scaling"] == "strong"
     assert two["n_gpus"] == 2 and two["config"]["batches_per_step"] == 4 and two["scaling"] == "strong"
     assert two["config"]["total_bases"] == one["config"]["total_bases"] and 2 * two["config"]["bases_per_gpu"] != 0
@@ -36,6 +58,10 @@ def test_bench_two_ranks_dry_run_matches_one_rank():
     assert two["no_exchange_anchor"] and two["no_exchange_anchor"]["value"] > 0
     assert "DRY RUN" in two["config"]["parallelism"] and "not RCCL" in two["config"]["comm"]
     assert two["roofline"]["kernel"] == "sketch_bs_kernel<14>" and one["roofline"]["launches_per_step"] == 8
+    # --dump-outputs at N > 1: every rank writes its own partition; the rows add up to the node count and the partitions' digests fold to the line's
+    d = [_dumped(tmp_path, "rank%d_" % r) for r in range(2)]
+    assert sum(int(x["node_counts"][1]) for x in d) == two["graph"]["nodes"] and all(int(x["node_counts"][0]) == two["graph"]["nodes"] for x in d)
+    assert _digest_hex([sum(_digest_words(x)[0] for x in d), _digest_words(d[0])[1] ^ _digest_words(d[1])[1]]) == two["graph"]["node_digest"]
 
 
 @pytest.mark.gpu
@@ -68,7 +94,8 @@ def test_bench_refuses_the_line_when_one_abundance_differs():
     the digest is not — no line, a non-zero exit and the reason on stderr"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MDBG_BENCH_CORRUPT"] = "abundance"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--genome-mb", "20", "--steps", "2", "--warmup", "1", "--cpu-seconds", "60", "--no-scale-anchor"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--genome-mb", "20", "--steps", "2", "--warmup", "1", "--cpu-seconds", "60",
+                        "--no-scale-anchor"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode != 0 and not [ln for ln in r.stdout.splitlines() if ln.strip()], (r.returncode, r.stdout[-500:])
     assert "no line printed" in r.stderr and "node digest" in r.stderr, r.stderr[-2000:]
@@ -133,3 +160,22 @@ def test_bench_eight_ranks_dry_run_matches_one_rank():
     assert lay["rounds_per_step"] == 2.0 and set(lay["slowest_rank"]) == set(lay["mean"]) and lay["slowest_rank"]["sketch"] > 0 and lay["slowest_rank"]["insert"] > 0
     assert all(lay["slowest_rank"][s_] >= lay["mean"][s_] - 1e-9 for s_ in lay["mean"])
     assert eight["exchange"]["budget_ms_per_step_8_ranks_human"]["sum"][0] > 10 and eight["exchange"]["nodes_busiest_rank_over_mean"] < 1.1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full: the timed steps and the line, no side legs; --dump-outputs writes the last timed step's node table, the same in two runs, and its
+    counts and digest are the line's"""
+    import numpy as np
+    small = ["--gpus", "1", "--genome-mb", "20", "--steps", "3", "--warmup", "1"]
+    a = _bench(*small, "--dump-outputs", str(tmp_path / "a"), full=False)
+    b = _bench(*small, "--dump-outputs", str(tmp_path / "b"), full=False)
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["value"] > 0 and a["unit"] == "Gbases/s" and a["higher_is_better"] is True
+    assert a["config"]["full"] is False and a["roofline"]["launches_timed"] == 3
+    assert all(a[f] is None for f in ("cpu_baseline", "ascii_in", "roofline_hpc_input", "syncmers", "edges_after_timed_region", "scale_anchor_n1", "stage_ms_last_step"))
+    assert a["graph"]["nodes"] == b["graph"]["nodes"] > 1000 and a["graph"]["node_digest"] == b["graph"]["node_digest"]
+    da, db = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert set(da) == set(db) and all(da[f].dtype == np.float64 and np.array_equal(da[f], db[f]) for f in da)
+    assert int(da["node_counts"][0]) == a["graph"]["nodes"] and _digest_hex(_digest_words(da)) == a["graph"]["node_digest"]
+    n = len(da["index"])
+    assert 0 < n <= a["graph"]["nodes"] and np.all(np.diff(da["index"]) > 0) and da["keys_hi32"].shape == (n, 35) and da["abundance"].min() >= 2
