@@ -62,7 +62,7 @@ def classify(mn, ops, line):
 
 def parse_kernel(path, l):
     txt = open(path).read()
-    head = "_Z16sketch_bs_kernelILi%dELi0ELi1ELi4ELi1EEv10SketchArgs:" % l
+    head = "_Z16sketch_bs_kernelILi%dELi0ELi1EEv10SketchArgs:" % l
     i = txt.index(head)
     body = txt[i:]
     body = body[:body.index(".Lfunc_end")]
@@ -113,7 +113,7 @@ def build_probe(l, asm):
     a = t.index(stamp); b = t.index("\n", a)
     t = t[:a] + '#define MDBG_STAMP(i) asm volatile("s_nop 0 ; MDBG_PHASE_MARK " #i ::: "memory")' + t[b:]
     open(p, "w").write(t)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-DMDBG_ONLY_L=%d" % l,
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
                            "-o", asm, "libmdbg.hip"], cwd=work, stderr=subprocess.DEVNULL)
     shutil.rmtree(tmp, ignore_errors=True)
     return asm

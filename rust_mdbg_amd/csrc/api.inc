@@ -255,25 +255,22 @@ int read_scalars(mdbg_ctx* c, u64* host, bool with_fin = false, bool zero_batchw
     launch_publish_scalars(pa, c->stream);
     // the kernel's last store is the sequence number: poll it (a few microseconds after the store) rather than wait for the runtime to see
     // the queue's completion signal; whatever goes wrong on the device ends the wait through the stream's status
-    static const bool no_poll = getenv("MDBG_NO_POLL") != nullptr;
     volatile u64* const flag = c->h_scal + SC_N;
     // A short busy poll (what a step of a few milliseconds waits for arrives within it), then polls that give the core away in between (a rank behind a
     // long kernel must not burn a core its reader and packer threads want), then the runtime's own wait.
     bool seen = false;
-    if (!no_poll) {
-        const double t0 = now_ms();
-        for (u32 spins = 0; !seen; ++spins) {
-            seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
-            if (seen) break;
+    const double t0 = now_ms();
+    for (u32 spins = 0; !seen; ++spins) {
+        seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
+        if (seen) break;
 #if defined(__x86_64__)
-            __builtin_ia32_pause();
+        __builtin_ia32_pause();
 #endif
-            if ((spins & 0x3FFu) != 0x3FFu) continue;
-            const double waited = now_ms() - t0;
-            if (waited > 0.3) std::this_thread::yield();
-            if (waited > 20.0) break;
-            if ((spins & 0xFFFFu) == 0xFFFFu) { const hipError_t q = hipStreamQuery(c->stream); if (q != hipErrorNotReady) break; }
-        }
+        if ((spins & 0x3FFu) != 0x3FFu) continue;
+        const double waited = now_ms() - t0;
+        if (waited > 0.3) std::this_thread::yield();
+        if (waited > 20.0) break;
+        if ((spins & 0xFFFFu) == 0xFFFFu) { const hipError_t q = hipStreamQuery(c->stream); if (q != hipErrorNotReady) break; }
     }
     if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(host, c->h_scal, SC_N * 8);
@@ -487,8 +484,7 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
     if (first_ordinal + n_reads >= (1ull << (64 - WIN_BITS))) return fail(c, MDBG_E_CAPACITY, "read ordinal too large");
     hipStream_t s = c->stream;
     const bool sync = c->P.scheme == MDBG_SCHEME_SYNCMERS;
-    const TileShape shape = tile_shape_for(sync ? 1u : 0u);
-    const u64 tile_bases = (u64)shape.stride;
+    const u64 tile_bases = TILE_STRIDE;
     const u64 n_tiles_total = (n_bases + tile_bases - 1) / tile_bases;
     if (n_tiles_total >= 0x7FFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "batch too large for one call");
     u32 slot0 = 0;
@@ -500,7 +496,7 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
     {
         // syncmers: about one l-mer in l-s+1 has its smallest s-mer in the middle, of which a fraction `density` survives
         const double per_base = sync ? std::min(1.0, std::max(0.0, c->P.density)) / (c->P.syncmer_s ? std::max(1.0, (double)(c->P.l - c->P.syncmer_s + 1) / 2.0) : 1.0) : dens2;
-        const double e = (double)tile_bases * per_base; double v = e * 1.25 + 6.0 * sqrt(e) + (shape.nw == 1 ? 16.0 : 32.0); if (v > (double)tile_bases) v = (double)tile_bases; slab_cap = ((u32)v + 7u) & ~7u;
+        const double e = (double)tile_bases * per_base; double v = e * 1.25 + 6.0 * sqrt(e) + 32.0; if (v > (double)tile_bases) v = (double)tile_bases; slab_cap = ((u32)v + 7u) & ~7u;
         // small tiles: one gather wave takes several (about 256 expected records)
         if (e < 128.0) gather_tiles = (u32)std::max(1.0, std::min(16.0, 256.0 / std::max(e, 1.0)));
     }
@@ -542,8 +538,7 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
         init0.zero[0] = scal(c) + SC_ERRFLAG; init0.zero[1] = scal(c) + SC_SLOWTOTAL; init0.zero[2] = scal(c) + SC_OVERMAX; init0.set_p = scal(c) + SC_CARRY; init0.set_v = c->M;
         // the insertion can ride behind this sketch when its grid can be sized without the count: the store's free room is the bound, and it must not be
         // much more than the batch is expected to fill (a store sized for many batches would launch mostly idle workgroups)
-        static const bool no_fuse = getenv("MDBG_NO_FUSE") != nullptr;      // (A/B switch)
-        const bool fused = !no_fuse && then_insert && inserted && n_tiles_total && part_end.size() == 1 && !phase_dbg && c->cap && c->own_world <= 1 && !c->lmer_on && !c->routed && !c->pending_m &&
+        const bool fused = then_insert && inserted && n_tiles_total && part_end.size() == 1 && !phase_dbg && c->cap && c->own_world <= 1 && !c->lmer_on && !c->routed && !c->pending_m &&
                            c->batches_inserted == c->batches.size() && c->mcap > c->M && c->mcap - c->M <= 2 * (want - c->M) + (1u << 20) &&
                            want - c->M <= (48ull << 20);          // (larger rounds are inserted in slices, insert_resident_impl)
         if (fused) init0.zero[3] = scal(c) + SC_BATCHWIN;
@@ -572,13 +567,12 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
             // the first level of the gather's scan is accumulated by the tiles themselves (SketchArgs::block_sum; zeroed by the kernel that prepares the tile records)
             const u32 n_gran = (u32)((max_part + SCAN_GRAN - 1) / SCAN_GRAN);
             HIPCHK(c, c->gran_sum.ensure((size_t)n_gran * 8 + 64, 0, s));
-            static const bool no_tile_sums = getenv("MDBG_NO_TILE_SUMS") != nullptr;      // (A/B switch: the scan's first level by a kernel of its own, as until round 5)
-            A.block_sum = no_tile_sums ? nullptr : (unsigned long long*)c->gran_sum.as<u64>();
+            A.block_sum = (unsigned long long*)c->gran_sum.as<u64>();
             init0.zero_arr = c->gran_sum.as<u64>(); init0.zero_arr_n = n_gran;
-            launch_bread(d_offsets, (u32)n_reads, n_bases, A.n_tiles, c->bread.as<u32>(), c->tile_recs.as<TileRec>(), init0, shape, s);
+            launch_bread(d_offsets, (u32)n_reads, n_bases, A.n_tiles, c->bread.as<u32>(), c->tile_recs.as<TileRec>(), init0, s);
             if (in.n_exc) {
                 HIPCHK(c, hipMemsetAsync(c->tile_flags.p, 0, n_tiles_total, s));
-                launch_tile_flags(in.d_exc_pos, (u32)in.n_exc, A.n_tiles, c->tile_flags.as<u8>(), shape, s);
+                launch_tile_flags(in.d_exc_pos, (u32)in.n_exc, A.n_tiles, c->tile_flags.as<u8>(), s);
             }
             if (sync) {
                 A.scheme = 1; A.s = c->P.syncmer_s; A.btop = 0;
@@ -592,13 +586,13 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
                 Rec* const part_slab = c->slab.as<Rec>();
                 A.tile0 = (u32)t0; A.slab = part_slab;
                 if (pi) HIPCHK(c, hipMemsetAsync(c->gran_sum.p, 0, (size_t)n_gran * 8, s));      // (several launches per batch — dense settings —: the next launch's sums start from zero)
-                { hipEvent_t tb = next_tile_event(c), te = next_tile_event(c); launch_sketch(A, nt, shape, s, tb, te); }
+                { hipEvent_t tb = next_tile_event(c), te = next_tile_event(c); launch_sketch(A, nt, s, tb, te); }
                 GatherArgs G{};
                 G.tile0 = (u32)t0; G.n = nt; G.slab = part_slab; G.slab_cap = slab_cap; G.n_valid = A.n_valid; G.n_scan = A.n_scan; G.last_read = A.last_read;
                 G.out_hash = c->mh.as<u64>(); G.out_pos = c->mpos.as<u32>(); G.out_read = c->mread.as<u32>(); G.out_cap = c->mcap;
                 G.m0 = c->M; G.slot0 = slot0; G.n_reads = (u32)n_reads; G.off = c->roff.as<u64>(); G.last_launch = pi + 1 == part_end.size() ? 1u : 0u;
                 G.tiles_per_wave = gather_tiles;
-                launch_gather(G, c->scan_tmp.as<u64>(), c->tile_base.as<u64>(), scal(c) + SC_CARRY, s, A.block_sum ? c->gran_sum.as<u64>() : nullptr);
+                launch_gather(G, c->scan_tmp.as<u64>(), c->tile_base.as<u64>(), scal(c) + SC_CARRY, s, c->gran_sum.as<u64>());
                 c->n_tile_launches += 1;
                 t0 = part_end[pi];
             }
@@ -813,12 +807,17 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
     for (;;) {
         launch_reserve_check(c->shards.as<u64>(), scal(c) + SC_NDISTINCT, scal(c) + SC_BATCHWIN, c->cap, flags + 1, s);
         STAGE_EVENT(c, c->ev0, s);
+        // a listed batch's pairs and their segments in own_lists; per_entry: launch_insert_listed takes the per-entry kernel for it (the one decision behind the
+        // grouping, the claim bytes and the launch below)
+        auto list_of = [&](const Batch& b) { return c->own_lists.as<u32>() + b.list_off; };
+        auto seg_of = [&](const Batch& b) { return c->own_lists.as<u32>() + b.list_off + 2 * b.owned; };
+        auto per_entry = [&](const Batch& b) { return listed_per_entry(table_args(c), b.m0, b.m1, b.owned, seg_of(b) != nullptr); };
         // thinly listed batches (a rank's share of the peers' sketches at 4+ ranks) share ONE launch
         std::vector<ListedBatch> multi; u64 multi_total = 0;
         for (size_t i = first; i < last; ++i) {
             const Batch& b = c->batches[i];
-            if (b.list_off != ~0ull && b.owned != ~0ull && b.owned && c->own_world > 1 && listed_is_sparse(table_args(c), b.m0, b.m1, b.owned)) {
-                ListedBatch lb{}; lb.start = multi_total; lb.m0 = b.m0; lb.m1 = b.m1; lb.first_ordinal = b.first_ordinal; lb.list = c->own_lists.as<u32>() + b.list_off;
+            if (b.list_off != ~0ull && b.owned != ~0ull && b.owned && c->own_world > 1 && per_entry(b)) {
+                ListedBatch lb{}; lb.start = multi_total; lb.m0 = b.m0; lb.m1 = b.m1; lb.first_ordinal = b.first_ordinal; lb.list = list_of(b);
                 lb.slot0 = b.slot0; lb.n_reads = b.n_reads;
                 multi.push_back(lb); multi_total += b.owned;
             }
@@ -829,7 +828,7 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
         if (c->claims_ok && c->claim.p && c->own_world > 1)
             for (size_t i = first; i < last; ++i) {
                 const Batch& b = c->batches[i];
-                if (b.list_off != ~0ull && b.owned != ~0ull && b.m1 > b.m0 && (!b.owned || listed_is_sparse(table_args(c), b.m0, b.m1, b.owned)))
+                if (b.list_off != ~0ull && b.owned != ~0ull && b.m1 > b.m0 && (!b.owned || per_entry(b)))
                     HIPCHK(c, hipMemsetAsync(c->claim.as<u8>() + b.m0, 0, b.m1 - b.m0, s));
             }
         if (!multi.empty()) {
@@ -841,10 +840,9 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
         }
         for (size_t i = first; i < last; ++i) {
             const Batch& b = c->batches[i];
-            if (multi_total && b.list_off != ~0ull && b.owned != ~0ull && b.owned && c->own_world > 1 && listed_is_sparse(table_args(c), b.m0, b.m1, b.owned)) continue;      // went with the shared launch
+            if (multi_total && b.list_off != ~0ull && b.owned != ~0ull && b.owned && c->own_world > 1 && per_entry(b)) continue;      // went with the shared launch
             if (b.list_off != ~0ull && b.owned != ~0ull && c->own_world > 1)          // the sender listed this rank's windows: no scan of the foreign sketch
-                launch_insert_listed(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), b.m0, b.m1, c->own_lists.as<u32>() + b.list_off,
-                                     c->own_lists.as<u32>() + b.list_off + 2 * b.owned, b.owned, b.slot0, b.n_reads, b.first_ordinal, flags, s);
+                launch_insert_listed(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), b.m0, b.m1, list_of(b), seg_of(b), b.owned, b.slot0, b.n_reads, b.first_ordinal, flags, s);
             else
                 launch_insert_windows(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), b.m0, b.m1, b.slot0, b.first_ordinal,
                                       scal(c) + SC_NWINDOWS, flags, s);
@@ -871,13 +869,7 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
 extern "C" {
 
 uint32_t mdbg_abi_version(void) { return MDBG_ABI_VERSION; }
-uint32_t mdbg_build_flags(void) {
-    uint32_t f = 0;
-#ifdef MDBG_WAVE_TILES
-    f |= 1u;
-#endif
-    return f;
-}
+uint32_t mdbg_build_flags(void) { return 0; }
 static size_t host_cache_trim_fwd();
 uint64_t mdbg_release_cached_memory(void) { (void)host_cache_trim_fwd(); return (uint64_t)block_cache().trim(); }
 
@@ -1388,7 +1380,7 @@ int mdbg_get_stats(mdbg_ctx* c, mdbg_stats* o) {
     o->table_capacity = c->cap; o->n_slow_tiles = c->n_slow_tiles; o->n_tiles = c->n_tiles;
     o->ms_sketch = c->ms_sketch; o->ms_insert = c->ms_insert; o->ms_finalize = c->ms_finalize;
     o->ms_sketch_tile = c->ms_tile; o->n_sketch_tile_launches = c->n_tile_launches; o->n_sketch_tile_bases = c->n_tile_bases;
-    o->tile_bases = tile_shape_for(c->P.scheme == MDBG_SCHEME_SYNCMERS ? 1u : 0u).stride;
+    o->tile_bases = TILE_STRIDE;
     if (c->link_ctr.p) {
         (void)hipSetDevice(c->dev);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1468,7 +1460,7 @@ static int fin_setup(mdbg_ctx* c, FinArgs& F, u64& n_words_out, bool byte_maps =
                 for (u32 i = 0; i < nb && dense_is_store; ++i) dense_is_store = !bs[i].partial && rb[i] == bs[i].m0;
                 if (use_claims) {
                     F.claims = dense_is_store ? 1 : 2;
-                    F.by_first = c->claim.as<u8>(); F.by_solid = nullptr;          // one map: bit 0 first sighting, bit 1 solid (fin_mark_kernel); nothing to zero
+                    F.by_first = c->claim.as<u8>(); F.by_solid = nullptr;          // one map: bit 0 first sighting, bit 1 solid (fin_mark_claims_kernel); nothing to zero
                     z.n[0] = 0; z.n[1] = 0;                                        // (the bytes behind the store's end are masked by launch_bytes_to_bits: n_bits = M)
                 } else {
                     HIPCHK(c, c->by_maps.ensure(n_words * 128, 0, s));

@@ -41,11 +41,8 @@ typedef uint64_t bs_u64;
 
 // hash bits evaluated by the bit-sliced filter (top bits 63 .. 64-BS_B).  A tunable, not a switch: the filter is a NECESSARY condition (prefix(hash) <= prefix(bound)) and
 // every survivor is evaluated exactly, so any width gives the same minimizers; fewer planes = fewer filter instructions and more exact evaluations.  8 is the measured
-// optimum at the densities of BASELINE.json (profiles/r06_bs_b_sweep.txt: 6 .. 10 at d = 0.002 and 0.003); -DMDBG_BS_B=n builds another width.
-#ifndef MDBG_BS_B
-#define MDBG_BS_B 8
-#endif
-constexpr int BS_B = MDBG_BS_B;
+// optimum at the densities of BASELINE.json (profiles/r06_bs_b_sweep.txt: 6 .. 10 at d = 0.002 and 0.003).
+constexpr int BS_B = 8;
 static_assert(BS_B >= 3 && BS_B <= 12, "filter width");
 constexpr int BS_MAX_L = 32;
 

@@ -9,20 +9,14 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 // ---- tile geometry of the sketch kernel (sketch.hip) ----------------------------------------------
-// A tile is staged by NW waves of 64 lanes, four words of 32 raw bases per lane: HALO bases of look-back (owned by the tile in
-// front) followed by the STRIDE bases whose l-mer END positions the tile owns.  Two geometries are compiled:
-//   NW = 1  one WAVE per tile (8,192 bases staged, 128 of look-back): no workgroup barrier anywhere in the tile's life, the waves of
-//           a CU drift apart and their phases (compaction: VALU, filter: VALU + crossbar, exact evaluation: LDS + scalar) overlap;
-//   NW = 4  one 256-lane workgroup per tile (32,768 staged, 256 of look-back): rounds 1-3; still used by the syncmer scheme.
-// The host picks one per context (TileShape); everything behind the tile kernel (slabs, scans, gather) only sees tile counts.
-constexpr int TILE_WPT = 4;                       // raw words per lane
-template <int NW> struct TileGeo {
-    static constexpr int THREADS = 64 * NW;
-    static constexpr int RAW_WORDS = TILE_WPT * THREADS;
-    static constexpr int HALO_BASES = NW == 1 ? 128 : 256;
-    static constexpr int STRIDE = RAW_WORDS * 32 - HALO_BASES;       // NW = 4: 32,512 raw bases per tile; NW = 1: 8,064
-};
-struct TileShape { u32 nw, tpw, stride, halo; };   // tpw: tiles per workgroup of the launch (NW = 1: 1 or 4 waves per workgroup)
+// A tile is one 256-lane workgroup, four words of 32 raw bases per lane: TILE_HALO bases of look-back (owned by the tile in front) followed
+// by the TILE_STRIDE bases whose l-mer END positions the tile owns.  Everything behind the tile kernel (slabs, scans, gather) only sees tile
+// counts.  (One-wave tiles measured 7-9 % slower and were dropped: DESIGN.md §3.1, profiles/r04_b_tile_shapes_ab.txt.)
+constexpr int TILE_WPT = 4;                               // raw words per lane
+constexpr int TILE_THREADS = 256;
+constexpr int TILE_RAW_WORDS = TILE_WPT * TILE_THREADS;   // raw words staged per tile (halo included)
+constexpr int TILE_HALO = 256;
+constexpr int TILE_STRIDE = TILE_RAW_WORDS * 32 - TILE_HALO;      // 32,512 raw bases per tile
 constexpr int MDBG_MAX_L_DEV = 32;                // = MDBG_MAX_L of the C ABI
 
 // the table slots keep the A smallest ordinals of a k-min-mer for A up to this; larger min_abundance values get the A-th sighting from a
@@ -88,23 +82,9 @@ __device__ inline u32 block_excl_scan_256(u32 v, u32* tmp, u32& total) {
     return base + inc - v;
 }
 
-// ---- the same two primitives for a tile of NW waves --------------------------------------------------
-// NW = 1: the tile is one wave.  LDS instructions of one wave execute in issue order, so a store is visible to every later load of the
-// same wave whichever lane issued it: "barrier" = keep the compiler from moving LDS accesses across it, no instruction at all.
-template <int NW> __device__ __forceinline__ void tile_sync() {
-    if constexpr (NW == 1) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-    else __syncthreads();
-}
-template <int NW> __device__ __forceinline__ u32 tile_excl_scan(u32 v, u32* tmp, u32& total) {
-    if constexpr (NW == 1) {
-        const u32 inc = wave_incl_scan(v);
-        total = (u32)__builtin_amdgcn_readlane((int)inc, 63);
-        return inc - v;
-    } else {
-        static_assert(NW == 4, "block scan over 256 threads");
-        return block_excl_scan_256(v, tmp, total);
-    }
-}
+// the exclusive scan of a sketch tile (one 256-lane workgroup).  Always inlined: the tile kernel's code depends on the order in which the
+// compiler inlines the scan
+__device__ __forceinline__ u32 tile_excl_scan(u32 v, u32* tmp, u32& total) { return block_excl_scan_256(v, tmp, total); }
 
 // Sharded counters.  Same-address device atomics serialise at ~12 ns each on MI355X (MI355X_MICROARCH.md "fanin"), so
 // a hot counter is spread over CTR_SHARDS addresses chosen by (block, wave); sum_shards_kernel folds them when the

@@ -34,7 +34,8 @@ struct SketchArgs {
     const u32* bread;            // read containing the first staged base of tile t, [n_tiles + 2]
     const TileRec* recs;         // [n_tiles] (tile_rec_kernel)
     u32 n_tiles;
-    u32 tile0, tile_end;         // the launch runs the tiles [tile0, tile_end): workgroup b, tile slot ts -> tile tile0 + b * TPW + ts
+    u32 tile0, tile_end;         // the launch runs the tiles [tile0, tile_end): workgroup b -> tile tile0 + b (the grid is exactly these tiles: the kernel
+                                 // does not read tile_end, which keeps the argument layout the kernel was measured with)
     Rec* slab; u32 slab_cap;     // records of the launch's i-th tile: slab[i * slab_cap ..), in position order
     u32* n_valid;                // [n_tiles] number of minimizers whose l-mer ENDS in the tile
     u32* n_scan;                 // [n_tiles] slab slots the tile used when they are NOT all valid records (dense settings: rejected candidates
@@ -177,57 +178,41 @@ __device__ inline bool walk_lmer(const Src& s, u64 rlo, u64 p, u32 l, u64& start
 // ---- tile state in LDS ------------------------------------------------------------------------------------
 constexpr int WPT = TILE_WPT;                 // raw words per thread
 constexpr int DPAD = 4;                       // zero words in front of the dense stream (look-back of the first words)
-template <int NW> struct TG {                 // geometry of a tile staged by NW waves
-    static constexpr int TT = TileGeo<NW>::THREADS;
-    static constexpr int RW = TileGeo<NW>::RAW_WORDS;       // raw words staged per tile (halo included)
-    static constexpr int HALO = TileGeo<NW>::HALO_BASES;
-    static constexpr int HW = HALO / 32;                     // leading halo words
-    static constexpr int STRIDE = TileGeo<NW>::STRIDE;
-    static constexpr int QCAP = NW == 4 ? 704 : 176;         // candidates that fit the unordered list (evaluated in rounds of TT); more: the word-wise rounds
-    static constexpr int RS_CAP = NW == 4 ? 32 : 8;          // read starts of a tile kept in LDS (more: binary search in global memory)
-    static_assert(RW == WPT * TT && HW % WPT == 0 && HW % 2 == 0 && (RW - HW) % 2 == 0, "the halo is a whole number of threads; 16-byte aligned word pairs per thread");
-};
+constexpr int TILE_HW = TILE_HALO / 32;       // leading halo words
+constexpr int TILE_QCAP = 704;                // candidates that fit the unordered list (evaluated in rounds of TILE_THREADS); more: the word-wise rounds
+constexpr int TILE_RS_CAP = 32;               // read starts of a tile kept in LDS (more: binary search in global memory)
+static_assert(TILE_RAW_WORDS == WPT * TILE_THREADS && TILE_HW % WPT == 0 && TILE_HW % 2 == 0 && (TILE_RAW_WORDS - TILE_HW) % 2 == 0,
+              "the halo is a whole number of threads; 16-byte aligned word pairs per thread");
 
-template <int NW> struct __attribute__((aligned(16))) TileLds {
-    typedef TG<NW> G;
-    u32 dense[2 * (DPAD + G::RW + 4)];        // dense word D: planes at [2 * (DPAD + D)], [.. + 1]; during phases 1-2 the first RW
-                                              // words hold the read-start bitmap (every reader zeroes what it read)
-    u32 kw[G::RW];                            // keep mask of raw word w
-    u16 rpre[G::RW + 8];                      // kept bases in front of raw word w; [RW] = all
-    struct { u32 cand[G::RW + 8]; u16 cpre[G::RW + 8]; u16 list[G::QCAP]; u16 surv[G::TT]; } c;    // cpre doubles as the survivors' hashes (u64 x TT) before count_words
-    int64_t rs0;                              // start of read rl relative to the first staged position (may lie far in front of it)
-    int32_t rs_rel[G::RS_CAP];                // start of read rl + i, i >= 1, likewise (clamped to 2^31 - 1)
-    u32 misc[NW == 4 ? 32 : 24];              // [0..4] scan scratch, [8] slow, [11] Hh, [16] next round, [17] list fill, [18..20] survivors per round
-#ifdef MDBG_LDS_PAD
-    u32 pad_experiment[MDBG_LDS_PAD / 4];     // occupancy experiments only (scratch/build_variant.sh)
-#endif
+struct __attribute__((aligned(16))) TileLds {
+    u32 dense[2 * (DPAD + TILE_RAW_WORDS + 4)];       // dense word D: planes at [2 * (DPAD + D)], [.. + 1]; during phases 1-2 the first RW (= TILE_RAW_WORDS)
+                                                      // words hold the read-start bitmap (every reader zeroes what it read)
+    u32 kw[TILE_RAW_WORDS];                           // keep mask of raw word w
+    u16 rpre[TILE_RAW_WORDS + 8];                     // kept bases in front of raw word w; [RW] = all
+    struct { u32 cand[TILE_RAW_WORDS + 8]; u16 cpre[TILE_RAW_WORDS + 8]; u16 list[TILE_QCAP]; u16 surv[TILE_THREADS]; } c;    // cpre doubles as the survivors' hashes (u64 x TT) before count_words
+    int64_t rs0;                                      // start of read rl relative to the first staged position (may lie far in front of it)
+    int32_t rs_rel[TILE_RS_CAP];                      // start of read rl + i, i >= 1, likewise (clamped to 2^31 - 1)
+    u32 misc[32];                                     // [0..4] scan scratch, [8] slow, [11] Hh, [16] next round, [17] list fill, [18..20] survivors per round
 };
-constexpr int T3_WORDS = 2 << (2 * BS_GS);    // exact evaluation: 3-base groups {F, R}, one table per WORKGROUP (every wave writes the same values into it)
-template <int SCHEME, int NW> struct TileLdsS : TileLds<NW> {};
+constexpr int T3_WORDS = 2 << (2 * BS_GS);    // exact evaluation: 3-base groups {F, R}, one table per workgroup
+template <int SCHEME> struct TileLdsS : TileLds {};
 // syncmers: + a bitmap over DENSE positions (a read starts here).  The generic machine of a flagged tile keeps its ring of s-mer hashes (32 x 128 words: it runs on
 // half of the tile's threads) on top of the structure, which is dead by then — with a ring for all 256 threads the structure had to be padded to 32 KB and only four
 // workgroups fitted a CU
-template <int NW> struct TileLdsS<1, NW> : TileLds<NW> {
-    u32 dstart[TG<NW>::RW + 8];
+template <> struct TileLdsS<1> : TileLds {
+    u32 dstart[TILE_RAW_WORDS + 8];
 };
 constexpr int SYNC_SLOW_THREADS = 128;       // threads of a tile that run the generic syncmer machine: their ring (32 x 128 words = 16 KB) lies on top of the tile state, dead by then
-static_assert(sizeof(TileLdsS<1, 4>) >= 32 * SYNC_SLOW_THREADS * 4, "the ring of the generic syncmer machine fits the tile state");
+static_assert(sizeof(TileLdsS<1>) >= 32 * SYNC_SLOW_THREADS * 4, "the ring of the generic syncmer machine fits the tile state");
 // FMT_ASCII stages the half planes of its 16-base chunks (2 * RW words, phase 1 only) in memory that is idle then: the part of the dense
 // stream behind the read-start bitmap plus the keep masks (the stream part is zeroed again before phase 2 writes it)
-template <int NW> struct StageAt {
-    static constexpr int RW = TG<NW>::RW;
-    static constexpr int AT = 2 * (DPAD + RW + 4) + RW - 2 * RW;      // index into dense[]: the stage ends where kw[] ends
-    static_assert(AT >= RW && AT % 4 == 0 && offsetof(TileLds<NW>, kw) == sizeof(u32) * 2 * (DPAD + RW + 4), "stage = dense[AT ..) + kw[]");
-    static_assert((2 * (DPAD + RW + 4) - AT) == 4 * TG<NW>::TT, "one 16-byte store per thread");
-};
-// NW = 4: six workgroups per CU (22.8 KB each + the 1 KB table).  NW = 1: 5.9 KB per wave tile; four of them and one table per 256-lane workgroup
-// (24.6 KB: six per CU = 24 waves), or one per 64-lane workgroup (6.9 KB: 22 per CU).
-#ifndef MDBG_LDS_PAD
-static_assert((sizeof(TileLds<4>) + T3_WORDS * 8) * 6 <= 160 * 1024, "NW = 4: 6 workgroups per CU");
-static_assert((sizeof(TileLds<1>) * 4 + T3_WORDS * 8) * 6 <= 160 * 1024, "NW = 1, four tiles per workgroup: 6 workgroups per CU");
-#endif
-static_assert((TG<4>::RW + 8) * 2 >= TG<4>::TT * 8 && (TG<1>::RW + 8) * 2 >= TG<1>::TT * 8 && ((TG<1>::RW + 8) * 4) % 8 == 0 && offsetof(TileLds<4>, c) % 16 == 0 && offsetof(TileLds<1>, c) % 16 == 0, "cpre holds one u64 per thread");
-static_assert(TG<1>::RS_CAP > TREC_N, "the read starts of a tile record fit rs_rel");
+constexpr int TILE_STAGE_AT = 2 * (DPAD + TILE_RAW_WORDS + 4) + TILE_RAW_WORDS - 2 * TILE_RAW_WORDS;      // index into dense[]: the stage ends where kw[] ends
+static_assert(TILE_STAGE_AT >= TILE_RAW_WORDS && TILE_STAGE_AT % 4 == 0 && offsetof(TileLds, kw) == sizeof(u32) * 2 * (DPAD + TILE_RAW_WORDS + 4), "stage = dense[AT ..) + kw[]");
+static_assert((2 * (DPAD + TILE_RAW_WORDS + 4) - TILE_STAGE_AT) == 4 * TILE_THREADS, "one 16-byte store per thread");
+// six workgroups per CU (22.8 KB each + the 1 KB table)
+static_assert((sizeof(TileLds) + T3_WORDS * 8) * 6 <= 160 * 1024, "6 workgroups per CU");
+static_assert((TILE_RAW_WORDS + 8) * 2 >= TILE_THREADS * 8 && ((TILE_RAW_WORDS + 8) * 4) % 8 == 0 && offsetof(TileLds, c) % 16 == 0, "cpre holds one u64 per thread");
+static_assert(TILE_RS_CAP > TREC_N, "the read starts of a tile record fit rs_rel");
 
 // 16 ASCII bases -> {plane0 half | plane1 half}, MSB first (base 0 in bits 31 / 15); bad != 0: a byte outside ACGT
 __device__ inline u32 ascii16_to_hp(uint4 v, u32& bad) {
@@ -287,12 +272,12 @@ __device__ inline void put_count(const SketchArgs& a, u32 gt, u32 n, bool last_k
 }
 
 // ---- generic exact path for one tile (inside the tile kernel) --------------------------------------------
-template <bool HPC, int NW, class Src>
-__device__ void slow_tile(const SketchArgs& a, const Src& src, u32 gt, Rec* slab, TileLds<NW>& S) {
-    constexpr int TT = TG<NW>::TT;
-    const int tid = threadIdx.x % TT;
-    const u64 t_lo = (u64)gt * TG<NW>::STRIDE;
-    u64 t_hi = t_lo + TG<NW>::STRIDE; if (t_hi > a.n_bases) t_hi = a.n_bases;
+template <bool HPC, class Src>
+__device__ void slow_tile(const SketchArgs& a, const Src& src, u32 gt, Rec* slab, TileLds& S) {
+    constexpr int TT = TILE_THREADS;
+    const int tid = threadIdx.x % TT;         // (a no-op in a TT-thread workgroup; without it the compiler allocates the tile kernel's registers differently)
+    const u64 t_lo = (u64)gt * TILE_STRIDE;
+    u64 t_hi = t_lo + TILE_STRIDE; if (t_hi > a.n_bases) t_hi = a.n_bases;
     const u32 rl = a.bread[gt], rh_ = a.bread[gt + 2];
     const u64 first_base = a.offsets[0];
     u32* tmp = S.misc;
@@ -309,7 +294,7 @@ __device__ void slow_tile(const SketchArgs& a, const Src& src, u32 gt, Rec* slab
             if (kept_at<HPC>(src, rlo, p) && walk_lmer<HPC>(src, rlo, p, a.l, start, hash) && hash <= a.bound) sel = 1;
         }
         u32 total;
-        const u32 rank = tile_excl_scan<NW>(sel, tmp, total);
+        const u32 rank = tile_excl_scan(sel, tmp, total);
         if (sel) put_rec(a, slab, running + rank, hash, (u32)(start - rlo), r + a.read_base);
         running += total;
     }
@@ -370,7 +355,7 @@ __device__ inline u32 nt4_code(u8 c) {                         // src/read.rs:23
 // on top of the tile state, which is dead by then); sc_tmp: 8 words of scan scratch + 1 flag
 template <bool HPC, class Src>
 __device__ __attribute__((noinline)) void sync_slow_tile(const SketchArgs& a, const Src& src, u32 gt, Rec* slab, u32 (*dq)[SYNC_SLOW_THREADS], u32* sc_tmp) {
-    constexpr int TT = SYNC_SLOW_THREADS, TILE_STRIDE = TG<4>::STRIDE;      // (the syncmer scheme runs on the 256-lane tiles; this machine on the first TT of their threads)
+    constexpr int TT = SYNC_SLOW_THREADS;         // (this machine runs on the first TT of the tile's threads)
     constexpr u32 SEG = (TILE_STRIDE + TT - 1) / TT;           // raw positions per thread
     u32& any_over = sc_tmp[8];
     const int tid = threadIdx.x;
@@ -475,8 +460,8 @@ __device__ __attribute__((noinline)) void sync_slow_tile(const SketchArgs& a, co
 // ---- fast tile kernel ---------------------------------------------------------------------------------------------
 struct CandOut { u64 hash; u32 pos, read; };
 
-// One tile per NW waves; TPW tiles per workgroup (TPW > 1 only with NW = 1: independent wave tiles that share the exact-hash table and
-// never meet at a barrier).  (A persistent variant — workgroups looping over tiles with the next tile's words prefetched — was measured
+// One tile per 256-lane workgroup (one-wave tiles without workgroup barriers were measured 7-9 % slower and dropped: DESIGN.md §3.1,
+// profiles/r04_b_tile_shapes_ab.txt).  (A persistent variant — workgroups looping over tiles with the next tile's words prefetched — was measured
 // and dropped: the loop makes the compiler keep ~100 more values live across the phases, 3-4 instead of 6 waves per SIMD, 3.4-4.9 ms
 // instead of 2.2 ms; capped to 80 registers it spills and is no better.  profiles/r02_notes.md.)
 // SCHEME 0: density scheme, L = l (compile-time: every shift of the bit-sliced filter is a constant).  SCHEME 1: syncmers, L = 0 and l
@@ -488,29 +473,23 @@ struct CandOut { u64 hash; u32 pos, read; };
 // directory in which the macro yields `value` and the phase stamps become marker lines, and disassembles that copy: its ISA is the hot path, whose
 // static instruction counts x trip counts are compared with the SQ counters.  No build flag of the product sources does that.
 #define MDBG_HOT(cond, value) (cond)
-template <int L, int SCHEME = 0, int WMAX = 1, int NW = 4, int TPW = 1>
-__global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kernel(SketchArgs a) {
-    typedef TG<NW> G;
-    constexpr int TT = G::TT, RW = G::RW, HW = G::HW, QCAP = G::QCAP, RS_CAP = G::RS_CAP, STAGE_AT = StageAt<NW>::AT;
-    static_assert(TPW == 1 || NW == 1, "several tiles per workgroup: wave tiles only (no workgroup barrier inside a tile)");
-    static_assert(SCHEME == 0 || (NW == 4 && TPW == 1), "the syncmer scheme runs on the 256-lane tiles");
-    __shared__ TileLdsS<SCHEME, NW> S_all[TPW];
+template <int L, int SCHEME = 0, int WMAX = 1>
+__global__ __launch_bounds__(TILE_THREADS, SCHEME ? 5 : 6) void sketch_bs_kernel(SketchArgs a) {
+    constexpr int TT = TILE_THREADS, RW = TILE_RAW_WORDS, HW = TILE_HW, QCAP = TILE_QCAP, RS_CAP = TILE_RS_CAP, STAGE_AT = TILE_STAGE_AT;
+    __shared__ TileLdsS<SCHEME> S;
     __shared__ __attribute__((aligned(16))) u64 S_t3[T3_WORDS];
     __shared__ u32 sync_tmp[SCHEME ? 16 : 1];       // scan scratch of the generic syncmer machine (its ring covers S)
     const u32 Lr = SCHEME ? a.l : (u32)L;           // l
-    const int tslot = TPW == 1 ? 0 : (int)(threadIdx.x / TT);
-    const int tid = TPW == 1 ? (int)threadIdx.x : (int)(threadIdx.x % TT), lane = tid & 63, wv = NW == 1 ? 0 : tid >> 6;
-    TileLdsS<SCHEME, NW>& S = S_all[tslot];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t nb = (int64_t)a.n_bases;
     const int64_t n_pairs = (nb + 31) >> 5;
     const bool hpc = MDBG_HOT(a.hpc != 0, true);
     typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-    const u32 wg = blockIdx.x * TPW + (u32)tslot, gt = a.tile0 + wg;       // the launch's wg-th tile
-    if (TPW > 1 && gt >= a.tile_end) return;          // (a whole wave; nothing below waits for it)
+    const u32 wg = blockIdx.x, gt = a.tile0 + wg;     // the launch's wg-th tile
     Rec* const slab = a.slab + (size_t)wg * a.slab_cap;
 #define MDBG_STAMP(i) do { if (a.dbg && tid == 0) a.dbg[(size_t)gt * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
     MDBG_STAMP(0);
-    const int64_t raw0 = (int64_t)gt * G::STRIDE - G::HALO;      // first staged raw position (negative for tile 0)
+    const int64_t raw0 = (int64_t)gt * TILE_STRIDE - TILE_HALO;      // first staged raw position (negative for tile 0)
     const bool interior = MDBG_HOT(raw0 >= 0 && raw0 + RW * 32 <= nb, true);
     const TileRec* const rec = a.recs + gt;
     // (the record is read with vector loads — the compiler cannot prove it read-only —, so what is the same in every lane is moved to scalar
@@ -545,7 +524,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
     const u32 rl = (u32)__builtin_amdgcn_readfirstlane((int)rec->rl), rh_ = (u32)__builtin_amdgcn_readfirstlane((int)rec->rh);
     static_assert((2 * (DPAD + RW + 4)) % 4 == 0, "the dense stream is a whole number of 16-byte words");
     for (int i = tid; i < 2 * (DPAD + RW + 4) / 4; i += TT) ((uint4*)S.dense)[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (SCHEME == 0) {                                // (TPW > 1: every wave writes the whole table — the same values — so none waits for another)
+    if (SCHEME == 0) {
         static_assert(T3_WORDS % 128 == 0, "the table is copied 16 bytes per lane");
         for (int i = tid; i < T3_WORDS / 2; i += TT) ((uint4*)S_t3)[i] = ((const uint4*)a.t4)[i];
     } else {                                          // 8 bits -> 16 bits, bit i to bit 2 i: the exact phase interleaves the code planes with it
@@ -554,7 +533,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         ((u16*)S_t3)[tid] = (u16)v;
     }
     if (tid == 0) { S.misc[8] = a.force_slow | ((a.tile_flags && a.tile_flags[gt]) ? 1u : 0u); S.misc[9] = 0; S.misc[11] = 0; S.misc[17] = 0; S.misc[18] = 0; S.misc[19] = 0; S.misc[20] = 0; }
-    tile_sync<NW>();
+    __syncthreads();
     if (MDBG_HOT(rh_ - rl < (u32)TREC_N, true)) {                       // the usual case: the read starts come with the tile's record
         if ((u32)tid <= rh_ - rl) {
             const int64_t rel = tid == 0 ? rec->start0 : (int64_t)rec->rel[tid - 1];
@@ -593,20 +572,20 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
                 }
             }
         }
-        tile_sync<NW>();
+        __syncthreads();
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
             const uint2 h = *(const uint2*)(stage + 2 * (WPT * tid + i));
             x0[i] = (h.x & 0xFFFF0000u) | (h.y >> 16); x1[i] = (h.x << 16) | (h.y & 0xFFFFu);
         }
         if (tid) { const u32 hp = stage[2 * WPT * tid - 1]; pv0 = hp >> 16; pv1 = hp; }
-        tile_sync<NW>();                                     // the stage has been read: its stream part goes back to zero (the barriers of the scan below order this before the stream writes)
+        __syncthreads();                                     // the stage has been read: its stream part goes back to zero (the barriers of the scan below order this before the stream writes)
         static_assert((2 * (DPAD + RW + 4) - STAGE_AT) == 4 * TT && STAGE_AT % 4 == 0, "one 16-byte store per thread");
         ((uint4*)(S.dense + STAGE_AT))[tid] = make_uint4(0u, 0u, 0u, 0u);
     } else {
 #pragma unroll
         for (int i = 0; i < WPT; ++i) { x0[i] = __brev(pr[i].x); x1[i] = __brev(pr[i].y); }
-        tile_sync<NW>();
+        __syncthreads();
     }
     MDBG_STAMP(1);
     if (MDBG_HOT(a.stop_phase == 1, false)) { if (tid == 0) a.n_valid[gt] = x0[0] == 0x12345u; return; }
@@ -652,7 +631,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         }
     }
     u32 H;
-    u32 off = tile_excl_scan<NW>(mine, S.misc, H);          // (its barriers also order the bitmap reset before the stream writes)
+    u32 off = tile_excl_scan(mine, S.misc, H);          // (its barriers also order the bitmap reset before the stream writes)
     static_assert(HW % WPT == 0, "the halo is a whole number of threads");
     if (tid == HW / WPT) S.misc[11] = off;                   // kept bases of the halo words
     if (tid == TT - 1) S.rpre[RW] = (u16)H;
@@ -675,7 +654,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         }
         off += n;
     }
-    tile_sync<NW>();
+    __syncthreads();
     MDBG_STAMP(2);
     if (MDBG_HOT(a.stop_phase == 2, false)) { if (tid == 0) a.n_valid[gt] = 0; return; }
     const u32 Hh = S.misc[11];
@@ -690,7 +669,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
             else { PlaneSrc src{a.planes, a.exc_pos, a.exc_val, a.tile_flags && a.tile_flags[gt] ? a.n_exc : 0u}; if (hpc) sync_slow_tile<true>(a, src, gt, slab, (u32(*)[SYNC_SLOW_THREADS])&S, sync_tmp); else sync_slow_tile<false>(a, src, gt, slab, (u32(*)[SYNC_SLOW_THREADS])&S, sync_tmp); }
         }
     };
-    if (MDBG_HOT(S.misc[8] || (!true_start && Hh < Lr), false)) { tile_sync<NW>(); run_slow_tile(); return; }
+    if (MDBG_HOT(S.misc[8] || (!true_start && Hh < Lr), false)) { __syncthreads(); run_slow_tile(); return; }
 
     // ---- phase 3: bit-sliced filter over the dense stream -> candidate bitmap + (unordered) candidate list ---------------
     // candidate plane coordinate x = e + BS_B - 1; owned END positions e in [max(Hh, L-1), H)
@@ -738,7 +717,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         const u32 l = a.l, sm = a.s, w = l - sm + 1, t = (w + 1) / 2;
         const u32 smask = sm ? (sm >= 16 ? 0xFFFFFFFFu : (1u << (2 * sm)) - 1u) : 0u, sshift = sm ? 2 * (sm - 1) : 0;
         for (int i = tid; i < RW + 8; i += TT) { S.dstart[i] = 0; S.c.cand[i] = 0; }
-        tile_sync<NW>();
+        __syncthreads();
         // read starts in DENSE coordinates (a start is a forced run start: its dense index is the number of kept bases in front of it)
         auto mark_start = [&](int64_t rel) {
             if (rel < 0 || rel >= (int64_t)RW * 32) return;
@@ -748,7 +727,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         };
         if (n_rs <= RS_CAP) { for (u32 i = tid; i < n_rs; i += TT) mark_start(i ? (int64_t)S.rs_rel[i] : S.rs0); }
         else for (u32 r = rl + tid; r <= rh_ && r < a.n_reads; r += TT) mark_start((int64_t)a.offsets[r] - raw0);
-        tile_sync<NW>();
+        __syncthreads();
         // The machine as a SCAN (round 6; until round 5 one thread ran the reference's machine over a stretch of ~94 positions after 32 positions of
         // look-back: ~280 VALU per window).  The tracked s-mer of a window is always an occurrence of the window's smallest hash; which one, among
         // equal ones, is history: T(p) = T(p - 1) while that s-mer is still inside the window, else the RIGHTMOST occurrence (the rescan from the back);
@@ -761,10 +740,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         // quarter of the tile's positions and walks it in rounds of 64 G positions, the carry from round to round in a scalar; one look-back round in
         // front of the quarter warms the carry up.  A window of an owned position whose state is still unknown then (no anchor in 512 positions: a
         // tandem repeat) sends the tile to the generic machine.
-#ifndef MDBG_SYNC_SG
-#define MDBG_SYNC_SG 16
-#endif
-        constexpr int SG = MDBG_SYNC_SG;                   // windows per lane and round (8 or 16: a lane's view is 64 positions: l - 1 + SG of them are used)
+        constexpr int SG = 16;                             // windows per lane and round (8 or 16: a lane's view is 64 positions: l - 1 + SG of them are used)
         constexpr int NH = WMAX + SG - 1;                  // s-mer hashes of a lane: END positions p0 - (w - 1) .. p0 + SG - 1
         // s <= 4: the s-mer hash comes from a table (second half of t3: 256 x u16, filled here) indexed by the s bits of plane 1 and the s bits of plane 0 ^ plane 1
         // as they lie in the stream — the table's builder de-interleaves the index, forms the s-mer and its reverse complement and hashes the smaller: a hash costs two
@@ -772,7 +748,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         const bool use_lut = sm != 0 && sm <= 4;
         u16* const lut = (u16*)S_t3 + 256;
         u32* const lut32 = (u32*)S.c.list;                // 256 words on top of the candidate list, which is written behind this phase
-        static_assert(sizeof(S.c.list) >= 256 * 4 && offsetof(TileLds<NW>, c) % 4 == 0 && (sizeof(S.c.cand) + sizeof(S.c.cpre)) % 4 == 0, "the packed s-mer table fits the candidate list");
+        static_assert(sizeof(S.c.list) >= 256 * 4 && offsetof(TileLds, c) % 4 == 0 && (sizeof(S.c.cand) + sizeof(S.c.cpre)) % 4 == 0, "the packed s-mer table fits the candidate list");
         if (use_lut) {
             const u32 ia = (u32)tid >> sm, ib = (u32)tid & ((1u << sm) - 1u);
             u32 fw = 0, rc = 0;
@@ -784,10 +760,10 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
             lut[tid] = (u16)hv;
             lut32[tid] = (hv << 6) * 0x10001u;             // both halves hash << 6 (at most 14 bits: s <= 4): the packed form of the common rounds below
         }
-        tile_sync<NW>();
+        __syncthreads();
         {
             const u32 n_own = H > e_lo ? H - e_lo : 0u;
-            const u32 Qw = (((n_own + NW - 1) / NW) + (64u * SG - 1u)) & ~(64u * SG - 1u);      // owned positions per wave: whole rounds
+            const u32 Qw = (((n_own + TT / 64 - 1) / (TT / 64)) + (64u * SG - 1u)) & ~(64u * SG - 1u);      // owned positions per wave: whole rounds
             const u32 wv_s = (u32)__builtin_amdgcn_readfirstlane(wv);
             const u32 Awv = e_lo + wv_s * Qw, Bwv = Awv + Qw < H ? Awv + Qw : H;                   // the wave's owned positions [Awv, Bwv)
             int32_t carry = 4096;                           // (UNKI below: nothing known in front of the look-back round)
@@ -1027,10 +1003,10 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
             }
             if (need_slow) S.misc[9] = 1;
         }
-        tile_sync<NW>();
-        if (S.misc[9]) { tile_sync<NW>(); run_slow_tile(); return; }
+        __syncthreads();
+        if (S.misc[9]) { __syncthreads(); run_slow_tile(); return; }
     }
-    tile_sync<NW>();
+    __syncthreads();
     // the (unordered) candidate list: every thread expands the bitmap words 4 tid .. 4 tid + 3.  (Round 2 and the first version of this
     // round appended to the list inside the filter loop: one LDS fetch-add and a bit loop per step, 12 times per wave instead of once.)
     auto expand_list = [&]() {
@@ -1057,7 +1033,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         }
     };
     expand_list();
-    tile_sync<NW>();
+    __syncthreads();
     MDBG_STAMP(3);
     if (MDBG_HOT(a.stop_phase == 3, false)) { if (tid == 0) a.n_valid[gt] = 0; return; }
 
@@ -1067,11 +1043,11 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         const u32 c0 = bs_popc(cw.x), c1 = bs_popc(cw.y), c2 = bs_popc(cw.z), c3 = bs_popc(cw.w);
         const u32 last = tid == TT - 1 ? bs_popc(S.c.cand[RW]) : 0u;       // the last thread also takes word RW
         u32 total;
-        const u32 o = tile_excl_scan<NW>(c0 + c1 + c2 + c3 + last, S.misc, total);
+        const u32 o = tile_excl_scan(c0 + c1 + c2 + c3 + last, S.misc, total);
         const u32 o1 = o + c0, o2 = o1 + c1, o3 = o2 + c2;
         *(uint2*)(S.c.cpre + WPT * tid) = make_uint2(o | o1 << 16, o2 | o3 << 16);
         if (tid == TT - 1) S.c.cpre[RW] = (u16)(o3 + c3);
-        tile_sync<NW>();
+        __syncthreads();
         return total;
     };
     // tile-relative raw position of dense position r.  The kept fraction is nearly uniform along a tile, so r * RW / H lands within a word
@@ -1148,26 +1124,19 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             if ((u32)(TT * i) < n) {
-                if (i) tile_sync<NW>();                               // the previous sub-round's survivors have been read
+                if (i) __syncthreads();                               // the previous sub-round's survivors have been read
                 const u32 j = tid + TT * i;
                 bool pass = false; u32 e = 0; u64 h = 0;
                 if (j < n) { e = S.c.list[j]; h = exact(e); pass = h <= a.bound; if (!pass) clear_bit(e); }
                 const u64 bal = __ballot(pass);
-                u32 n_surv;
-                if constexpr (NW == 1) {                               // one wave: its own ballot is the whole round
-                    n_surv = (u32)__popcll(bal);
-                    if (pass) { const u32 slot = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u)); S.c.surv[slot] = (u16)e; s_h[slot] = h; }
-                    tile_sync<NW>();
-                } else {
-                    if (bal) {
-                        u32 base = 0;
-                        if (lane == 0) base = atomicAdd(&S.misc[18 + i], (u32)__popcll(bal));
-                        base = (u32)__builtin_amdgcn_readfirstlane((int)base);
-                        if (pass) { const u32 slot = base + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u)); S.c.surv[slot] = (u16)e; s_h[slot] = h; }
-                    }
-                    tile_sync<NW>();
-                    n_surv = S.misc[18 + i];
+                if (bal) {
+                    u32 base = 0;
+                    if (lane == 0) base = atomicAdd(&S.misc[18 + i], (u32)__popcll(bal));
+                    base = (u32)__builtin_amdgcn_readfirstlane((int)base);
+                    if (pass) { const u32 slot = base + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u)); S.c.surv[slot] = (u16)e; s_h[slot] = h; }
                 }
+                __syncthreads();
+                const u32 n_surv = S.misc[18 + i];
                 if ((u32)tid < n_surv) {
                     e = S.c.surv[tid];
                     keep_e[i] = e;
@@ -1175,7 +1144,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
                 }
             }
         }
-        tile_sync<NW>();
+        __syncthreads();
         MDBG_STAMP(4);
         if (MDBG_HOT(a.stop_phase == 4, false)) return 0u;            // (diagnostic: instruction counts of the exact evaluation + placement alone; uniform over the tile)
         const u32 left = count_words();
@@ -1202,7 +1171,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
         // barriers, no second evaluation; the gather squeezes the holes out (it is a copy anyway).  Round 2 validated all candidates in
         // one pass and evaluated the survivors again to write them; a first version of this round ran the two-stage rounds of the fast
         // path over stretches of the bitmap: 0.43 Tbases/s at d = 0.1, most of it spent at ~100 barriers per tile.
-        tile_sync<NW>();
+        __syncthreads();
         if constexpr (SCHEME == 1) {
             // Syncmers: one position in w is a candidate (2,700 of a tile's 24,500 at l = 12 s = 4), and the density bound then keeps a few per cent of them.  Written
             // like the dense settings of the density scheme — every candidate a 16-byte slot of the slab, the rejected ones as holes — that was 43 KB per tile to HBM
@@ -1225,16 +1194,16 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
                 if (tid == TT - 1) S.c.cand[RW] = w5[4];
                 if (tid == 0) S.misc[17] = 0;
             }
-            tile_sync<NW>();
+            __syncthreads();
             expand_list();
-            tile_sync<NW>();
+            __syncthreads();
             const u32 n2 = S.misc[17];
             if (n2 <= QCAP) {
                 const u32 nv = n2 ? process_list(n2) : 0;
                 if (tid == 0) { put_count(a, gt, nv, true); if (a.dbg) { a.dbg[(size_t)gt * 16 + 9] = n_cand; a.dbg[(size_t)gt * 16 + 10] = nv; } }
                 return;
             }
-            tile_sync<NW>();
+            __syncthreads();
         }
         const u32 C = count_words();
         const u32 per = (C + TT - 1) / TT;
@@ -1258,7 +1227,7 @@ __global__ __launch_bounds__(64 * NW * TPW, SCHEME ? 5 : 6) void sketch_bs_kerne
             }
         }
         u32 nv;
-        tile_excl_scan<NW>(surv, S.misc, nv);
+        tile_excl_scan(surv, S.misc, nv);
         if (tid == 0) {
             a.n_valid[gt] = nv; if (a.n_scan) a.n_scan[gt] = C;
             if (a.block_sum && nv) atomicAdd(a.block_sum + ((gt - a.tile0) >> SCAN_GRAN_LOG), (unsigned long long)nv);
@@ -1568,31 +1537,12 @@ void launch_pack_planes(const u8* bases, u64 n_bases, uint2* words, u64* exc_pos
 }
 
 // ---- host launchers -------------------------------------------------------------------------------
-void launch_bread(const u64* offsets, u32 n_reads, u64 n_bases, u32 n_tiles, u32* bread, TileRec* recs, const SketchInit& init, const TileShape& sh, hipStream_t s) {
+void launch_bread(const u64* offsets, u32 n_reads, u64 n_bases, u32 n_tiles, u32* bread, TileRec* recs, const SketchInit& init, hipStream_t s) {
     const u32 n = n_tiles + 2;
-    hipLaunchKernelGGL(tile_rec_kernel, dim3((n + 255) / 256), dim3(256), 0, s, offsets, n_reads, n_bases, n_tiles, bread, recs, init, (int64_t)sh.stride, (int64_t)sh.halo);
+    hipLaunchKernelGGL(tile_rec_kernel, dim3((n + 255) / 256), dim3(256), 0, s, offsets, n_reads, n_bases, n_tiles, bread, recs, init, (int64_t)TILE_STRIDE, (int64_t)TILE_HALO);
 }
-void launch_tile_flags(const u64* exc_pos, u32 n_exc, u32 n_tiles, u8* flags, const TileShape& sh, hipStream_t s) {
-    if (n_exc) hipLaunchKernelGGL(tile_flags_kernel, dim3((n_exc + 255) / 256), dim3(256), 0, s, exc_pos, n_exc, n_tiles, flags, (u64)sh.stride, (u64)sh.halo);
-}
-// The tile geometry of a context.  256-lane tiles are the default: the wave tiles (MDBG_TILE = "1x4": four to a workgroup, "1x1": one
-// 64-lane workgroup each) were built to take the ~20 workgroup barriers out of a tile's life, and measured SLOWER by 7 - 9 % on configs[2]
-// (profiles/r04_b_tile_shapes_ab.txt): the kernel follows its VALU instruction count, and a wave tile spends more of them per base (four
-// filter steps of 63 words for 193 dense words, a placement pass per 24 instead of 97 survivors, twice the look-back share).
-// The switch is read once; the syncmer scheme only exists on the 256-lane tiles.
-// Since round 5 the wave-tile kernels are only compiled with -DMDBG_WAVE_TILES (scratch/build_variant.sh wave_tiles -DMDBG_WAVE_TILES; mdbg_build_flags() bit 0):
-// the default library carries ONE tile shape, MDBG_TILE is ignored by it.
-TileShape tile_shape_for(u32 scheme) {
-    u32 nw = 4, tpw = 1;
-#ifdef MDBG_WAVE_TILES
-    static const char* const env = getenv("MDBG_TILE");
-    if (env && env[0] == '1' && env[1] == 'x' && env[2] == '4') { nw = 1; tpw = 4; }
-    else if (env && env[0] == '1' && env[1] == 'x' && env[2] == '1') { nw = 1; tpw = 1; }
-#endif
-    if (scheme == 1) { nw = 4; tpw = 1; }
-    TileShape sh; sh.nw = nw; sh.tpw = tpw;
-    sh.stride = nw == 4 ? (u32)TileGeo<4>::STRIDE : (u32)TileGeo<1>::STRIDE; sh.halo = nw == 4 ? (u32)TileGeo<4>::HALO_BASES : (u32)TileGeo<1>::HALO_BASES;
-    return sh;
+void launch_tile_flags(const u64* exc_pos, u32 n_exc, u32 n_tiles, u8* flags, hipStream_t s) {
+    if (n_exc) hipLaunchKernelGGL(tile_flags_kernel, dim3((n_exc + 255) / 256), dim3(256), 0, s, exc_pos, n_exc, n_tiles, flags, (u64)TILE_STRIDE, (u64)TILE_HALO);
 }
 void launch_alphabet_rule(const SketchArgs& a, unsigned long long* which, hipStream_t s) {
     if (!a.n_reads) return;
@@ -1601,42 +1551,27 @@ void launch_alphabet_rule(const SketchArgs& a, unsigned long long* which, hipStr
     else hipLaunchKernelGGL(alphabet_rule_kernel<PlaneSrc>, g, b, 0, s, PlaneSrc{a.planes, a.exc_pos, a.exc_val, a.n_exc}, a.offsets, a.n_reads, a.l, a.hpc, which);
 }
 
-template <int L> static void launch_bs(const SketchArgs& a, u32 n_tiles, const TileShape& sh, hipStream_t s) {
-#ifdef MDBG_WAVE_TILES
-    if (sh.nw == 1 && sh.tpw == 1) { hipLaunchKernelGGL((sketch_bs_kernel<L, 0, 1, 1, 1>), dim3(n_tiles), dim3(64), 0, s, a); return; }
-    if (sh.nw == 1) { hipLaunchKernelGGL((sketch_bs_kernel<L, 0, 1, 1, 4>), dim3((n_tiles + 3) / 4), dim3(256), 0, s, a); return; }
-#endif
-    (void)sh;
-    hipLaunchKernelGGL((sketch_bs_kernel<L, 0, 1, 4, 1>), dim3(n_tiles), dim3(256), 0, s, a);
-}
 // one launch covers the whole batch (launch boundaries would only re-synchronise the workgroups' phases); n_tiles = tiles to run from a.tile0
-void launch_sketch(SketchArgs a, u32 n_tiles, const TileShape& sh, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
+void launch_sketch(SketchArgs a, u32 n_tiles, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
     if (!n_tiles) return;
     a.tile_end = a.tile0 + n_tiles;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
     if (a.scheme == 1) {                              // syncmers: l is a run-time value, the window a compile-time one
-#ifndef MDBG_ONLY_L
         switch (a.l - a.s + 1) {
-#define MDBG_W(n) case n: hipLaunchKernelGGL((sketch_bs_kernel<0, 1, n>), dim3(n_tiles), dim3(256), 0, s, a); break;
+#define MDBG_W(n) case n: hipLaunchKernelGGL((sketch_bs_kernel<0, 1, n>), dim3(n_tiles), dim3(TILE_THREADS), 0, s, a); break;
             MDBG_W(1) MDBG_W(2) MDBG_W(3) MDBG_W(4) MDBG_W(5) MDBG_W(6) MDBG_W(7) MDBG_W(8) MDBG_W(9) MDBG_W(10) MDBG_W(11) MDBG_W(12) MDBG_W(13) MDBG_W(14) MDBG_W(15) MDBG_W(16)
             MDBG_W(17) MDBG_W(18) MDBG_W(19) MDBG_W(20) MDBG_W(21) MDBG_W(22) MDBG_W(23) MDBG_W(24) MDBG_W(25) MDBG_W(26) MDBG_W(27) MDBG_W(28) MDBG_W(29) MDBG_W(30) MDBG_W(31)
 #undef MDBG_W
-            default: hipLaunchKernelGGL((sketch_bs_kernel<0, 1, 32>), dim3(n_tiles), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((sketch_bs_kernel<0, 1, 32>), dim3(n_tiles), dim3(TILE_THREADS), 0, s, a); break;
         }
-#endif
     }
     else switch (a.l) {
-#define MDBG_L(n) case n: launch_bs<n>(a, n_tiles, sh, s); break;
-#ifdef MDBG_ONLY_L                                    // quick experiment builds: one l, no syncmers
-        MDBG_L(MDBG_ONLY_L)
-        default: break;
-#else
+#define MDBG_L(n) case n: hipLaunchKernelGGL((sketch_bs_kernel<n>), dim3(n_tiles), dim3(TILE_THREADS), 0, s, a); break;
         MDBG_L(2) MDBG_L(3) MDBG_L(4) MDBG_L(5) MDBG_L(6) MDBG_L(7) MDBG_L(8) MDBG_L(9) MDBG_L(10) MDBG_L(11) MDBG_L(12) MDBG_L(13)
         MDBG_L(14) MDBG_L(15) MDBG_L(16) MDBG_L(17) MDBG_L(18) MDBG_L(19) MDBG_L(20) MDBG_L(21) MDBG_L(22) MDBG_L(23) MDBG_L(24)
         MDBG_L(25) MDBG_L(26) MDBG_L(27) MDBG_L(28) MDBG_L(29) MDBG_L(30) MDBG_L(31) MDBG_L(32)
-        default: launch_bs<32>(a, n_tiles, sh, s); break;      // l > 32: every tile takes the generic walker (force_slow is set by the host)
-#endif
 #undef MDBG_L
+        default: hipLaunchKernelGGL((sketch_bs_kernel<32>), dim3(n_tiles), dim3(TILE_THREADS), 0, s, a); break;      // l > 32: every tile takes the generic walker (force_slow is set by the host)
     }
     if (ev_end) (void)hipEventRecord(ev_end, s);
 }

@@ -370,10 +370,7 @@ __device__ inline u64 upsert_wave_h(const TableArgs& T, bool act, u32 li, u64 i,
 // local indices of the windows this rank has to insert, and then works the list off densely, so the long find-or-claim chains run on
 // full wavefronts (0.80 -> 0.64 ms per 6.6 M windows against one thread per minimizer index).  Orientation, hash and the own side of the
 // key comparison read the staged values.
-#ifndef OWN_SPAN_V
-#define OWN_SPAN_V 2048
-#endif
-constexpr int OWN_SPAN = OWN_SPAN_V;
+constexpr int OWN_SPAN = 2048;
 __global__ __launch_bounds__(256) void insert_windows_kernel(TableArgs T, const u64* __restrict__ mh, const u32* __restrict__ mread,
                                                                    const u64* __restrict__ roff, u64 i0, u64 i1, u32 slot0, u64 first_ordinal,
                                                                    u32* __restrict__ cap_err, const u64* __restrict__ i1_dev, u64 n_lim) {
@@ -810,25 +807,23 @@ static void launch_listed_entries(const TableArgs& T, const u64* mh, u32* mread,
                                   u32* cap_err, const ListedBatch* multi, u32 n_multi, hipStream_t s) {
     hipLaunchKernelGGL(insert_listed_entries_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, T, mh, mread, roff, m0, m1, list, n, slot0, n_reads, first_ordinal, cap_err, multi, n_multi);
 }
+// Few listed windows per span (a rank's share of a sketch at 4+ ranks): staging every span of the sketch would mostly fetch hashes nobody needs, and
+// a workgroup would work off a few dozen entries; the per-entry kernel reads each window's values where they lie.  So do very long k (the span does not
+// fit the default LDS window) and a list without segments.
+constexpr u64 LISTED_SPAN_MIN = 150;          // listed windows per span below which a batch takes the per-entry kernel
+static size_t listed_span_lds(const TableArgs& T) { return ((size_t)OWNL_SPAN + T.ks.k) * sizeof(u64) + OWNL_SPAN; }      // hashes + the span's claim bytes
+// true: launch_insert_listed takes the per-entry kernel for this batch (then several such batches can share one launch, launch_insert_listed_multi, and their
+// claim bytes must start from zero: the per-entry kernel sets only the byte of a window that creates its key, the span kernel writes every byte of its batch)
+bool listed_per_entry(const TableArgs& T, u64 m0, u64 m1, u64 n, bool have_seg) {
+    return !have_seg || listed_span_lds(T) > 64 * 1024 || n < (u64)owner_list_spans(m1 - m0) * LISTED_SPAN_MIN;
+}
 void launch_insert_listed(const TableArgs& T, const u64* mh, u32* mread, const u64* roff, u64 m0, u64 m1, const u32* list, const u32* seg, u64 n, u32 slot0,
                           u32 n_reads, u64 first_ordinal, u32* cap_err, hipStream_t s) {
     if (!n) return;
-    const size_t lds = ((size_t)OWNL_SPAN + T.ks.k) * sizeof(u64) + OWNL_SPAN;      // hashes + the span's claim bytes
-    // few listed windows per span (a rank's share of a sketch at 4+ ranks): staging every span of the sketch would mostly fetch hashes nobody needs, and
-    // a workgroup would work off a few dozen entries; the per-entry kernel reads each window's values where they lie
-    u64 per_span_min = 150;
-    { const char* v = getenv("MDBG_LISTED_SPAN_MIN"); if (v) per_span_min = strtoull(v, nullptr, 10); }
-    const bool sparse = n < (u64)owner_list_spans(m1 - m0) * per_span_min;
-    if (seg && lds <= 64 * 1024 && !sparse)
-        hipLaunchKernelGGL(insert_listed_span_kernel, dim3(owner_list_spans(m1 - m0)), dim3(256), lds, s, T, mh, mread, roff, m0, m1, list, seg, n, slot0, n_reads, first_ordinal, cap_err);
-    else       // (also very long k: the span does not fit the default LDS window, every window reads its values from HBM)
+    if (!listed_per_entry(T, m0, m1, n, seg != nullptr))
+        hipLaunchKernelGGL(insert_listed_span_kernel, dim3(owner_list_spans(m1 - m0)), dim3(256), listed_span_lds(T), s, T, mh, mread, roff, m0, m1, list, seg, n, slot0, n_reads, first_ordinal, cap_err);
+    else
         launch_listed_entries(T, mh, mread, roff, m0, m1, list, n, slot0, n_reads, first_ordinal, cap_err, nullptr, 0u, s);
-}
-// true: launch_insert_listed would take the per-entry kernel for this batch (then several such batches can share one launch, launch_insert_listed_multi)
-bool listed_is_sparse(const TableArgs& T, u64 m0, u64 m1, u64 n) {
-    u64 per_span_min = 150;
-    { const char* v = getenv("MDBG_LISTED_SPAN_MIN"); if (v) per_span_min = strtoull(v, nullptr, 10); }
-    return n < (u64)owner_list_spans(m1 - m0) * per_span_min || ((size_t)OWNL_SPAN + T.ks.k) * sizeof(u64) + OWNL_SPAN > 64 * 1024;
 }
 void launch_insert_listed_multi(const TableArgs& T, const u64* mh, u32* mread, const u64* roff, const ListedBatch* d_batches, u32 n_batches, u64 total, u32* cap_err, hipStream_t s) {
     if (!total) return;
@@ -1034,6 +1029,7 @@ __device__ inline SlotView slot_view(const Slot& e, u64 s, const u64* mx, u32 ca
     return v;
 }
 
+// Finalize's marking pass for the byte-map mode (F.claims == 0: one byte map per bit, zeroed per finalize; the claim-map mode has fin_mark_claims_kernel).
 // FIN_SPT slots per thread, all requested before the first is looked at: the kernel is a chain of dependent round trips (slot -> read
 // offsets of the smallest ordinal -> bitmap atomic), and with one slot per thread its 9,700 workgroups went through it 19 deep
 constexpr int FIN_SPT = 4;
@@ -1055,20 +1051,6 @@ __global__ __launch_bounds__(1024) void fin_mark_kernel(FinArgs F) {
             ++n_occ; solid[u] = F.A == 1 || (u16)count >= (u16)F.A; n_wrapped += count >= 65536u ? 1u : 0u;          // as slot_view
             // first sighting: the claimer's window or the smallest ordinal the others pushed.  Most keys are seen once (sequencing
             // errors), and the claimer's dense index follows from `rep` alone: no read map / offset lookups for them
-            if (F.claims) {
-                // the claimer's byte is set already (insert_windows_kernel); a key seen again may have an earlier sighting: move the mark there.  201 M scattered byte
-                // stores into a 721 MB map were 10 ms of the human table's finalize (1.3 TB/s); 183 M of those keys are seen once and cost nothing here
-                // ONE map in this mode: bit 0 = first sighting, bit 1 = the key is solid (no second map to zero: 2.2 ms per finalize of the human table); with the batches in ordinal order — the mode's
-                // condition — a first sighting never moves forward
-                // (F.claims == 2: the map is indexed by STORE index, the dense index of the claimer comes from the batch table)
-                const u64 ic = (u32)e[u].word;
-                const u64 Dc = F.claims == 2 ? dense_of_index(F, ic) : ic;
-                u64 at = ic;
-                D = Dc;
-                if (e[u].count) { u64 i, D1; decode_ordinal(F, e[u].m1, i, D1); if (D1 < Dc) { D = D1; at = i; F.by_first[ic] = 0; } }
-                // (a key seen again always rewrites its byte: its solid bit may have to GO — a u16 abundance that wrapped below minabund between two finalize calls, round-5 advice)
-                if (e[u].count || solid[u]) F.by_first[at] = solid[u] ? 3 : 1;
-            } else {
             if (e[u].word & (1ull << 33)) { u64 i; const u64 ro = rep_ordinal(F, e[u].word); decode_ordinal(F, ro < e[u].m1 ? ro : e[u].m1, i, D); }   // routed record
             else {
                 D = dense_of_index(F, (u32)e[u].word);
@@ -1076,7 +1058,6 @@ __global__ __launch_bounds__(1024) void fin_mark_kernel(FinArgs F) {
             }
             F.by_first[D] = 1;                       // (distinct keys have distinct first sightings: nobody else writes this byte)
             if (solid[u]) F.by_solid[D] = 1;
-            }
         }
         dense[u] = D;
         m[u] = __ballot(solid[u]);
@@ -1102,7 +1083,7 @@ __global__ __launch_bounds__(1024) void fin_mark_kernel(FinArgs F) {
             F.solid_list[j] = s0 + 1024ull * u; F.solid_dense[j] = dense[u];
         }
 }
-// fin_mark_kernel for the claim-map mode (F.claims), in two passes over the workgroup's 4,096 slots.  A slot needs more than a look only when its key was seen again
+// The marking pass for the claim-map mode (F.claims), in two passes over the workgroup's 4,096 slots.  A slot needs more than a look only when its key was seen again
 // (the first sighting may lie in front of the claimer: one scattered read, up to two scattered byte stores) or is solid (a row of the node table): 9 % of the human
 // table's slots, which in fin_mark_kernel sit spread over every wave, so every wave waits for its few slow lanes on each of its four rounds.  Here the first pass
 // only looks (word and count) and lists those slots in LDS; the second pass works the list off on full waves, and lists the solid ones once more for the ONE
@@ -1153,7 +1134,7 @@ __global__ __launch_bounds__(1024) void fin_mark_claims_kernel(FinArgs F) {
             const u32 count = e.count + 1u;
             solid = F.A == 1 || (u16)count >= (u16)F.A;
             // the claimer's byte is set already (insert_windows_kernel); a key seen again may have an earlier sighting: move the mark there.  ONE map in this mode: bit 0 =
-            // first sighting, bit 1 = the key is solid (see fin_mark_kernel)
+            // first sighting, bit 1 = the key is solid
             const u64 ic = (u32)e.word;                                    // store index of the claimer; F.claims == 2: the map is indexed by store index, not by dense index
             const u64 Dc = F.claims == 2 ? dense_of_index(F, ic) : ic;
             u64 at = ic;
@@ -1176,7 +1157,7 @@ __global__ __launch_bounds__(1024) void fin_mark_claims_kernel(FinArgs F) {
     for (u32 t = threadIdx.x; t < ns; t += 1024) { F.solid_list[bbase + t] = b0 + sol_li[t]; F.solid_dense[bbase + t] = (u64)sol_D[t]; }
 }
 // bitmap word w <- bit i = (byte 64 w + i != 0), for both maps; one thread per word (four 16-byte loads per map).  by1 == null: ONE map whose bytes hold bit 0 = first
-// sighting, bit 1 = solid (the claim-map mode of fin_mark_kernel).  Bits at or behind n_bits are cleared (the claim map's bytes behind the store's end are whatever
+// sighting, bit 1 = solid (the claim-map mode, fin_mark_claims_kernel).  Bits at or behind n_bits are cleared (the claim map's bytes behind the store's end are whatever
 // the allocation holds: masked here instead of being zeroed by a fill in front of every finalize).  block_sum (non-null): the popcounts of the workgroup's 1,024 words of
 // either bitmap — what popc_block_kernel would compute in a launch of its own: [blockIdx] and [n_blocks + blockIdx].
 __global__ __launch_bounds__(1024) void bytes_to_bits_kernel(const u8* __restrict__ by0, const u8* __restrict__ by1, u64 n_words, u64 n_bits, u64* __restrict__ bm0, u64* __restrict__ bm1,
@@ -1840,8 +1821,7 @@ void launch_fin_order(const FinArgs& F, u64 n_solid, u64* order, hipStream_t s) 
     if (n_solid) hipLaunchKernelGGL(fin_order_kernel, dim3((unsigned)((n_solid + 255) / 256)), dim3(256), 0, s, F, n_solid, order);
 }
 void launch_fin_mark(const FinArgs& F, hipStream_t s) {
-    static const bool one_pass = getenv("MDBG_FIN_ONE_PASS") != nullptr;      // (A/B switch: the round-5 kernel for the claim-map mode too)
-    if (F.claims && !one_pass) { hipLaunchKernelGGL(fin_mark_claims_kernel, dim3((unsigned)((F.cap + 1024 * FIN_SPT - 1) / (1024 * FIN_SPT))), dim3(1024), 0, s, F); return; }
+    if (F.claims) { hipLaunchKernelGGL(fin_mark_claims_kernel, dim3((unsigned)((F.cap + 1024 * FIN_SPT - 1) / (1024 * FIN_SPT))), dim3(1024), 0, s, F); return; }
     hipLaunchKernelGGL(fin_mark_kernel, dim3((unsigned)((F.cap + 1024 * FIN_SPT - 1) / (1024 * FIN_SPT))), dim3(1024), 0, s, F);
 }
 void launch_wrap_list(Slot* tab, u64 cap, u32 A, bool all_solid, u64* w_jstar, u32* w_count, unsigned long long* counters, hipStream_t s) {

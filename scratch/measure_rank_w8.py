@@ -123,7 +123,7 @@ def receive():
 for rep in range(3):               # (the first pass grows the table; the later ones find it large enough, as every step after a job's first does)
     n_listed, t_ins, t_fb, t_fe, nw, n_nodes = receive()
     st = m.stats()
-    print("receiver pass %d [MDBG_LISTED_SPAN_MIN=%s]: own windows + %d listed windows of %d peers inserted in %.3f ms (library timer ms_insert %.3f); finalize over the whole "
+    print("receiver pass %d: own windows + %d listed windows of %d peers inserted in %.3f ms (library timer ms_insert %.3f); finalize over the whole "
           "index space (%d bitmap words): begin %.3f ms, end %.3f ms (no all-reduce, no position fetch), nodes of this rank %d, distinct keys %d" % (
-              rep, os.environ.get("MDBG_LISTED_SPAN_MIN", "-"), n_listed, W - 1, t_ins * 1e3, st["ms_insert"], nw, t_fb * 1e3, t_fe * 1e3, n_nodes,
+              rep, n_listed, W - 1, t_ins * 1e3, st["ms_insert"], nw, t_fb * 1e3, t_fe * 1e3, n_nodes,
               st["n_distinct"]), flush=True)

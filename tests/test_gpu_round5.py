@@ -7,8 +7,8 @@ import pytest
 
 from conftest import ROOT
 
-# the gather of SMALL tiles (gather_multi_kernel: one wave takes several tiles) is chosen whenever a tile expects fewer than 128 records — with the product's 256-lane
-# tiles that is any density below ~0.002 —, and until round 5 only the wave-tile experiment exercised it.  Child process: the hooks are read once per process.
+# the gather of SMALL tiles (gather_multi_kernel: one wave takes several tiles) is chosen whenever a tile expects fewer than 128 records — with the 256-lane tiles that
+# is any density below ~0.002 —; the children below exercise it.  Child process: the hooks are read once per process.
 CHILD = r"""
 import sys
 sys.path.insert(0, %r)
@@ -61,7 +61,7 @@ def test_small_tile_gather_survives_slab_overflow_and_several_launches():
 @pytest.mark.gpu
 def test_default_build_has_one_tile_shape():
     from rust_mdbg_amd import api
-    assert api.load_library().mdbg_build_flags() == 0          # no wave tiles (the only build switch left)
+    assert api.load_library().mdbg_build_flags() == 0          # no build flag is defined
 
 
 @pytest.mark.gpu
@@ -375,4 +375,3 @@ def test_insertion_confirms_neighbouring_repeats_as_links_and_stays_exact():
     assert weak > 0
     _insert_child(MDBG_WEAK_FP=1, MDBG_NO_CHAIN=1)
     _insert_child(MDBG_WEAK_FP=1, MDBG_POISON=1)
-    _insert_child(MDBG_FIN_ONE_PASS=1)          # finalize's marking kernel of the claim-map mode in one pass (the default lists the slots that need work and takes two)
