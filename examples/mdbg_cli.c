@@ -1,7 +1,9 @@
 /* mdbg_cli.c — the two C ABIs used from plain C, the way rust-mdbg's main() would use them through FFI:
  *   reads.fa[.gz]  ->  mdbg_reader_*  ->  mdbg_ingest_batch[_packed]  ->  mdbg_finalize  ->  mdbg_graph_edges  ->  <prefix>.gfa (+ <prefix>.0.sequences)
+ *   --contigs:  ... ->  mdbg_graph_unitigs  ->  mdbg_emit_contigs_*  ->  <prefix>.unitigs.gfa + <prefix>.unitigs.fa   (what the reference's users get from
+ *   `gfatools asm -u` + to_basespace + gfa2fasta.sh; no tip or bubble removal)
  * Same flags as the reference binary for this path (src/main.rs:330-420): -k -l --density --minabund --presimp --prefix --threads
- * --reference --skiphpc --syncmers/-s --lmer-counts/--lmer_counts_min/--lmer_counts_max --no-basespace.
+ * --reference --skiphpc --syncmers/-s --lmer-counts/--lmer_counts_min/--lmer_counts_max --no-basespace; --contigs is this host's own.
  * --threads N > 1: an uncompressed input is mapped and parsed by N threads (mdbg_reader_open_mt) that also pack their pieces to 2 bits
  * per base (mdbg_reader_next_packed); a reader thread produces batch i+1 while the main thread ingests batch i.
  * Build:  gcc -O2 -Iinclude examples/mdbg_cli.c -Lrust_mdbg_amd -lmdbg_hip -lmdbg_emit -lpthread -Wl,-rpath,$PWD/rust_mdbg_amd -o mdbg_cli
@@ -69,7 +71,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     for (int i = 1; i < argc; ++i) {
@@ -86,13 +88,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--lmer_counts_min") && i + 1 < argc) lc_min = (uint32_t)strtoul(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "--lmer_counts_max") && i + 1 < argc) lc_max = (uint32_t)strtoul(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "--timing")) timing = 1;
+        else if (!strcmp(argv[i], "--contigs")) contigs = 1;
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
 
     int err = 0;
@@ -164,10 +167,19 @@ int main(int argc, char** argv) {
     if (rc) die(NULL, "mdbg_emit_write_gfa", rc);
     if (timing) fprintf(stderr, "timing: %llu reads, %llu bases; ingest %.3f s, to .gfa %.3f s (%.2f Gbases/s; context creation not included); ingest loop: waiting for the reader %.3f, mdbg_ingest_batch_packed %.3f s\n",
                         (unsigned long long)n_reads, (unsigned long long)n_bases, t_ingest - t0, now_s() - t0, (double)n_bases / (now_s() - t0) / 1e9, t_wait, t_gpu);
-    if (write_sequences) {                                          /* second pass over the input: the node sequences */
+    mdbg_contigs* ctg = NULL;
+    if (contigs) {                                                  /* unitigs + copy plan from the GPU; the handle keeps its own copy of the plan */
+        mdbg_unitig_list ul;
+        rc = mdbg_graph_unitigs(ctx, &ul);
+        if (rc) die(ctx, "mdbg_graph_unitigs", rc);
+        printf("Number of unitigs: %llu\n", (unsigned long long)ul.n_unitigs);
+        ctg = mdbg_emit_contigs_open(&ul, &nodes, &err);
+        if (!ctg) die(NULL, "mdbg_emit_contigs_open", err);
+    }
+    if (write_sequences || ctg) {                                   /* second pass over the input: the node sequences, the contigs' bases */
         /* one file per writer thread, "<prefix>.<t>.sequences", as the reference's worker threads write them (main.rs:614-630) */
         enum { MAX_WRITERS = 16 };
-        const int nw = threads > MAX_WRITERS ? MAX_WRITERS : threads;
+        const int nw = !write_sequences ? 0 : threads > MAX_WRITERS ? MAX_WRITERS : threads;
         mdbg_seqfile* sf[MAX_WRITERS]; seqjob_t job[MAX_WRITERS]; pthread_t th[MAX_WRITERS];
         for (int t = 0; t < nw; ++t) {
             snprintf(path, sizeof path, "%s.%d.sequences", prefix, t);
@@ -183,12 +195,13 @@ int main(int argc, char** argv) {
             rc = mdbg_reader_next(rd, 256u << 20, &bases, &offs, &n);
             if (rc) die(NULL, "mdbg_reader_next", rc);
             if (!n) break;
+            if (ctg) { rc = mdbg_emit_contigs_add_batch(ctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
             for (int t = 0; t < nw; ++t) {
                 seqjob_t jb; jb.sf = sf[t]; jb.nodes = &nodes; jb.part = (uint32_t)t; jb.n_parts = (uint32_t)nw; jb.bases = bases; jb.offs = offs; jb.n = n; jb.first = first; jb.rc = 0;
                 job[t] = jb;
                 if (t) pthread_create(&th[t], NULL, seqjob_main, &job[t]);
             }
-            seqjob_main(&job[0]);
+            if (nw) seqjob_main(&job[0]);
             for (int t = 1; t < nw; ++t) pthread_join(th[t], NULL);
             for (int t = 0; t < nw; ++t) if (job[t].rc) die(NULL, "mdbg_seqfile_write_batch_part", job[t].rc);
             first += n;
@@ -196,6 +209,15 @@ int main(int argc, char** argv) {
         mdbg_reader_close(rd);
         for (int t = 0; t < nw; ++t) { rc = mdbg_seqfile_close(sf[t]); if (rc) die(NULL, "mdbg_seqfile_close", rc); }
         if (timing) fprintf(stderr, "timing: .sequences pass %.3f s (%d file%s)\n", now_s() - ts, nw, nw > 1 ? "s" : "");
+    }
+    if (ctg) {
+        snprintf(path, sizeof path, "%s.unitigs.gfa", prefix);
+        rc = mdbg_emit_contigs_write_gfa(ctg, path);
+        if (rc) die(NULL, "mdbg_emit_contigs_write_gfa", rc);
+        snprintf(path, sizeof path, "%s.unitigs.fa", prefix);
+        rc = mdbg_emit_contigs_write_fasta(ctg, path, 0);
+        if (rc) die(NULL, "mdbg_emit_contigs_write_fasta", rc);
+        mdbg_emit_contigs_close(ctg);
     }
     mdbg_destroy(ctx);
     return 0;

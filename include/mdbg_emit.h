@@ -104,6 +104,29 @@ int mdbg_lmer_filter_from_counts(const char* path, uint32_t l, double density, u
                                  uint64_t** codes, uint64_t* n_codes, uint64_t* n_ignored);
 void mdbg_lmer_filter_free(uint64_t* codes);
 
+/* ---- contigs: unitig sequences from the copy plan of mdbg_graph_unitigs (mdbg_hip.h) — the stitching and output half of
+ * src/to_basespace.rs (:203-262 pieces, :252,284-291 H / S lines, :312-323 L lines) and utils/gfa2fasta.sh.  Like the unitig list
+ * itself this is `gfatools asm -u` + to_basespace only: no tip or bubble removal.
+ *   mdbg_emit_contigs_open        copies the list (HOST arrays of mdbg_graph_unitigs; it may be released afterwards) and allocates every
+ *                                 unitig's sequence from length[].  nodes: the table the list was made from, or NULL; only nodes->n is
+ *                                 read (it must equal n_entries: every node lies on exactly one unitig).
+ *   mdbg_emit_contigs_add_batch   executes the plan entries whose src_read lies in the batch.  Feed every batch that was ingested, with
+ *                                 the same buffers / ordinals (as mdbg_seqfile_write_batch), in any order, cut anywhere; feeding a
+ *                                 batch twice is harmless.  Reverse complement as src/utils.rs:3-24: a byte outside ACGTU acgtu gives N.
+ *   mdbg_emit_contigs_write_gfa   "H\tVN:Z:1.0", "S\t<name>\t<seq>\tLN:i:<len>\tmc:f:<kc_sum / nodes, one decimal>",
+ *                                 "L\t<name>\t<+/->\t<name>\t<+/->\t<overlap>M"; names utg%07d + l / c.
+ *   mdbg_emit_contigs_write_fasta ">name" and the sequence on one line, for the unitigs of at least min_len bases.
+ *   mdbg_emit_contigs_get         sequence i in memory (not NUL-terminated; owned by the handle).
+ * The writers and _get return MDBG_E_STATE while some plan entry has not been filled (a batch is missing). */
+typedef struct mdbg_contigs mdbg_contigs;
+mdbg_contigs* mdbg_emit_contigs_open(const mdbg_unitig_list* unitigs, const mdbg_nodes* nodes, int* err);
+int mdbg_emit_contigs_add_batch(mdbg_contigs* h, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t first_read_ordinal);
+int mdbg_emit_contigs_write_gfa(mdbg_contigs* h, const char* path);
+int mdbg_emit_contigs_write_fasta(mdbg_contigs* h, const char* path, uint64_t min_len);
+uint64_t mdbg_emit_contigs_count(const mdbg_contigs* h);
+int mdbg_emit_contigs_get(const mdbg_contigs* h, uint64_t i, const char** seq, uint64_t* len);
+void mdbg_emit_contigs_close(mdbg_contigs* h);
+
 uint64_t mdbg_packed_words(uint64_t n_bases);
 int mdbg_pack_reads(const uint8_t* bases, uint64_t n_bases, uint64_t* words, uint64_t* exc_pos, uint8_t* exc_val,
                     uint64_t exc_cap, uint64_t* n_exc, int threads);

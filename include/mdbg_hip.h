@@ -314,6 +314,47 @@ typedef struct mdbg_edge_list {
 int mdbg_graph_edges(mdbg_ctx* ctx, float presimp, mdbg_edge_list* out);
 int mdbg_graph_edges_device(mdbg_ctx* ctx, float presimp, mdbg_edge_list* out);
 
+/* ---- unitigs and the base-space copy plan (replaces `gfatools asm -u` + the planning half of src/to_basespace.rs) --------
+ * Every documented run of the reference pipes its .gfa through `gfatools asm -u` (compaction of non-branching paths) and the
+ * to_basespace binary to get sequences; this is that step — and only that step: no tip or bubble removal (magic_simplify's
+ * -t / -b rounds) — on the node table of the last mdbg_finalize* and the edge list of the last mdbg_graph_edges* of the context
+ * (with whatever presimp that call used).  MDBG_E_STATE without a current edge list (a finalize or an ingest since the last edge
+ * call), and on routed / partitioned contexts: SINGLE-GPU ONLY.  An empty context gives an empty list.
+ *
+ * Definition (gfatools' own names and orientation choices are not reproduced):
+ *   vertex = (node, orientation), comp(v) flips the orientation.  Arcs = the DISTINCT (n1,o1)->(n2,o2) of the edge records together
+ *   with their mirrors (n2,!o2)->(n1,!o1).  u->v is a LINK iff u has exactly one distinct out-arc, v exactly one distinct in-arc and
+ *   node(u) != node(v); chains of links come in disjoint mirror pairs, and a unitig is one maximal chain of each pair:
+ *     linear    the orientation whose first node has the smaller index (a single node: '+');
+ *     circular  the orientation that holds the cycle's smallest-index node as '+', starting at that node.
+ *   Unitigs are ordered by the index of their first node; unitig i is named "utg%07d" (i + 1) followed by 'l' or 'c'
+ *   (to_basespace.rs:89,103,294).
+ *   edges: every edge record whose arc is not an interior link, in source order, duplicates kept, as (unitig, +/-, unitig, +/-,
+ *   overlap) with n1 / n2 = 0-based unitig numbers; the closing link of a circular unitig u gives "u + u +" (its mirror "u - u -").
+ *   An overlap larger than either unitig's length becomes min(len_src - 1, len_sink - 1) (to_basespace.rs:312-320).
+ *   Walk of unitig i = entries offsets[i] .. offsets[i+1]: node[] (DbgEntry.index), ori[] ('+' / '-'), and the piece of the unitig's
+ *   sequence the entry contributes (to_basespace.rs:132-153,203-262, with seq = the node's .sequences sequence and (s0, s1) its
+ *   shift_full: first entry '+' all of seq, '-' revcomp(seq); later entries '+' the last s1 bases of seq, '-' revcomp of the first s0
+ *   bases), stored in READ coordinates: bases [src_begin, src_begin + len) of read src_read go to [dst_offset, dst_offset + len) of
+ *   the unitig, passed through utils::revcomp `revcomp` times (0: copied; 1: reverse-complemented; 2: in read order, but through
+ *   revcomp's byte map twice — a node whose sequence is itself a reverse complement, walked '-').  dst_offset is the running sum of
+ *   len inside the unitig and length[] (the LN tag) its total; kc_sum[] the sum of the nodes' abundances (the writer prints
+ *   mc:f = kc_sum / entries, to_basespace.rs:265-288); circular[] 0 / 1.  mdbg_emit_contigs_* (mdbg_emit.h) executes the plan.
+ * mdbg_graph_unitigs: HOST arrays; mdbg_graph_unitigs_device: DEVICE arrays; owned by the context until its next unitig, edge,
+ * finalize or reset call.  n_rounds: pointer-jumping rounds the call ran (at most ceil(log2(2 n)) + 1 to rank the paths, as many
+ * again where there are cycles; a ranking that does not settle inside the bound is reported as MDBG_E_DEVICE, never looped on). */
+typedef struct mdbg_unitig_list {
+    uint64_t n_unitigs, n_entries;
+    const uint64_t* offsets;      /* n_unitigs + 1 */
+    const uint32_t* node; const uint8_t* ori;                                             /* n_entries: the walk */
+    const uint64_t* src_read; const uint64_t* src_begin; const uint32_t* len; const uint8_t* revcomp; const uint64_t* dst_offset;  /* n_entries: the copy plan */
+    const uint64_t* length; const uint64_t* kc_sum; const uint8_t* circular;              /* n_unitigs */
+    mdbg_edge_list edges;         /* unitig edges; presimp_removed = 0 */
+    uint32_t n_rounds, reserved;
+} mdbg_unitig_list;
+int mdbg_graph_unitigs(mdbg_ctx* ctx, mdbg_unitig_list* out);
+int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
+
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),
  * so the ranks may exchange SKETCHES instead (one all-gather), each rank then windows the global sketch but inserts only

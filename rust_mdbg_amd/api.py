@@ -65,6 +65,30 @@ class EdgeList(C.Structure):
                 ("o2", C.POINTER(C.c_uint8)), ("overlap", C.POINTER(C.c_uint32)), ("presimp_removed", C.c_uint64)]
 
 
+class UnitigList(C.Structure):           # mdbg_unitig_list
+    _fields_ = [("n_unitigs", C.c_uint64), ("n_entries", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("node", C.POINTER(C.c_uint32)),
+                ("ori", C.POINTER(C.c_uint8)), ("src_read", C.POINTER(C.c_uint64)), ("src_begin", C.POINTER(C.c_uint64)), ("len", C.POINTER(C.c_uint32)),
+                ("revcomp", C.POINTER(C.c_uint8)), ("dst_offset", C.POINTER(C.c_uint64)), ("length", C.POINTER(C.c_uint64)),
+                ("kc_sum", C.POINTER(C.c_uint64)), ("circular", C.POINTER(C.c_uint8)), ("edges", EdgeList), ("n_rounds", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+UNITIG_FIELDS = (("offsets", np.uint64), ("node", np.uint32), ("ori", np.uint8), ("src_read", np.uint64), ("src_begin", np.uint64), ("len", np.uint32),
+                 ("revcomp", np.uint8), ("dst_offset", np.uint64), ("length", np.uint64), ("kc_sum", np.uint64), ("circular", np.uint8))
+EDGE_FIELDS = (("n1", np.uint32), ("o1", np.uint8), ("n2", np.uint32), ("o2", np.uint8), ("overlap", np.uint32))
+
+
+def unitig_counts(u):
+    """elements of every array of a UnitigList, by field name"""
+    nu, ne = int(u.n_unitigs), int(u.n_entries)
+    return dict(offsets=nu + 1 if nu else 0, node=ne, ori=ne, src_read=ne, src_begin=ne, len=ne, revcomp=ne, dst_offset=ne, length=nu, kc_sum=nu, circular=nu)
+
+
+def unitig_name(i, circular):
+    """name of unitig i (0-based) as the writers print it: the shape of gfatools' names quoted in src/to_basespace.rs:89,103,294"""
+    return "utg%07d%s" % (i + 1, "c" if circular else "l")
+
+
 class PackedBatch(C.Structure):          # mdbg_packed_batch
     _fields_ = [("words", C.c_void_p), ("offsets", C.c_void_p), ("n_reads", C.c_uint64), ("exc_pos", C.c_void_p),
                 ("exc_val", C.c_void_p), ("n_exc", C.c_uint64)]
@@ -81,7 +105,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_insert_resident", "mdbg_route_pack", "mdbg_insert_records", "mdbg_sync", "mdbg_synth_reads_device", "mdbg_copy_to_host", "mdbg_copy_to_device",
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
-           "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device",
+           "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -168,6 +192,8 @@ def load_library():
     L.mdbg_last_batch.argtypes = [vp, C.POINTER(BatchInfo)]
     L.mdbg_graph_edges.argtypes = [vp, C.c_float, C.POINTER(EdgeList)]
     L.mdbg_graph_edges_device.argtypes = [vp, C.c_float, C.POINTER(EdgeList)]
+    L.mdbg_graph_unitigs.argtypes = [vp, C.POINTER(UnitigList)]
+    L.mdbg_graph_unitigs_device.argtypes = [vp, C.POINTER(UnitigList)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -413,6 +439,29 @@ class Mdbg:
         e = EdgeList()
         self._chk(self.L.mdbg_graph_edges_device(self.h, presimp, C.byref(e)))
         return e
+
+    def graph_unitigs(self, raw=False):
+        """unitigs of the last finalize() + graph_edges() and their base-space copy plan, compacted on the GPU (`gfatools asm -u` + the planning half of
+        src/to_basespace.rs; no tip / bubble removal; single GPU) -> dict of numpy arrays named like the fields of mdbg_unitig_list (include/mdbg_hip.h), with
+        `edges` a dict like graph_edges() whose n1 / n2 are 0-based unitig numbers; raw=True: the C struct with HOST arrays (for Emitter.contigs)"""
+        u = UnitigList()
+        self._chk(self.L.mdbg_graph_unitigs(self.h, C.byref(u)))
+        if raw:
+            return u
+        cnt = unitig_counts(u)
+        out = {f: _np(getattr(u, f), cnt[f], t) for f, t in UNITIG_FIELDS}
+        if not len(out["offsets"]):
+            out["offsets"] = np.zeros(1, np.uint64)
+        ne = int(u.edges.n)
+        out.update(n_unitigs=int(u.n_unitigs), n_entries=int(u.n_entries), n_rounds=int(u.n_rounds),
+                   edges={f: _np(getattr(u.edges, f), ne, t) for f, t in EDGE_FIELDS})
+        return out
+
+    def graph_unitigs_device(self):
+        """-> UnitigList with DEVICE pointers (valid until the next unitig / edge / finalize / reset call)"""
+        u = UnitigList()
+        self._chk(self.L.mdbg_graph_unitigs_device(self.h, C.byref(u)))
+        return u
 
     def store_reserve(self, n_minimizers_total, n_reads_total):
         self._chk(self.L.mdbg_store_reserve(self.h, n_minimizers_total, n_reads_total))

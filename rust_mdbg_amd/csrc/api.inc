@@ -14,6 +14,7 @@
 
 #include "../../include/mdbg_hip.h"
 #include "edges.h"
+#include "unitigs.h"
 
 namespace {
 
@@ -221,6 +222,9 @@ struct mdbg_ctx {
     DevBuf w_jstar, w_count, w_ctr, w_start, w_fill, w_occ, w_sorted, w_ath;   // nodes whose u16 abundance wrapped (resolve_wrapped)
     u64 nodes_n = 0; bool nodes_ok = false;  // device node table of the last local finalize is intact
     HostRaw<u32> he_n1, he_n2, he_ov; HostRaw<u8> he_o1, he_o2;           // host copy of the last edge list
+    EdgeResult last_edges{}; bool edges_ok = false;                        // device edge list of the last edge call; edges_ok: it belongs to the node table as it stands (unitigs.hip reads both)
+    UnitigBuffers* ub = nullptr;             // unitig compaction (unitigs.hip), created on first use
+    HostRaw<u64> hu_off, hu_sread, hu_sbegin, hu_dst, hu_length, hu_kc; HostRaw<u32> hu_node, hu_len, hu_n1, hu_n2, hu_ov; HostRaw<u8> hu_ori, hu_rc, hu_circ, hu_o1, hu_o2;   // host copy of the last unitig list
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -923,6 +927,7 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (auto e : c->tile_ev) (void)hipEventDestroy(e);
     if (c->eb) edge_buffers_destroy(c->eb);
+    if (c->ub) unitig_buffers_destroy(c->ub);
     if (c->h_scal) (void)hipHostFree(c->h_scal);
     for (auto& g : c->stage) if (g.st) (void)hipStreamDestroy(g.st);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1625,7 +1630,7 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
             c->fin_rows_guess = n_solid + n_solid / 4 + 1024;
             if (d_row) *d_row = nullptr;
             out->n = n_solid;
-            c->nodes_n = n_solid; c->nodes_ok = true;
+            c->nodes_n = n_solid; c->nodes_ok = true; c->edges_ok = false;
             return finalize_hand_over(c, out, to_host, n_solid);
         }
         STAGE_EVENT(c, c->ev0, s);        // (the span of the plain path starts here; what was written above is overwritten)
@@ -1672,7 +1677,7 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
     c->ms_finalize += ev_ms(c);
     if (d_row) *d_row = F.o_row;
     out->n = n_solid;
-    c->nodes_n = n_solid; c->nodes_ok = !partitioned;
+    c->nodes_n = n_solid; c->nodes_ok = !partitioned; c->edges_ok = false;
     return finalize_hand_over(c, out, to_host, n);
 }
 
@@ -1739,13 +1744,15 @@ static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_h
     if (!(presimp >= 0.0f)) return fail(c, MDBG_E_PARAM, "presimp must be >= 0");
     memset(out, 0, sizeof *out);
     if (!c->nodes_ok && !(c->cap == 0 || c->M == 0)) return fail(c, MDBG_E_STATE, "no finalized node table on this context (call mdbg_finalize / mdbg_finalize_device first)");
-    if (!c->nodes_ok || c->nodes_n == 0) return MDBG_OK;
+    c->edges_ok = false; c->last_edges = EdgeResult{};
+    if (!c->nodes_ok || c->nodes_n == 0) { c->edges_ok = c->nodes_ok; return MDBG_OK; }
     if (c->nodes_n >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
     if (!c->eb) c->eb = edge_buffers_create();
     const FinArgs& F = c->finF;
     EdgeNodes nd; nd.keys = F.o_keys; nd.index = F.o_index; nd.abund = F.o_abund; nd.seqlen = F.o_seqlen; nd.shift = F.o_shift; nd.n = c->nodes_n; nd.k = c->P.k;
     EdgeResult r;
     HIPCHK(c, build_edges(c->eb, nd, presimp, c->stream, &r));
+    c->last_edges = r; c->edges_ok = true;
     out->n = r.n; out->presimp_removed = r.presimp_removed;
     if (!to_host) { out->n1 = r.n1; out->o1 = r.o1; out->n2 = r.n2; out->o2 = r.o2; out->overlap = r.overlap; return MDBG_OK; }
     if (!(c->he_n1.resize(r.n) && c->he_n2.resize(r.n) && c->he_ov.resize(r.n) && c->he_o1.resize(r.n) && c->he_o2.resize(r.n))) return fail(c, MDBG_E_NOMEM, "host copy of the edge list");
@@ -1761,6 +1768,51 @@ static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_h
 }
 int mdbg_graph_edges(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return edges_impl(c, presimp, out, true); }
 int mdbg_graph_edges_device(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return edges_impl(c, presimp, out, false); }
+
+// ---- unitigs + base-space copy plan of the last node table and edge list (unitigs.hip) -------------------
+static int unitigs_impl(mdbg_ctx* c, mdbg_unitig_list* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "unitigs are single-GPU only: not available on a routed or partitioned context");
+    if (c->cap == 0 || c->M == 0) return MDBG_OK;                       // empty context: empty list
+    if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
+    if (c->nodes_n == 0) return MDBG_OK;
+    if (!c->ub) c->ub = unitig_buffers_create();
+    const FinArgs& F = c->finF;
+    UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
+    nd.reversed = F.o_rev; nd.n = c->nodes_n;
+    UnitigResult r; hipError_t he = hipSuccess;
+    const int rc = build_unitigs(c->ub, nd, c->last_edges, c->stream, &r, &he);
+    if (rc == 1) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "build_unitigs", he);
+    if (rc) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, or the walk broke an invariant");
+    const u64 U = r.n_unitigs, N = r.n_entries, E = r.edges.n;
+    out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = E;
+    if (!to_host) {
+        out->offsets = r.offsets; out->node = r.node; out->ori = r.ori; out->src_read = r.src_read; out->src_begin = r.src_begin; out->len = r.len; out->revcomp = r.revcomp;
+        out->dst_offset = r.dst_offset; out->length = r.length; out->kc_sum = r.kc_sum; out->circular = r.circular;
+        out->edges.n1 = r.edges.n1; out->edges.o1 = r.edges.o1; out->edges.n2 = r.edges.n2; out->edges.o2 = r.edges.o2; out->edges.overlap = r.edges.overlap;
+        return MDBG_OK;
+    }
+    if (!(c->hu_off.resize(U + 1) && c->hu_node.resize(N) && c->hu_ori.resize(N) && c->hu_sread.resize(N) && c->hu_sbegin.resize(N) && c->hu_len.resize(N) && c->hu_rc.resize(N) &&
+          c->hu_dst.resize(N) && c->hu_length.resize(U) && c->hu_kc.resize(U) && c->hu_circ.resize(U) && c->hu_n1.resize(E) && c->hu_n2.resize(E) && c->hu_ov.resize(E) &&
+          c->hu_o1.resize(E) && c->hu_o2.resize(E))) return fail(c, MDBG_E_NOMEM, "host copy of the unitig list");
+#define UCOPY(dst, src, cnt, sz) do { if (cnt) HIPCHK(c, hipMemcpy((dst).data(), (src), (size_t)(cnt) * (sz), hipMemcpyDeviceToHost)); } while (0)
+    UCOPY(c->hu_off, r.offsets, U + 1, 8); UCOPY(c->hu_node, r.node, N, 4); UCOPY(c->hu_ori, r.ori, N, 1); UCOPY(c->hu_sread, r.src_read, N, 8); UCOPY(c->hu_sbegin, r.src_begin, N, 8);
+    UCOPY(c->hu_len, r.len, N, 4); UCOPY(c->hu_rc, r.revcomp, N, 1); UCOPY(c->hu_dst, r.dst_offset, N, 8); UCOPY(c->hu_length, r.length, U, 8); UCOPY(c->hu_kc, r.kc_sum, U, 8);
+    UCOPY(c->hu_circ, r.circular, U, 1); UCOPY(c->hu_n1, r.edges.n1, E, 4); UCOPY(c->hu_n2, r.edges.n2, E, 4); UCOPY(c->hu_ov, r.edges.overlap, E, 4); UCOPY(c->hu_o1, r.edges.o1, E, 1);
+    UCOPY(c->hu_o2, r.edges.o2, E, 1);
+#undef UCOPY
+    out->offsets = c->hu_off.data(); out->node = c->hu_node.data(); out->ori = c->hu_ori.data(); out->src_read = c->hu_sread.data(); out->src_begin = c->hu_sbegin.data();
+    out->len = c->hu_len.data(); out->revcomp = c->hu_rc.data(); out->dst_offset = c->hu_dst.data(); out->length = c->hu_length.data(); out->kc_sum = c->hu_kc.data();
+    out->circular = c->hu_circ.data(); out->edges.n1 = c->hu_n1.data(); out->edges.o1 = c->hu_o1.data(); out->edges.n2 = c->hu_n2.data(); out->edges.o2 = c->hu_o2.data();
+    out->edges.overlap = c->hu_ov.data();
+    return MDBG_OK;
+}
+int mdbg_graph_unitigs(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, out, true); }
+int mdbg_graph_unitigs_device(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, out, false); }
 
 // ---- replicated-sketch multi-GPU mode (see include/mdbg_hip.h) ---------------------------------------
 int mdbg_set_partition(mdbg_ctx* c, uint32_t world, uint32_t rank) {

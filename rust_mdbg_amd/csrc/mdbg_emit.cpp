@@ -1372,3 +1372,135 @@ int mdbg_lmer_filter_from_counts(const char* path, uint32_t l, double density, u
 void mdbg_lmer_filter_free(uint64_t* codes) { free(codes); }
 
 }  // extern "C"
+
+// ---- contigs: the copy plan of mdbg_graph_unitigs executed on the host, and the writers ---------------------------------------------
+// What src/to_basespace.rs does between its .sequences pass and its output (:203-262 pieces, :253-262 concatenation, :284-291 S lines, :312-323 L
+// lines), with the pieces taken straight from the reads: the plan (include/mdbg_hip.h) says which bases of which read go where.
+struct mdbg_contigs {
+    u64 n_unitigs = 0, n_entries = 0, n_filled = 0;
+    std::vector<u64> offsets, src_read, src_begin, dst, length, kc_sum, seq_off;
+    std::vector<u32> len, by_read, n1, n2, ov;          // by_read: the entries ordered by src_read
+    std::vector<u8> rc, circular, filled, o1, o2;
+    std::string seq;                                    // the unitigs' sequences, one after the other (seq_off)
+};
+
+namespace {
+std::string unitig_name(u64 i, bool circular) { char b[40]; snprintf(b, sizeof b, "utg%07llu%c", (unsigned long long)(i + 1), circular ? 'c' : 'l'); return b; }
+bool write_all(FILE* f, const std::string& s) { return s.empty() || fwrite(s.data(), 1, s.size(), f) == s.size(); }
+}  // namespace
+
+extern "C" {
+
+mdbg_contigs* mdbg_emit_contigs_open(const mdbg_unitig_list* u, const mdbg_nodes* nodes, int* err) {
+    int dummy; if (!err) err = &dummy;
+    *err = MDBG_OK;
+    if (!u || (u->n_entries && (!u->offsets || !u->src_read || !u->src_begin || !u->len || !u->revcomp || !u->dst_offset)) ||
+        (u->n_unitigs && (!u->offsets || !u->length || !u->kc_sum || !u->circular)) || (u->edges.n && (!u->edges.n1 || !u->edges.o1 || !u->edges.n2 || !u->edges.o2 || !u->edges.overlap)) ||
+        (nodes && nodes->n != u->n_entries)) { *err = MDBG_E_PARAM; return nullptr; }      // (every node of the table lies on exactly one unitig)
+    try {
+        std::unique_ptr<mdbg_contigs> h(new mdbg_contigs());
+        const u64 U = u->n_unitigs, N = u->n_entries, E = u->edges.n;
+        h->n_unitigs = U; h->n_entries = N;
+        if (U) h->offsets.assign(u->offsets, u->offsets + U + 1); else h->offsets.assign(1, 0);
+        h->src_read.assign(u->src_read, u->src_read + N); h->src_begin.assign(u->src_begin, u->src_begin + N); h->dst.assign(u->dst_offset, u->dst_offset + N);
+        h->len.assign(u->len, u->len + N); h->rc.assign(u->revcomp, u->revcomp + N);
+        h->length.assign(u->length, u->length + U); h->kc_sum.assign(u->kc_sum, u->kc_sum + U); h->circular.assign(u->circular, u->circular + U);
+        h->n1.assign(u->edges.n1, u->edges.n1 + E); h->n2.assign(u->edges.n2, u->edges.n2 + E); h->ov.assign(u->edges.overlap, u->edges.overlap + E);
+        h->o1.assign(u->edges.o1, u->edges.o1 + E); h->o2.assign(u->edges.o2, u->edges.o2 + E);
+        if (h->offsets[0] != 0 || h->offsets[U] != N) { *err = MDBG_E_PARAM; return nullptr; }
+        h->seq_off.resize(U + 1); h->seq_off[0] = 0;
+        for (u64 i = 0; i < U; ++i) {
+            if (h->offsets[i] > h->offsets[i + 1]) { *err = MDBG_E_PARAM; return nullptr; }
+            for (u64 e = h->offsets[i]; e < h->offsets[i + 1]; ++e)                     // every piece inside its unitig's buffer
+                if (h->dst[e] > h->length[i] || h->len[e] > h->length[i] - h->dst[e] || h->rc[e] > 2) { *err = MDBG_E_PARAM; return nullptr; }
+            h->seq_off[i + 1] = h->seq_off[i] + h->length[i];
+        }
+        for (u64 e = 0; e < E; ++e) if (h->n1[e] >= U || h->n2[e] >= U) { *err = MDBG_E_PARAM; return nullptr; }
+        h->seq.assign((size_t)h->seq_off[U], '\0');
+        h->filled.assign(N, 0);
+        h->by_read.resize(N);
+        for (u64 e = 0; e < N; ++e) h->by_read[e] = (u32)e;
+        std::sort(h->by_read.begin(), h->by_read.end(), [&](u32 a, u32 b) { return h->src_read[a] != h->src_read[b] ? h->src_read[a] < h->src_read[b] : a < b; });
+        return h.release();
+    } catch (const std::bad_alloc&) { *err = MDBG_E_NOMEM; return nullptr; }
+}
+
+int mdbg_emit_contigs_add_batch(mdbg_contigs* h, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t first_read_ordinal) {
+    if (!h || !offsets || (n_reads && !bases && offsets[n_reads])) return MDBG_E_PARAM;
+    const u64 first = first_read_ordinal;
+    auto lo = std::lower_bound(h->by_read.begin(), h->by_read.end(), first, [&](u32 e, u64 r) { return h->src_read[e] < r; });
+    // the unitig of an entry: the last offset <= e
+    for (; lo != h->by_read.end() && h->src_read[*lo] - first < n_reads; ++lo) {
+        const u32 e = *lo;
+        const u64 r = h->src_read[e] - first, ro = offsets[r], rl = offsets[r + 1] - ro, b = h->src_begin[e], n = h->len[e];
+        if (b > rl || n > rl - b) return MDBG_E_PARAM;                                  // not the reads the table was built from
+        const u64 ui = (u64)(std::upper_bound(h->offsets.begin(), h->offsets.end(), (u64)e) - h->offsets.begin()) - 1;
+        char* d = &h->seq[0] + h->seq_off[ui] + h->dst[e];
+        const u8* s = bases + ro + b;
+        switch (h->rc[e]) {                                                              // utils::revcomp (src/utils.rs:3-24) that many times
+            case 0: memcpy(d, s, n); break;
+            case 1: for (u64 i = 0; i < n; ++i) d[i] = switch_base((char)s[n - 1 - i]); break;
+            default: for (u64 i = 0; i < n; ++i) d[i] = switch_base(switch_base((char)s[i])); break;
+        }
+        if (!h->filled[e]) { h->filled[e] = 1; ++h->n_filled; }
+    }
+    return MDBG_OK;
+}
+
+int mdbg_emit_contigs_write_gfa(mdbg_contigs* h, const char* path) {
+    if (!h || !path) return MDBG_E_PARAM;
+    if (h->n_filled != h->n_entries) return MDBG_E_STATE;
+    FILE* f = fopen(path, "wb");
+    if (!f) return MDBG_E_IO;
+    bool ok = true;
+    try {
+        std::string b = "H\tVN:Z:1.0\n";                                               // to_basespace.rs:252
+        char num[64];
+        for (u64 i = 0; i < h->n_unitigs && ok; ++i) {                                  // :284-291  S\t{name}\t{seq}\tLN:i:{len}\tmc:f:{mean abundance:.1}
+            const u64 cnt = h->offsets[i + 1] - h->offsets[i];
+            b += "S\t"; b += unitig_name(i, h->circular[i] != 0); b += '\t';
+            b.append(h->seq, (size_t)h->seq_off[i], (size_t)h->length[i]);
+            snprintf(num, sizeof num, "\tLN:i:%llu\tmc:f:%.1f\n", (unsigned long long)h->length[i], cnt ? (double)h->kc_sum[i] / (double)cnt : 0.0);
+            b += num;
+            if (b.size() >= (4u << 20)) { ok = write_all(f, b); b.clear(); }
+        }
+        for (u64 e = 0; e < h->n1.size() && ok; ++e) {                                  // :321-323  six fields
+            b += "L\t"; b += unitig_name(h->n1[e], h->circular[h->n1[e]] != 0); b += '\t'; b += (char)h->o1[e]; b += '\t';
+            b += unitig_name(h->n2[e], h->circular[h->n2[e]] != 0); b += '\t'; b += (char)h->o2[e];
+            snprintf(num, sizeof num, "\t%uM\n", h->ov[e]);
+            b += num;
+            if (b.size() >= (4u << 20)) { ok = write_all(f, b); b.clear(); }
+        }
+        ok = ok && write_all(f, b);
+    } catch (const std::bad_alloc&) { fclose(f); return MDBG_E_NOMEM; }
+    if (fclose(f) != 0) ok = false;
+    return ok ? MDBG_OK : MDBG_E_IO;
+}
+
+int mdbg_emit_contigs_write_fasta(mdbg_contigs* h, const char* path, uint64_t min_len) {
+    if (!h || !path) return MDBG_E_PARAM;
+    if (h->n_filled != h->n_entries) return MDBG_E_STATE;
+    FILE* f = fopen(path, "wb");
+    if (!f) return MDBG_E_IO;
+    bool ok = true;
+    for (u64 i = 0; i < h->n_unitigs && ok; ++i) {                                      // utils/gfa2fasta.sh: ">" name, the sequence on one line
+        if (h->length[i] < min_len) continue;
+        const std::string name = unitig_name(i, h->circular[i] != 0);
+        ok = fputc('>', f) != EOF && write_all(f, name) && fputc('\n', f) != EOF &&
+             (h->length[i] == 0 || fwrite(h->seq.data() + h->seq_off[i], 1, (size_t)h->length[i], f) == (size_t)h->length[i]) && fputc('\n', f) != EOF;
+    }
+    if (fclose(f) != 0) ok = false;
+    return ok ? MDBG_OK : MDBG_E_IO;
+}
+
+uint64_t mdbg_emit_contigs_count(const mdbg_contigs* h) { return h ? h->n_unitigs : 0; }
+int mdbg_emit_contigs_get(const mdbg_contigs* h, uint64_t i, const char** seq, uint64_t* len) {
+    if (!h || !seq || !len || i >= h->n_unitigs) return MDBG_E_PARAM;
+    if (h->n_filled != h->n_entries) return MDBG_E_STATE;
+    *seq = h->seq.data() + h->seq_off[i]; *len = h->length[i];
+    return MDBG_OK;
+}
+
+void mdbg_emit_contigs_close(mdbg_contigs* h) { delete h; }
+
+}  // extern "C"

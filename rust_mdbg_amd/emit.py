@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .api import Nodes
+from .api import EDGE_FIELDS, MDBG_E_STATE, UNITIG_FIELDS, MdbgError, Nodes, UnitigList
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -15,7 +15,8 @@ from .api import EdgeList as Edges          # one type for the host emitter's an
 
 
 EXPORTS = ["mdbg_lmer_filter_from_counts", "mdbg_lmer_filter_free", "mdbg_packed_words", "mdbg_pack_reads", "mdbg_seqfile_write_batch_part", "mdbg_emit_create", "mdbg_emit_destroy", "mdbg_emit_edges", "mdbg_emit_write_gfa", "mdbg_seqfile_open",
-           "mdbg_seqfile_write_batch", "mdbg_seqfile_close"]
+           "mdbg_seqfile_write_batch", "mdbg_seqfile_close", "mdbg_emit_contigs_open", "mdbg_emit_contigs_add_batch", "mdbg_emit_contigs_write_gfa",
+           "mdbg_emit_contigs_write_fasta", "mdbg_emit_contigs_count", "mdbg_emit_contigs_get", "mdbg_emit_contigs_close"]
 
 
 def load_library():
@@ -42,6 +43,16 @@ def load_library():
                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mdbg_lmer_filter_free.argtypes = [vp]
         L.mdbg_lmer_filter_free.restype = None
+        L.mdbg_emit_contigs_open.restype = vp
+        L.mdbg_emit_contigs_open.argtypes = [C.POINTER(UnitigList), C.POINTER(Nodes), C.POINTER(C.c_int)]
+        L.mdbg_emit_contigs_add_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
+        L.mdbg_emit_contigs_write_gfa.argtypes = [vp, C.c_char_p]
+        L.mdbg_emit_contigs_write_fasta.argtypes = [vp, C.c_char_p, C.c_uint64]
+        L.mdbg_emit_contigs_count.restype = C.c_uint64
+        L.mdbg_emit_contigs_count.argtypes = [vp]
+        L.mdbg_emit_contigs_get.argtypes = [vp, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
+        L.mdbg_emit_contigs_close.argtypes = [vp]
+        L.mdbg_emit_contigs_close.restype = None
         _LIB = L
     return _LIB
 
@@ -62,6 +73,77 @@ class NodeTable:
                        seqlen=P("seqlen", C.c_uint32), shift=P("shift", C.c_uint16), shift_full=P("shift_full", C.c_uint64),
                        src_read=P("src_read", C.c_uint64), src_start=P("src_start", C.c_uint64), src_end=P("src_end", C.c_uint64),
                        reversed=P("reversed", C.c_uint8), n_distinct=int(nodes.get("n_nodes_before", 0)), n_wrapped=int(nodes.get("n_wrapped", 0)))
+
+
+def unitig_list(u):
+    """dict of arrays shaped like Mdbg.graph_unitigs() -> (UnitigList with HOST pointers, the arrays that must outlive it)"""
+    keep = {f: np.ascontiguousarray(u[f], dtype=t) for f, t in UNITIG_FIELDS}
+    keep.update({"e_" + f: np.ascontiguousarray(u["edges"][f], dtype=t) for f, t in EDGE_FIELDS})
+    P = lambda a: a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+    out = UnitigList(n_unitigs=len(keep["length"]), n_entries=len(keep["node"]), **{f: P(keep[f]) for f, _ in UNITIG_FIELDS})
+    out.edges.n = len(keep["e_n1"])
+    for f, _ in EDGE_FIELDS:
+        setattr(out.edges, f, P(keep["e_" + f]))
+    return out, keep
+
+
+class Contigs:
+    """unitig sequences stitched on the host from the copy plan of Mdbg.graph_unitigs (include/mdbg_emit.h, mdbg_emit_contigs_*)"""
+
+    def __init__(self, unitigs, n_nodes=None):
+        """unitigs: Mdbg.graph_unitigs(raw=True) or the dict of graph_unitigs(); n_nodes: size of the node table, checked against the list when given"""
+        self.L = load_library()
+        u, self._keep = (unitigs, None) if isinstance(unitigs, UnitigList) else unitig_list(unitigs)
+        nd = None if n_nodes is None else C.byref(Nodes(n=n_nodes))
+        err = C.c_int()
+        self.h = self.L.mdbg_emit_contigs_open(C.byref(u), nd, C.byref(err))
+        if not self.h:
+            raise MdbgError(err.value, "mdbg_emit_contigs_open")
+        self._keep = None                                  # the handle holds its own copy
+
+    def _chk(self, rc, what):
+        if rc:
+            raise MdbgError(rc, what + (": a batch of the reads has not been fed" if rc == MDBG_E_STATE else ""))
+
+    def add_batch(self, bases, offsets, first_read_ordinal=0):
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._chk(self.L.mdbg_emit_contigs_add_batch(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, first_read_ordinal), "mdbg_emit_contigs_add_batch")
+
+    def write_gfa(self, path):
+        self._chk(self.L.mdbg_emit_contigs_write_gfa(self.h, os.fsencode(path)), "mdbg_emit_contigs_write_gfa")
+
+    def write_fasta(self, path, min_len=0):
+        self._chk(self.L.mdbg_emit_contigs_write_fasta(self.h, os.fsencode(path), min_len), "mdbg_emit_contigs_write_fasta")
+
+    def __len__(self):
+        return int(self.L.mdbg_emit_contigs_count(self.h))
+
+    def sequences(self):
+        """-> list of bytes, one per unitig"""
+        out = []
+        for i in range(int(self.L.mdbg_emit_contigs_count(self.h))):
+            p, n = C.c_char_p(), C.c_uint64()
+            self._chk(self.L.mdbg_emit_contigs_get(self.h, i, C.byref(p), C.byref(n)), "mdbg_emit_contigs_get")
+            out.append(C.string_at(p, n.value))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mdbg_emit_contigs_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Emitter:
@@ -112,6 +194,22 @@ class Emitter:
             rc = self.L.mdbg_seqfile_close(f)
         if rc:
             raise RuntimeError("mdbg_seqfile_close failed: %d" % rc)
+
+    def contigs(self, unitigs, batches, gfa_path=None, fasta_path=None, min_len=0, n_nodes=None):
+        """stitches the unitigs of Mdbg.graph_unitigs() from the reads and writes them: batches as write_sequences takes them (what was ingested);
+        gfa_path / fasta_path: files to write (None: not written) -> the open Contigs (sequences(); close() it when done)"""
+        c = Contigs(unitigs, n_nodes)
+        try:
+            for bases, offsets, first in batches:
+                c.add_batch(bases, offsets, first)
+            if gfa_path is not None:
+                c.write_gfa(gfa_path)
+            if fasta_path is not None:
+                c.write_fasta(fasta_path, min_len)
+        except BaseException:
+            c.close()
+            raise
+        return c
 
     def write_sequences_parallel(self, prefix, nodes, l, batches, threads):
         """`threads` files "<prefix>.<t>.sequences" (the reference's one-file-per-worker layout, src/main.rs:614-630) written by as many

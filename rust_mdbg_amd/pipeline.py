@@ -8,7 +8,7 @@ import threading
 import time
 
 from .api import Mdbg
-from .emit import Emitter, Reader, lmer_filter_from_counts
+from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 
 def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max):
@@ -21,8 +21,11 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None):
+             threads=1, packed=None, contigs=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
+    contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
+    (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
+    to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
     threads: host threads of the reader (uncompressed input: mdbg_reader_open_mt) and of the 2-bit packer; packed: hand the GPU 2-bit
     packed batches (a quarter of the bytes over PCIe), default: when threads > 1"""
     if packed is None:
@@ -120,25 +123,40 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             em = Emitter()
             em.write_gfa(prefix + ".gfa", nodes, raw)
             tm["gfa"] = time.perf_counter() - t0
+            ctg = None
+            if contigs:                                  # the plan is copied out of the context here; the bases follow in the second pass
+                ctg = Contigs(m.graph_unitigs(raw=True), nodes["n_nodes"])
+                tm["unitigs"] = time.perf_counter() - t0
         tm["close"] = time.perf_counter() - t0
     finally:
         stop.set()                          # error or not: release the reader (it closes the file) and wait for it
         th.join()
     tm["reader_closed"] = time.perf_counter() - t0
-    if write_sequences:                              # second pass over the input for the node sequences
+    if write_sequences or ctg is not None:           # second pass over the input for the node sequences and the contigs' bases
         def again():
             first = 0
             with Reader(path, strip_newlines, threads=threads) as r:
                 for bases, offs in r.batches(batch_bases, copy=False):      # consumed before the next batch is asked for
+                    if ctg is not None:
+                        ctg.add_batch(bases, offs, first)
                     yield bases, offs, first
                     first += len(offs) - 1
         t1 = time.perf_counter()
-        if threads > 1:                              # one file per writer thread, like the reference's worker threads (main.rs:614-630)
+        if not write_sequences:
+            for _ in again():
+                pass
+        elif threads > 1:                              # one file per writer thread, like the reference's worker threads (main.rs:614-630)
             em.write_sequences_parallel(prefix, nodes, l, again(), min(threads, 16))
         else:
             em.write_sequences(prefix + ".0.sequences", nodes, l, again())
         tm["sequences"] = time.perf_counter() - t1
-    return dict(n_reads=n_reads, n_bases=n_bases, n_minimizers=stats["n_minimizers"], n_windows=stats["n_windows"],
+    extra = {}
+    if ctg is not None:
+        with ctg:
+            ctg.write_gfa(prefix + ".unitigs.gfa")
+            ctg.write_fasta(prefix + ".unitigs.fa")
+            extra["n_unitigs"] = len(ctg)
+    return dict(extra, n_reads=n_reads, n_bases=n_bases, n_minimizers=stats["n_minimizers"], n_windows=stats["n_windows"],
                 n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=len(edges["n1"]),
                 presimp_removed=edges["presimp_removed"], seconds_until={k_: round(v, 4) for k_, v in tm.items()})
 
@@ -165,7 +183,9 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     into contigs is the caller's (the script shells out to magic_simplify = gfatools + to_basespace, outside this path); what it
     returns is filtered like `seqtk seq -L 100000` (min_contig_len), taken TWICE (`zcat -f x.msimpl.fa x.msimpl.fa`, utils/multik:72)
     and put IN FRONT of the reads for the next k: the reads keep their resident sketches and their ordinals (READ_ORDINAL_BASE + i),
-    the contigs get the ordinals 0 .. 2C-1, and the previous round's contigs are forgotten (mdbg_rewind)."""
+    the contigs get the ordinals 0 .. 2C-1, and the previous round's contigs are forgotten (mdbg_rewind).
+    contigs_fn="unitigs": the built-in producer — the round's unitigs (Mdbg.graph_unitigs: `gfatools asm -u` + to_basespace, WITHOUT magic_simplify's tip and
+    bubble rounds), stitched from the previous round's contigs and one more pass over the reads per round."""
     ks = list(ks)
     out = {}
     n_reads = n_bases = 0
@@ -196,6 +216,17 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
             out[k] = dict(n_reads=n_reads, n_bases=n_bases, n_contigs=len(contigs), n_minimizers=st["n_minimizers"], n_windows=st["n_windows"],
                           n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=int(raw.n),
                           presimp_removed=int(raw.presimp_removed))
-            if contigs_fn is not None:
+            if contigs_fn == "unitigs":
+                def fed():                               # what this round ingested, with its ordinals: the contigs in front, then the reads
+                    if contigs:
+                        yield concat_records(contigs + contigs) + (0,)
+                    first = base
+                    with Reader(path, strip_newlines) as r2:
+                        for bases, offs in r2.batches(batch_bases, copy=False):
+                            yield bases, offs, first
+                            first += len(offs) - 1
+                with em.contigs(m.graph_unitigs(raw=True), fed(), n_nodes=nodes["n_nodes"]) as ctg:
+                    contigs = [c for c in ctg.sequences() if len(c) >= min_contig_len]
+            elif contigs_fn is not None:
                 contigs = [bytes(c) for c in contigs_fn(k, gfa, nodes) if len(c) >= min_contig_len]
     return out
