@@ -74,6 +74,12 @@ int main(int argc, char** argv) {
     const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
+    /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L append steps of their own, in command-line order */
+    static const mdbg_simplify_step magic[] = {{MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000},
+        {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000},
+        {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}, {MDBG_SIMPLIFY_TIPS, 10, 150000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}};
+    enum { MAX_STEPS = 256 };
+    mdbg_simplify_step steps[MAX_STEPS]; uint32_t n_steps = 0; int simplify = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-k") && i + 1 < argc) p.k = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "-l") && i + 1 < argc) p.l = (uint32_t)atoi(argv[++i]);
@@ -89,14 +95,28 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--lmer_counts_max") && i + 1 < argc) lc_max = (uint32_t)strtoul(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "--timing")) timing = 1;
         else if (!strcmp(argv[i], "--contigs")) contigs = 1;
+        else if (!strcmp(argv[i], "--simplify")) {
+            simplify = 1;
+            for (uint32_t j = 0; j < sizeof magic / sizeof magic[0] && n_steps < MAX_STEPS; ++j) steps[n_steps++] = magic[j];
+        }
+        else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "-b")) && i + 1 < argc) {
+            const int tip = argv[i][1] == 't';
+            char* end = NULL; const char* a = argv[++i];
+            mdbg_simplify_step st; st.kind = tip ? MDBG_SIMPLIFY_TIPS : MDBG_SIMPLIFY_BUBBLES; st.max_nodes = 0;
+            if (tip) { st.max_nodes = (uint32_t)strtoul(a, &end, 10); if (*end != ',') { fprintf(stderr, "-t wants N,L\n"); return 2; } a = end + 1; }
+            st.max_bases = strtoull(a, &end, 10);
+            if (*end || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b\n"); return 2; }
+            steps[n_steps++] = st; simplify = 1;
+        }
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
+    if (simplify) contigs = 1;
 
     int err = 0;
     mdbg_ctx* ctx = mdbg_create(&p, &err);
@@ -167,7 +187,19 @@ int main(int argc, char** argv) {
     if (rc) die(NULL, "mdbg_emit_write_gfa", rc);
     if (timing) fprintf(stderr, "timing: %llu reads, %llu bases; ingest %.3f s, to .gfa %.3f s (%.2f Gbases/s; context creation not included); ingest loop: waiting for the reader %.3f, mdbg_ingest_batch_packed %.3f s\n",
                         (unsigned long long)n_reads, (unsigned long long)n_bases, t_ingest - t0, now_s() - t0, (double)n_bases / (now_s() - t0) / 1e9, t_wait, t_gpu);
-    mdbg_contigs* ctg = NULL;
+    mdbg_contigs* ctg = NULL; mdbg_contigs* sctg = NULL;
+    if (simplify) {                                                 /* tips and simple bubbles removed on the GPU (this project's own rules, not gfatools parity: mdbg_hip.h) */
+        mdbg_unitig_list sl; mdbg_simplify_stats ss;
+        rc = mdbg_graph_simplify(ctx, steps, n_steps, &sl, &ss);
+        if (rc) die(ctx, "mdbg_graph_simplify", rc);
+        for (uint32_t j = 0; j < ss.n_steps; ++j)
+            printf("simplify step %u (%s %u,%llu): %llu unitigs, %llu nodes removed\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_TIPS ? "tips" : "bubbles", steps[j].max_nodes,
+                   (unsigned long long)steps[j].max_bases, (unsigned long long)ss.unitigs_removed[j], (unsigned long long)ss.nodes_removed[j]);
+        printf("simplify: %llu unitigs, %llu nodes removed; %llu contigs left\n", (unsigned long long)ss.total_unitigs_removed, (unsigned long long)ss.total_nodes_removed,
+               (unsigned long long)sl.n_unitigs);
+        sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
+        if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
+    }
     if (contigs) {                                                  /* unitigs + copy plan from the GPU; the handle keeps its own copy of the plan */
         mdbg_unitig_list ul;
         rc = mdbg_graph_unitigs(ctx, &ul);
@@ -196,6 +228,7 @@ int main(int argc, char** argv) {
             if (rc) die(NULL, "mdbg_reader_next", rc);
             if (!n) break;
             if (ctg) { rc = mdbg_emit_contigs_add_batch(ctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
+            if (sctg) { rc = mdbg_emit_contigs_add_batch(sctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
             for (int t = 0; t < nw; ++t) {
                 seqjob_t jb; jb.sf = sf[t]; jb.nodes = &nodes; jb.part = (uint32_t)t; jb.n_parts = (uint32_t)nw; jb.bases = bases; jb.offs = offs; jb.n = n; jb.first = first; jb.rc = 0;
                 job[t] = jb;
@@ -218,6 +251,15 @@ int main(int argc, char** argv) {
         rc = mdbg_emit_contigs_write_fasta(ctg, path, 0);
         if (rc) die(NULL, "mdbg_emit_contigs_write_fasta", rc);
         mdbg_emit_contigs_close(ctg);
+    }
+    if (sctg) {
+        snprintf(path, sizeof path, "%s.msimpl.gfa", prefix);
+        rc = mdbg_emit_contigs_write_gfa(sctg, path);
+        if (rc) die(NULL, "mdbg_emit_contigs_write_gfa", rc);
+        snprintf(path, sizeof path, "%s.msimpl.fa", prefix);
+        rc = mdbg_emit_contigs_write_fasta(sctg, path, 0);
+        if (rc) die(NULL, "mdbg_emit_contigs_write_fasta", rc);
+        mdbg_emit_contigs_close(sctg);
     }
     mdbg_destroy(ctx);
     return 0;

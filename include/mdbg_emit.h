@@ -106,7 +106,10 @@ void mdbg_lmer_filter_free(uint64_t* codes);
 
 /* ---- contigs: unitig sequences from the copy plan of mdbg_graph_unitigs (mdbg_hip.h) — the stitching and output half of
  * src/to_basespace.rs (:203-262 pieces, :252,284-291 H / S lines, :312-323 L lines) and utils/gfa2fasta.sh.  Like the unitig list
- * itself this is `gfatools asm -u` + to_basespace only: no tip or bubble removal.
+ * itself this is `gfatools asm -u` + to_basespace only: no tip or bubble removal — unless the list comes from mdbg_graph_simplify (mdbg_hip.h),
+ * which returns the same layout for the graph left after its tip / bubble steps (own rules, not gfatools parity).  Such a list covers the surviving
+ * nodes only (n_entries < nodes->n): open it with nodes = NULL.  Its plan entries name reads of surviving nodes only, so add_batch and the writers
+ * treat it like any other list.
  *   mdbg_emit_contigs_open        copies the list (HOST arrays of mdbg_graph_unitigs; it may be released afterwards) and allocates every
  *                                 unitig's sequence from length[].  nodes: the table the list was made from, or NULL; only nodes->n is
  *                                 read (it must equal n_entries: every node lies on exactly one unitig).

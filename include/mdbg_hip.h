@@ -317,7 +317,7 @@ int mdbg_graph_edges_device(mdbg_ctx* ctx, float presimp, mdbg_edge_list* out);
 /* ---- unitigs and the base-space copy plan (replaces `gfatools asm -u` + the planning half of src/to_basespace.rs) --------
  * Every documented run of the reference pipes its .gfa through `gfatools asm -u` (compaction of non-branching paths) and the
  * to_basespace binary to get sequences; this is that step — and only that step: no tip or bubble removal (magic_simplify's
- * -t / -b rounds) — on the node table of the last mdbg_finalize* and the edge list of the last mdbg_graph_edges* of the context
+ * -t / -b rounds: see mdbg_graph_simplify below) — on the node table of the last mdbg_finalize* and the edge list of the last mdbg_graph_edges* of the context
  * (with whatever presimp that call used).  MDBG_E_STATE without a current edge list (a finalize or an ingest since the last edge
  * call), and on routed / partitioned contexts: SINGLE-GPU ONLY.  An empty context gives an empty list.
  *
@@ -340,7 +340,7 @@ int mdbg_graph_edges_device(mdbg_ctx* ctx, float presimp, mdbg_edge_list* out);
  *   revcomp's byte map twice — a node whose sequence is itself a reverse complement, walked '-').  dst_offset is the running sum of
  *   len inside the unitig and length[] (the LN tag) its total; kc_sum[] the sum of the nodes' abundances (the writer prints
  *   mc:f = kc_sum / entries, to_basespace.rs:265-288); circular[] 0 / 1.  mdbg_emit_contigs_* (mdbg_emit.h) executes the plan.
- * mdbg_graph_unitigs: HOST arrays; mdbg_graph_unitigs_device: DEVICE arrays; owned by the context until its next unitig, edge,
+ * mdbg_graph_unitigs: HOST arrays; mdbg_graph_unitigs_device: DEVICE arrays; owned by the context until its next unitig, simplify, edge,
  * finalize or reset call.  n_rounds: pointer-jumping rounds the call ran (at most ceil(log2(2 n)) + 1 to rank the paths, as many
  * again where there are cycles; a ranking that does not settle inside the bound is reported as MDBG_E_DEVICE, never looped on). */
 typedef struct mdbg_unitig_list {
@@ -354,6 +354,50 @@ typedef struct mdbg_unitig_list {
 } mdbg_unitig_list;
 int mdbg_graph_unitigs(mdbg_ctx* ctx, mdbg_unitig_list* out);
 int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
+
+/* ---- graph simplification: tip clipping and simple-bubble popping (the -t / -b rounds of utils/magic_simplify) --------------
+ * Runs a caller-given schedule of steps on the GPU and returns the unitig list (same layout, same ownership rule, same state
+ * requirements as mdbg_graph_unitigs: a current edge list, SINGLE GPU ONLY) of the graph that is left.  With n_steps = 0 the result
+ * equals mdbg_graph_unitigs array for array.  The first `gfatools asm` line of utils/magic_simplify is the schedule
+ * t t b b t b b b t b t B T B with t = {TIPS, 10, 50000}, b = {BUBBLES, 0, 100000}, B = {BUBBLES, 0, 1000000}, T = {TIPS, 10, 150000}.
+ *
+ * THE RULES ARE THIS PROJECT'S OWN DEFINITION, NOT BIT-PARITY WITH GFATOOLS.  gfatools deletes in place while it scans, so its result
+ * depends on vertex order; the rules below are order-free (a parallel implementation and a dictionary-and-set checker must agree:
+ * tests/simplify_restatement.py).  The two outputs have never been compared.
+ *
+ *   State: a set S of surviving nodes, at first all nodes of the table.  The current graph is the arc set of mdbg_graph_unitigs
+ *   restricted to arcs whose two nodes are in S; the current unitigs are its unitigs by the definition above (order, orientation,
+ *   names, length, kc_sum unchanged).  A step chooses unitigs to remove — every decision against the graph as it is when the step
+ *   starts — and removes all their nodes from S.
+ *   A unitig is SMALL for a step iff it is not circular, has at most max_nodes entries and length <= max_bases (0 = no limit).
+ *   a BEATS b: higher mean abundance kc_sum / entries (compared exactly by cross-multiplication), then larger length, then the
+ *   smaller unitig number.
+ *   TIPS.  Orient a small unitig u so that its first vertex has no in-arc.  u is a tip candidate iff that is possible in exactly
+ *   one of its two orientations (a unitig with two dead ends is an isolated piece and is never removed: a deliberate difference from
+ *   gfatools); x = the last vertex in that orientation, its attached vertex.  u is removed iff for every arc x -> w the vertex w has
+ *   another in-neighbour x' != x that is not the attached vertex of a tip candidate, or is the attached vertex of a candidate that
+ *   beats u.  Hence a vertex that survives and had an in-arc keeps one: clipping never makes a new dead end, and where every way
+ *   into w is a small tip the best one stays.
+ *   BUBBLES (simple ones only).  A small unitig u with first vertex f and last vertex t is a branch iff f has exactly one in-arc
+ *   p -> f, t exactly one out-arc t -> q, neither node(p) nor node(q) lies on u, and q != comp(p).  Its key is the smaller of (p, q)
+ *   and (comp(q), comp(p)) under the vertex order 2 * index + minus.  Of the branches with one key all but the one that beats the
+ *   others are removed.  Branches that branch themselves (superbubbles) are not treated; repeated tip and bubble steps reduce many
+ *   of them to simple ones.
+ *   Result: n_entries = |S|; edges = every edge record whose two nodes survive and whose arc is not an interior link, in source order.
+ * MDBG_E_PARAM: an unknown kind, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
+ * entries owned by the context (valid like the list); n_compactions: compactions run (a step that removes nothing is followed by none);
+ * n_syncs: host synchronisations of the call (per step: those of one compaction + 1). */
+#define MDBG_SIMPLIFY_TIPS 1u
+#define MDBG_SIMPLIFY_BUBBLES 2u
+typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
+typedef struct mdbg_simplify_stats {
+    uint32_t n_steps, n_compactions;
+    const uint64_t* unitigs_removed; const uint64_t* nodes_removed;      /* n_steps */
+    uint64_t total_unitigs_removed, total_nodes_removed;
+    uint32_t n_rounds_total, n_syncs;
+} mdbg_simplify_stats;
+int mdbg_graph_simplify(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
+int mdbg_graph_simplify_device(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
 
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),

@@ -84,6 +84,31 @@ def unitig_counts(u):
     return dict(offsets=nu + 1 if nu else 0, node=ne, ori=ne, src_read=ne, src_begin=ne, len=ne, revcomp=ne, dst_offset=ne, length=nu, kc_sum=nu, circular=nu)
 
 
+class SimplifyStep(C.Structure):       # mdbg_simplify_step
+    _fields_ = [("kind", C.c_uint32), ("max_nodes", C.c_uint32), ("max_bases", C.c_uint64)]
+
+
+class SimplifyStats(C.Structure):      # mdbg_simplify_stats
+    _fields_ = [("n_steps", C.c_uint32), ("n_compactions", C.c_uint32), ("unitigs_removed", C.POINTER(C.c_uint64)), ("nodes_removed", C.POINTER(C.c_uint64)),
+                ("total_unitigs_removed", C.c_uint64), ("total_nodes_removed", C.c_uint64), ("n_rounds_total", C.c_uint32), ("n_syncs", C.c_uint32)]
+
+
+MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
+_T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
+# the schedule of the first `gfatools asm` line of utils/magic_simplify, as (kind, max_nodes, max_bases): -t N,L = tips of at most N nodes and L bases,
+# -b L = bubbles whose branches have at most L bases.  Same schedule, this project's own order-free rules (include/mdbg_hip.h): not gfatools parity.
+MAGIC_SIMPLIFY_STEPS = [_T, _T, _B, _B, _T, _B, _B, _B, _T, _B, _T, (MDBG_SIMPLIFY_BUBBLES, 0, 1000000), (MDBG_SIMPLIFY_TIPS, 10, 150000),
+                        (MDBG_SIMPLIFY_BUBBLES, 0, 1000000)]
+
+
+def simplify_steps(steps):
+    """[(kind, max_nodes, max_bases)] -> (ctypes array of mdbg_simplify_step or None, n)"""
+    steps = [tuple(int(x) for x in s) for s in steps]
+    if not steps:
+        return None, 0
+    return (SimplifyStep * len(steps))(*[SimplifyStep(k, mn, mb) for k, mn, mb in steps]), len(steps)
+
+
 def unitig_name(i, circular):
     """name of unitig i (0-based) as the writers print it: the shape of gfatools' names quoted in src/to_basespace.rs:89,103,294"""
     return "utg%07d%s" % (i + 1, "c" if circular else "l")
@@ -106,6 +131,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -194,6 +220,8 @@ def load_library():
     L.mdbg_graph_edges_device.argtypes = [vp, C.c_float, C.POINTER(EdgeList)]
     L.mdbg_graph_unitigs.argtypes = [vp, C.POINTER(UnitigList)]
     L.mdbg_graph_unitigs_device.argtypes = [vp, C.POINTER(UnitigList)]
+    L.mdbg_graph_simplify.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
+    L.mdbg_graph_simplify_device.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -442,12 +470,14 @@ class Mdbg:
 
     def graph_unitigs(self, raw=False):
         """unitigs of the last finalize() + graph_edges() and their base-space copy plan, compacted on the GPU (`gfatools asm -u` + the planning half of
-        src/to_basespace.rs; no tip / bubble removal; single GPU) -> dict of numpy arrays named like the fields of mdbg_unitig_list (include/mdbg_hip.h), with
+        src/to_basespace.rs; no tip / bubble removal: that is graph_simplify; single GPU) -> dict of numpy arrays named like the fields of mdbg_unitig_list (include/mdbg_hip.h), with
         `edges` a dict like graph_edges() whose n1 / n2 are 0-based unitig numbers; raw=True: the C struct with HOST arrays (for Emitter.contigs)"""
         u = UnitigList()
         self._chk(self.L.mdbg_graph_unitigs(self.h, C.byref(u)))
-        if raw:
-            return u
+        return u if raw else self._unitig_dict(u)
+
+    @staticmethod
+    def _unitig_dict(u):
         cnt = unitig_counts(u)
         out = {f: _np(getattr(u, f), cnt[f], t) for f, t in UNITIG_FIELDS}
         if not len(out["offsets"]):
@@ -462,6 +492,33 @@ class Mdbg:
         u = UnitigList()
         self._chk(self.L.mdbg_graph_unitigs_device(self.h, C.byref(u)))
         return u
+
+    @staticmethod
+    def _simplify_stats(st):
+        n = int(st.n_steps)
+        return dict(unitigs_removed=[int(st.unitigs_removed[i]) for i in range(n)], nodes_removed=[int(st.nodes_removed[i]) for i in range(n)],
+                    total_unitigs_removed=int(st.total_unitigs_removed), total_nodes_removed=int(st.total_nodes_removed), n_compactions=int(st.n_compactions),
+                    n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs))
+
+    def graph_simplify(self, steps, raw=False):
+        """the unitigs that are left after a schedule of tip and simple-bubble steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
+        project's own order-free rules in the spirit of `gfatools asm -t N,L -b L`, NOT bit-parity with gfatools).  steps: [(kind, max_nodes, max_bases)], e.g.
+        MAGIC_SIMPLIFY_STEPS; an empty schedule gives graph_unitigs().  -> the dict of graph_unitigs() plus `stats` (per step: unitigs / nodes removed; totals);
+        raw=True: (the C struct with HOST arrays, stats)"""
+        arr, n = simplify_steps(steps)
+        u, st = UnitigList(), SimplifyStats()
+        self._chk(self.L.mdbg_graph_simplify(self.h, arr, n, C.byref(u), C.byref(st)))
+        stats = self._simplify_stats(st)
+        if raw:
+            return u, stats
+        return dict(self._unitig_dict(u), stats=stats)
+
+    def graph_simplify_device(self, steps):
+        """-> (UnitigList with DEVICE pointers, valid until the next unitig / simplify / edge / finalize / reset call; stats)"""
+        arr, n = simplify_steps(steps)
+        u, st = UnitigList(), SimplifyStats()
+        self._chk(self.L.mdbg_graph_simplify_device(self.h, arr, n, C.byref(u), C.byref(st)))
+        return u, self._simplify_stats(st)
 
     def store_reserve(self, n_minimizers_total, n_reads_total):
         self._chk(self.L.mdbg_store_reserve(self.h, n_minimizers_total, n_reads_total))

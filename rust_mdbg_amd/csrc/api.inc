@@ -15,6 +15,7 @@
 #include "../../include/mdbg_hip.h"
 #include "edges.h"
 #include "unitigs.h"
+#include "simplify.h"
 
 namespace {
 
@@ -225,6 +226,7 @@ struct mdbg_ctx {
     EdgeResult last_edges{}; bool edges_ok = false;                        // device edge list of the last edge call; edges_ok: it belongs to the node table as it stands (unitigs.hip reads both)
     UnitigBuffers* ub = nullptr;             // unitig compaction (unitigs.hip), created on first use
     HostRaw<u64> hu_off, hu_sread, hu_sbegin, hu_dst, hu_length, hu_kc; HostRaw<u32> hu_node, hu_len, hu_n1, hu_n2, hu_ov; HostRaw<u8> hu_ori, hu_rc, hu_circ, hu_o1, hu_o2;   // host copy of the last unitig list
+    std::vector<u64> hs_unitigs, hs_nodes;   // per-step removal counts of the last mdbg_graph_simplify
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -1770,12 +1772,20 @@ int mdbg_graph_edges(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return e
 int mdbg_graph_edges_device(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return edges_impl(c, presimp, out, false); }
 
 // ---- unitigs + base-space copy plan of the last node table and edge list (unitigs.hip) -------------------
-static int unitigs_impl(mdbg_ctx* c, mdbg_unitig_list* out, bool to_host) {
-    if (!c || !out) return MDBG_E_PARAM;
+// steps == nullptr: plain compaction (mdbg_graph_unitigs); otherwise the schedule runs first (mdbg_graph_simplify, simplify.hip) and stats is filled
+static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats, bool to_host) {
+    if (!c || !out || (stats && n_steps && !steps)) return MDBG_E_PARAM;
     MDBG_LOCK(c);
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
     memset(out, 0, sizeof *out);
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        for (uint32_t i = 0; i < n_steps; ++i)
+            if (steps[i].kind != MDBG_SIMPLIFY_TIPS && steps[i].kind != MDBG_SIMPLIFY_BUBBLES) return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+        c->hs_unitigs.assign(n_steps, 0); c->hs_nodes.assign(n_steps, 0);
+        stats->n_steps = n_steps; stats->unitigs_removed = c->hs_unitigs.data(); stats->nodes_removed = c->hs_nodes.data();
+    }
     if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "unitigs are single-GPU only: not available on a routed or partitioned context");
     if (c->cap == 0 || c->M == 0) return MDBG_OK;                       // empty context: empty list
     if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
@@ -1785,9 +1795,15 @@ static int unitigs_impl(mdbg_ctx* c, mdbg_unitig_list* out, bool to_host) {
     UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
     nd.reversed = F.o_rev; nd.n = c->nodes_n;
     UnitigResult r; hipError_t he = hipSuccess;
-    const int rc = build_unitigs(c->ub, nd, c->last_edges, c->stream, &r, &he);
+    SimplifyInfo si{};
+    const int rc = stats ? simplify_unitigs(c->ub, nd, c->last_edges, steps, n_steps, c->stream, &r, c->hs_unitigs.data(), c->hs_nodes.data(), &si, &he)
+                         : build_unitigs(c->ub, nd, c->last_edges, c->stream, &r, &he);
     if (rc == 1) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "build_unitigs", he);
     if (rc) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, or the walk broke an invariant");
+    if (stats) {
+        stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
+        for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += c->hs_unitigs[i]; stats->total_nodes_removed += c->hs_nodes[i]; }
+    }
     const u64 U = r.n_unitigs, N = r.n_entries, E = r.edges.n;
     out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = E;
     if (!to_host) {
@@ -1811,8 +1827,16 @@ static int unitigs_impl(mdbg_ctx* c, mdbg_unitig_list* out, bool to_host) {
     out->edges.overlap = c->hu_ov.data();
     return MDBG_OK;
 }
-int mdbg_graph_unitigs(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, out, true); }
-int mdbg_graph_unitigs_device(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, out, false); }
+int mdbg_graph_unitigs(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, nullptr, 0, out, nullptr, true); }
+int mdbg_graph_unitigs_device(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, nullptr, 0, out, nullptr, false); }
+int mdbg_graph_simplify(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
+    if (!stats) return MDBG_E_PARAM;
+    return unitigs_impl(c, steps, n_steps, out, stats, true);
+}
+int mdbg_graph_simplify_device(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
+    if (!stats) return MDBG_E_PARAM;
+    return unitigs_impl(c, steps, n_steps, out, stats, false);
+}
 
 // ---- replicated-sketch multi-GPU mode (see include/mdbg_hip.h) ---------------------------------------
 int mdbg_set_partition(mdbg_ctx* c, uint32_t world, uint32_t rank) {

@@ -1,0 +1,225 @@
+// simplify.hip — tip clipping and simple-bubble popping on the unitig graph, on the GPU (gfx950).  Included at the end of unitigs.hip: it reads that stage's
+// arrays (sorted arcs, settled ranking, unitig numbers, lengths, abundance sums) and calls its compaction again under a node mask.
+//
+// The rules are the ones written out in include/mdbg_hip.h (mdbg_graph_simplify): this project's own order-free definition in the spirit of
+// `gfatools asm -t N,L -b L`, NOT gfatools' in-place passes.  A step decides against the graph as it is when the step starts, so every kernel below reads
+// one compaction and only the last one writes the mask.
+//
+// Adjacency comes from the ONE sorted arc array of the compaction (source, target): the out-arcs of x are the run with source x (binary search), and because
+// the arc set is closed under mirroring the in-neighbours of w are the complements of the out-targets of comp(w).  No second sort, no degree atomics.
+//
+//   ends_kernel          kept head -> first and last vertex of its unitig
+//   tip_cand_kernel      small unitig with exactly one dead end -> its attached vertex x (att[unitig], owner[x])
+//   tip_decide_kernel    candidate u is removed iff every target of x has another in-neighbour that is no candidate's attached vertex or a better candidate's
+//   bubble_key_kernel    small unitig with one way in (p) and one way out (q), p / q not on it, q != comp(p) -> key min((p,q), (comp q, comp p)); rocPRIM sorts (key, unitig)
+//   bubble_decide_kernel first entry of every run of equal keys: the best member stays, the others are removed
+//   scatter_kernel       vertices of removed unitigs -> alive[row] = 0; counts the nodes
+//
+// Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks.  A step that
+// removes nothing is followed by no compaction: the next step decides on the same arrays.
+#include "simplify.h"
+
+namespace {
+
+struct SimpArgs {
+    u32 n2x; u64 U, n_arcs; const u64* sk;
+    const u32* P; const u32* prv; const u32* flag; const u32* uid; const u8* cyc;
+    const u64* offsets; const u64* length; const u64* kc; const u8* circ;
+    u32 max_nodes; u64 max_bases;
+    u32* uhead; u32* utail; u32* att; u32* owner; u8* rem; u64* bkey; u32* bval; const u64* skey; const u32* sval; u32* ctr; u8* alive;
+};
+
+__device__ inline u64 arcs_from(const SimpArgs& a, u32 x) {      // first sorted arc whose source is >= x
+    const u64 key = (u64)x << 32;
+    u64 lo = 0, hi = a.n_arcs;
+    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (a.sk[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// number of distinct targets of x, counted up to 2; *only <- the first one
+__device__ inline u32 out_degree2(const SimpArgs& a, u32 x, u32* only) {
+    u32 n = 0; u64 last = 0;
+    for (u64 i = arcs_from(a, x); i < a.n_arcs && (u32)(a.sk[i] >> 32) == x && n < 2; ++i) {
+        const u64 k = a.sk[i];
+        if (n && k == last) continue;
+        if (!n) *only = (u32)k;
+        last = k; ++n;
+    }
+    return n;
+}
+__device__ inline bool is_small(const SimpArgs& a, u64 u) {
+    return !a.circ[u] && (a.max_nodes == 0 || a.offsets[u + 1] - a.offsets[u] <= a.max_nodes) && (a.max_bases == 0 || a.length[u] <= a.max_bases);
+}
+// a ranks above b: mean abundance kc / entries compared exactly (128-bit cross products), then the longer, then the smaller number
+__device__ inline bool beats(const SimpArgs& a, u32 x, u32 y) {
+    const u64 nx = a.offsets[x + 1] - a.offsets[x], ny = a.offsets[y + 1] - a.offsets[y];
+    const u64 lx = a.kc[x] * ny, hx = __umul64hi(a.kc[x], ny), ly = a.kc[y] * nx, hy = __umul64hi(a.kc[y], nx);
+    if (hx != hy) return hx > hy;
+    if (lx != ly) return lx > ly;
+    if (a.length[x] != a.length[y]) return a.length[x] > a.length[y];
+    return x < y;
+}
+__device__ inline u32 unitig_at(const SimpArgs& a, u32 v) {      // the unitig the node of v lies on
+    u32 h = a.P[v] & ~TERM;
+    if (!a.flag[h]) h = a.P[v ^ 1] & ~TERM;
+    return a.uid[h];
+}
+
+__global__ __launch_bounds__(256) void ends_kernel(SimpArgs a) {
+    const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= a.n2x || (a.P[v] & ~TERM) != v || !a.flag[v]) return;
+    const u32 u = a.uid[v];
+    if (u >= a.U) return;
+    a.uhead[u] = v;
+    a.utail[u] = (a.cyc && a.cyc[v]) ? a.prv[v] : ((a.P[v ^ 1] & ~TERM) ^ 1);
+}
+
+__global__ __launch_bounds__(256) void tip_cand_kernel(SimpArgs a) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.U) return;
+    u32 x = NONE;
+    if (is_small(a, u)) {
+        const u32 h = a.uhead[u], t = a.utail[u];
+        u32 dummy;
+        const bool fwd = out_degree2(a, h ^ 1, &dummy) == 0;      // nothing enters the first vertex  (in-arcs of h = out-arcs of comp(h))
+        const bool rev = out_degree2(a, t, &dummy) == 0;          // nothing enters comp(last)
+        if (fwd != rev) x = fwd ? t : (h ^ 1);
+    }
+    a.att[u] = x;
+    if (x != NONE && x < a.n2x) a.owner[x] = (u32)u;              // an attached vertex belongs to one unitig only
+}
+
+__global__ __launch_bounds__(256) void tip_decide_kernel(SimpArgs a) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool gone = false;
+    if (u < a.U) {
+        const u32 x = a.att[u];
+        if (x != NONE) {
+            gone = true;                                          // (x has an out-arc: its other end is the dead one)
+            for (u64 i = arcs_from(a, x); gone && i < a.n_arcs && (u32)(a.sk[i] >> 32) == x; ++i) {
+                const u32 w = (u32)a.sk[i];
+                bool other = false;
+                for (u64 j = arcs_from(a, w ^ 1); !other && j < a.n_arcs && (u32)(a.sk[j] >> 32) == (w ^ 1); ++j) {
+                    const u32 y = (u32)a.sk[j] ^ 1;               // an in-neighbour of w
+                    if (y == x || y >= a.n2x) continue;
+                    const u32 c = a.owner[y];
+                    other = c == NONE || beats(a, c, (u32)u);
+                }
+                gone = other;
+            }
+        }
+        a.rem[u] = gone ? 1 : 0;
+    }
+    count_to(a.ctr, gone);
+}
+
+__global__ __launch_bounds__(256) void bubble_key_kernel(SimpArgs a) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.U) return;
+    u64 key = ~0ull;
+    if (is_small(a, u)) {
+        const u32 h = a.uhead[u], t = a.utail[u];
+        u32 y = 0, q = 0;
+        if (out_degree2(a, h ^ 1, &y) == 1 && out_degree2(a, t, &q) == 1 && y < a.n2x && q < a.n2x) {
+            const u32 p = y ^ 1;
+            if (q != (p ^ 1) && unitig_at(a, p) != u && unitig_at(a, q) != u) {
+                const u64 k1 = ((u64)p << 32) | q, k2 = ((u64)(q ^ 1) << 32) | (p ^ 1);
+                key = k1 < k2 ? k1 : k2;
+            }
+        }
+    }
+    a.bkey[u] = key; a.bval[u] = (u32)u; a.rem[u] = 0;
+}
+
+__global__ __launch_bounds__(256) void bubble_decide_kernel(SimpArgs a) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u32 gone = 0;
+    if (i < a.U) {
+        const u64 key = a.skey[i];
+        if (key != ~0ull && (i == 0 || a.skey[i - 1] != key)) {
+            u32 best = a.sval[i]; u64 j = i + 1;
+            for (; j < a.U && a.skey[j] == key; ++j) { const u32 c = a.sval[j]; if (c < a.U && beats(a, c, best)) best = c; }
+            if (j > i + 1)
+                for (u64 m = i; m < j; ++m) { const u32 c = a.sval[m]; if (c != best && c < a.U) { a.rem[c] = 1; ++gone; } }
+        }
+    }
+    if (gone) atomicAdd(a.ctr, gone);
+}
+
+__global__ __launch_bounds__(256) void scatter_kernel(SimpArgs a) {
+    const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
+    bool gone = false;
+    if (v < a.n2x) {
+        const u32 h = a.P[v] & ~TERM;
+        if (a.flag[h]) { const u32 u = a.uid[h]; gone = u < a.U && a.rem[u]; }
+        if (gone) a.alive[v >> 1] = 0;
+    }
+    count_to(a.ctr + 1, gone);
+}
+
+}  // namespace
+
+int simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
+                     uint64_t* unitigs_removed, uint64_t* nodes_removed, SimplifyInfo* info, hipError_t* herr) {
+    memset(info, 0, sizeof *info);
+    if (n_steps == 0 || nd.n == 0) {                          // the empty schedule IS the unitig call
+        const int rc = build_unitigs(B, nd, ed, s, out, herr);
+        if (rc == 0 && nd.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed.n ? 1 : 0); }
+        return rc;
+    }
+    const u64 n = nd.n;
+    if (n >= (1ull << 30)) return 2;
+    const u32 n2x = (u32)(2 * n);
+    UHIP(B->alive.ensure(n));
+    UHIP(hipMemsetAsync(B->alive.p, 1, n, s));
+    u8* alive = B->alive.as<u8>();
+    u64 n_alive = n;
+    bool stale = true;                                        // the arrays of the last compaction no longer describe the surviving graph
+    auto compact = [&]() -> int {
+        const int rc = build_unitigs_masked(B, nd, ed, alive, n_alive, s, out, herr);
+        if (rc) return rc;
+        ++info->n_compactions; info->n_rounds_total += out->n_rounds; info->n_syncs += out->n_rounds + 3 + (ed.n ? 1 : 0);
+        stale = false;
+        return 0;
+    };
+    for (uint32_t k = 0; k < n_steps; ++k) {
+        unitigs_removed[k] = 0; nodes_removed[k] = 0;
+        if (stale) { const int rc = compact(); if (rc) return rc; }
+        const u64 U = out->n_unitigs;
+        if (U == 0) continue;
+        UHIP(B->uhead.ensure(n * 4)); UHIP(B->utail.ensure(n * 4)); UHIP(B->att.ensure(n * 4)); UHIP(B->rem.ensure(n)); UHIP(B->owner.ensure((size_t)n2x * 4));
+        u32* d_ctr = B->ctr.as<u32>();                        // (the compaction is over: its round counters are free)
+        UHIP(hipMemsetAsync(d_ctr, 0, 8, s));
+        SimpArgs a; memset(&a, 0, sizeof a);
+        a.n2x = n2x; a.U = U; a.n_arcs = B->n_arcs; a.sk = B->skeys.as<u64>(); a.P = B->Pfin; a.prv = B->prv.as<u32>(); a.flag = B->flag.as<u32>(); a.uid = B->uid.as<u32>(); a.cyc = B->cycfin;
+        a.offsets = out->offsets; a.length = out->length; a.kc = out->kc_sum; a.circ = out->circular; a.max_nodes = steps[k].max_nodes; a.max_bases = steps[k].max_bases;
+        a.uhead = B->uhead.as<u32>(); a.utail = B->utail.as<u32>(); a.att = B->att.as<u32>(); a.owner = B->owner.as<u32>(); a.rem = B->rem.as<u8>(); a.ctr = d_ctr; a.alive = alive;
+        const unsigned gu = grid_for(U), gv = grid_for(n2x);
+        hipLaunchKernelGGL(ends_kernel, dim3(gv), dim3(256), 0, s, a);
+        if (steps[k].kind == MDBG_SIMPLIFY_TIPS) {
+            UHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
+            hipLaunchKernelGGL(tip_cand_kernel, dim3(gu), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(tip_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+        } else {
+            UHIP(B->bkey.ensure(n * 8)); UHIP(B->bkey2.ensure(n * 8)); UHIP(B->bval.ensure(n * 4)); UHIP(B->bval2.ensure(n * 4));
+            a.bkey = B->bkey.as<u64>(); a.bval = B->bval.as<u32>(); a.skey = B->bkey2.as<u64>(); a.sval = B->bval2.as<u32>();
+            hipLaunchKernelGGL(bubble_key_kernel, dim3(gu), dim3(256), 0, s, a);
+            size_t tb = 0;
+            UHIP(rocprim::radix_sort_pairs(nullptr, tb, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
+            UHIP(B->tmp.ensure(tb + 256));
+            UHIP(rocprim::radix_sort_pairs(B->tmp.p, tb, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
+            hipLaunchKernelGGL(bubble_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+        }
+        hipLaunchKernelGGL(scatter_kernel, dim3(gv), dim3(256), 0, s, a);
+        u32 got[2];
+        UHIP(hipMemcpyAsync(got, d_ctr, 8, hipMemcpyDeviceToHost, s));
+        UHIP(hipStreamSynchronize(s));
+        ++info->n_syncs;
+        if (got[1] > n_alive || got[0] > U || (got[0] == 0) != (got[1] == 0)) return 2;
+        unitigs_removed[k] = got[0]; nodes_removed[k] = got[1];
+        n_alive -= got[1];
+        stale = got[1] != 0;
+    }
+    if (stale) { const int rc = compact(); if (rc) return rc; }
+    UHIP(hipGetLastError());
+    return 0;
+}

@@ -1,8 +1,8 @@
 // unitigs.hip — unitig compaction of the k-min-mer graph and the base-space copy plan, on the GPU (gfx950).
 //
 // Replaces the two tools every documented rust-mdbg run pipes its .gfa through: `gfatools asm -u` (compaction of non-branching paths) and
-// the part of src/to_basespace.rs that decides which piece of which node sequence goes where in a unitig (:132-153, 203-262).  No tip or
-// bubble removal.  Input: the node table of the last finalize and the edge list of the last edge call, both resident on the device.
+// the part of src/to_basespace.rs that decides which piece of which node sequence goes where in a unitig (:132-153, 203-262).  Tip and
+// bubble removal is simplify.hip (included at the end: it decides on this stage's arrays and compacts again under a node mask).  Input: the node table of the last finalize and the edge list of the last edge call, both resident on the device.
 //
 // Vertex v = 2 * row + (orientation == '-'), comp(v) = v ^ 1; rows are positions in the index-sorted node table, so vertex order is
 // (index, orientation) order.  The arc set is the set of DISTINCT (n1,o1)->(n2,o2) of the edge records plus their mirrors
@@ -57,10 +57,14 @@ __device__ inline u32 row_of(const u32* __restrict__ index, u32 n, u32 idx) {
 }
 
 __global__ __launch_bounds__(256) void arc_kernel(u64 n_edges, const u32* __restrict__ n1, const u8* __restrict__ o1, const u32* __restrict__ n2, const u8* __restrict__ o2,
-                                                  const u32* __restrict__ index, u32 n, u32* __restrict__ eu, u32* __restrict__ ev, u64* __restrict__ keys, u32* __restrict__ ctr) {
+                                                  const u32* __restrict__ index, u32 n, const u8* __restrict__ alive, u32* __restrict__ eu, u32* __restrict__ ev, u64* __restrict__ keys,
+                                                  u32* __restrict__ ctr) {
     const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_edges) return;
     const u32 ra = row_of(index, n, n1[e]), rb = row_of(index, n, n2[e]);
+    if (alive && ra != NONE && rb != NONE && !(alive[ra] && alive[rb])) {      // an end was removed (simplify.hip): no vertices, and both arcs sort behind every vertex (source 2n)
+        eu[e] = NONE; ev[e] = NONE; keys[2 * e] = (u64)(2 * n) << 32; keys[2 * e + 1] = (u64)(2 * n) << 32; return;
+    }
     if (ra == NONE || rb == NONE) { ctr[C_ERR] = 1; eu[e] = 0; ev[e] = 0; keys[2 * e] = 0; keys[2 * e + 1] = 0; return; }      // an edge of another table: reported by the host
     const u32 u = 2 * ra + (o1[e] == '-' ? 1u : 0u), v = 2 * rb + (o2[e] == '-' ? 1u : 0u);
     eu[e] = u; ev[e] = v;
@@ -69,11 +73,12 @@ __global__ __launch_bounds__(256) void arc_kernel(u64 n_edges, const u32* __rest
 }
 
 // sorted arcs: the first arc of a source group writes the group's only target, if it has only one
-__global__ __launch_bounds__(256) void succ_kernel(u64 n_arcs, const u64* __restrict__ sk, u32* __restrict__ succ) {
+__global__ __launch_bounds__(256) void succ_kernel(u64 n_arcs, u32 n2x, const u64* __restrict__ sk, u32* __restrict__ succ) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_arcs) return;
     const u64 key = sk[i];
     const u32 src = (u32)(key >> 32);
+    if (src >= n2x) return;                               // arcs of removed nodes
     if (i > 0 && (u32)(sk[i - 1] >> 32) == src) return;
     u64 lo = i + 1, hi = n_arcs;                          // first arc > key (duplicates of key are skipped)
     while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (sk[mid] <= key) lo = mid + 1; else hi = mid; }
@@ -131,11 +136,11 @@ __global__ __launch_bounds__(256) void cut_kernel(u32 n2x, const u32* __restrict
 
 // heads: is this chain the unitig or is its mirror?  linear: the first node has the smaller index (one node: '+'); circular: the smallest vertex is a '+'
 __global__ __launch_bounds__(256) void head_kernel(u32 n2x, const u32* __restrict__ P, const u32* __restrict__ D, const u32* __restrict__ prv, const u8* __restrict__ cyc,
-                                                   u32* __restrict__ flag, u32* __restrict__ hlen) {
+                                                   const u8* __restrict__ alive, u32* __restrict__ flag, u32* __restrict__ hlen) {
     const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n2x) return;
     u32 keep = 0, len = 0;
-    if ((P[v] & ~TERM) == v) {
+    if ((P[v] & ~TERM) == v && (!alive || alive[v >> 1])) {      // (a removed node has no arcs: its vertices are heads of nothing)
         u32 t;                                            // the chain's last vertex
         if (cyc && cyc[v]) { t = prv[v]; keep = (v & 1) ? 0u : 1u; }
         else { t = (P[v ^ 1] & ~TERM) ^ 1; keep = ((v >> 1) < (t >> 1) || (v == t && !(v & 1))) ? 1u : 0u; }      // comp(v) ends the mirror chain, whose head is comp(t)
@@ -200,6 +205,7 @@ __global__ __launch_bounds__(256) void uedge_kernel(UedgeArgs a) {
     const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.n_edges) return;
     const u32 u = a.eu[e], v = a.ev[e];
+    if (u == NONE) { if (!WRITE) a.keep[e] = 0; return; }      // a record of a removed node
     // interior link: a link that is not the closing link of a circular unitig (its target is the kept head) nor that link's mirror (its source is the head's complement);
     // a path has no link into its head, and the mirror cycle's own cut lies elsewhere, so only kept heads count
     if (!WRITE) { a.keep[e] = (a.nxt[u] == v && !a.flag[v] && !a.flag[u ^ 1]) ? 0u : 1u; return; }
@@ -221,6 +227,9 @@ struct UnitigBuffers {
     Buf keys, skeys, eu, ev, succ, nxt, prv, P[2], D[2], M[2], cyc, flag, hlen, uid, hoff, ctr, tmp;
     Buf offsets, node, ori, src_read, src_begin, len, rc, dst, ent_u, pl64, ab64, gs, ga, length, kc, circ;
     Buf ekeep, epos, un1, un2, uov, uo1, uo2;
+    // what the last build_unitigs left for simplify.hip: the settled ranking (one of P[] / D[]), the cycle marks (or null) and the number of sorted arcs in skeys
+    const u32* Pfin = nullptr; const u32* Dfin = nullptr; const u8* cycfin = nullptr; u64 n_arcs = 0;
+    Buf alive, uhead, utail, att, owner, rem, bkey, bkey2, bval, bval2;      // simplify.hip
 };
 UnitigBuffers* unitig_buffers_create() { return new UnitigBuffers(); }
 void unitig_buffers_destroy(UnitigBuffers* b) { delete b; }
@@ -237,11 +246,12 @@ static hipError_t excl_scan(UnitigBuffers* B, const In* in, Out* out, size_t n, 
     return rocprim::exclusive_scan(B->tmp.p, tb, in, out, (Out)0, n, rocprim::plus<Out>(), s);
 }
 
-int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, hipError_t* herr) {
+// alive (device, one byte per row of the node table; null = every node) restricts the graph to the surviving nodes and the arcs between them; n_alive = how many
+static int build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, hipError_t* herr) {
     memset(out, 0, sizeof *out);
     *herr = hipSuccess;
     const u64 n = nd.n, E = ed.n;
-    if (n == 0) return 0;
+    if (n == 0 || (alive && n_alive == 0)) return 0;
     if (n >= (1ull << 30) || E >= (1ull << 31)) return 2;
     const u32 n2x = (u32)(2 * n);
     const unsigned gv = grid_for(n2x);
@@ -255,13 +265,13 @@ int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed,
     UHIP(B->eu.ensure(E * 4 + 4)); UHIP(B->ev.ensure(E * 4 + 4));
     if (E) {
         UHIP(B->keys.ensure(2 * E * 8)); UHIP(B->skeys.ensure(2 * E * 8));
-        hipLaunchKernelGGL(arc_kernel, dim3(grid_for(E)), dim3(256), 0, s, E, ed.n1, ed.o1, ed.n2, ed.o2, nd.index, (u32)n, B->eu.as<u32>(), B->ev.as<u32>(), B->keys.as<u64>(), d_ctr);
-        unsigned end_bit = 33; while (end_bit < 64 && (1ull << (end_bit - 32)) < n2x) ++end_bit;
+        hipLaunchKernelGGL(arc_kernel, dim3(grid_for(E)), dim3(256), 0, s, E, ed.n1, ed.o1, ed.n2, ed.o2, nd.index, (u32)n, alive, B->eu.as<u32>(), B->ev.as<u32>(), B->keys.as<u64>(), d_ctr);
+        unsigned end_bit = 33; while (end_bit < 64 && (1ull << (end_bit - 32)) < (u64)n2x + (alive ? 1 : 0)) ++end_bit;      // (masked: the source 2n occurs)
         size_t tb = 0;
         UHIP(rocprim::radix_sort_keys(nullptr, tb, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
         UHIP(B->tmp.ensure(tb + 256));
         UHIP(rocprim::radix_sort_keys(B->tmp.p, tb, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
-        hipLaunchKernelGGL(succ_kernel, dim3(grid_for(2 * E)), dim3(256), 0, s, 2 * E, B->skeys.as<u64>(), B->succ.as<u32>());
+        hipLaunchKernelGGL(succ_kernel, dim3(grid_for(2 * E)), dim3(256), 0, s, 2 * E, n2x, B->skeys.as<u64>(), B->succ.as<u32>());
     }
     // ---- links, start state of the ranking
     UHIP(B->nxt.ensure((size_t)n2x * 4)); UHIP(B->prv.ensure((size_t)n2x * 4));
@@ -307,7 +317,7 @@ int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed,
     const u8* cyc = cycles ? B->cyc.as<u8>() : nullptr;
     // ---- kept heads -> unitig numbers (vertex order = order of the first node's index) and entry offsets
     UHIP(B->flag.ensure((size_t)n2x * 4)); UHIP(B->hlen.ensure((size_t)n2x * 4)); UHIP(B->uid.ensure((size_t)n2x * 4)); UHIP(B->hoff.ensure((size_t)n2x * 4));
-    hipLaunchKernelGGL(head_kernel, dim3(gv), dim3(256), 0, s, n2x, P, D, B->prv.as<u32>(), cyc, B->flag.as<u32>(), B->hlen.as<u32>());
+    hipLaunchKernelGGL(head_kernel, dim3(gv), dim3(256), 0, s, n2x, P, D, B->prv.as<u32>(), cyc, alive, B->flag.as<u32>(), B->hlen.as<u32>());
     UHIP(excl_scan(B, B->flag.as<u32>(), B->uid.as<u32>(), n2x, s));
     UHIP(excl_scan(B, B->hlen.as<u32>(), B->hoff.as<u32>(), n2x, s));
     u32 last[4];
@@ -317,7 +327,7 @@ int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed,
     UHIP(hipMemcpyAsync(&last[3], B->hoff.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
     UHIP(hipStreamSynchronize(s));
     const u64 U = (u64)last[0] + last[1], n_entries = (u64)last[2] + last[3];
-    if (n_entries != n || U == 0 || U > n) return 2;       // every node lies on exactly one unitig
+    if (n_entries != (alive ? n_alive : n) || U == 0 || U > n_entries) return 2;       // every (surviving) node lies on exactly one unitig
     // ---- walks and copy plan
     UHIP(B->offsets.ensure((U + 1) * 8)); UHIP(B->circ.ensure(U)); UHIP(B->length.ensure(U * 8)); UHIP(B->kc.ensure(U * 8));
     UHIP(B->node.ensure(n * 4)); UHIP(B->ori.ensure(n)); UHIP(B->src_read.ensure(n * 8)); UHIP(B->src_begin.ensure(n * 8)); UHIP(B->len.ensure(n * 4)); UHIP(B->rc.ensure(n));
@@ -327,8 +337,8 @@ int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed,
     ea.offsets = B->offsets.as<u64>(); ea.circular = B->circ.as<u8>(); ea.node = B->node.as<u32>(); ea.ori = B->ori.as<u8>(); ea.src_read = B->src_read.as<u64>();
     ea.src_begin = B->src_begin.as<u64>(); ea.len = B->len.as<u32>(); ea.rc = B->rc.as<u8>(); ea.ent_u = B->ent_u.as<u32>(); ea.pl64 = B->pl64.as<u64>(); ea.ab64 = B->ab64.as<u64>();
     hipLaunchKernelGGL(emit_kernel, dim3(gv), dim3(256), 0, s, ea);
-    UHIP(excl_scan(B, B->pl64.as<u64>(), B->gs.as<u64>(), (size_t)(n + 1), s));
-    UHIP(excl_scan(B, B->ab64.as<u64>(), B->ga.as<u64>(), (size_t)(n + 1), s));
+    UHIP(excl_scan(B, B->pl64.as<u64>(), B->gs.as<u64>(), (size_t)(n_entries + 1), s));
+    UHIP(excl_scan(B, B->ab64.as<u64>(), B->ga.as<u64>(), (size_t)(n_entries + 1), s));
     hipLaunchKernelGGL(finish_kernel, dim3(grid_for(n)), dim3(256), 0, s, n_entries, U, B->offsets.as<u64>(), B->ent_u.as<u32>(), B->gs.as<u64>(), B->ga.as<u64>(), B->dst.as<u64>(),
                        B->length.as<u64>(), B->kc.as<u64>());
     // ---- unitig edges: every edge record that is not an interior link, in source order
@@ -351,9 +361,16 @@ int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed,
     }
     UHIP(hipStreamSynchronize(s));
     UHIP(hipGetLastError());
+    B->Pfin = P; B->Dfin = D; B->cycfin = cyc; B->n_arcs = 2 * E;
     out->n_unitigs = U; out->n_entries = n_entries; out->offsets = B->offsets.as<u64>(); out->node = B->node.as<u32>(); out->ori = B->ori.as<u8>();
     out->src_read = B->src_read.as<u64>(); out->src_begin = B->src_begin.as<u64>(); out->len = B->len.as<u32>(); out->revcomp = B->rc.as<u8>(); out->dst_offset = B->dst.as<u64>();
     out->length = B->length.as<u64>(); out->kc_sum = B->kc.as<u64>(); out->circular = B->circ.as<u8>(); out->n_rounds = rounds;
     out->edges.n = UE; out->edges.n1 = B->un1.as<u32>(); out->edges.o1 = B->uo1.as<u8>(); out->edges.n2 = B->un2.as<u32>(); out->edges.o2 = B->uo2.as<u8>(); out->edges.overlap = B->uov.as<u32>();
     return 0;
 }
+
+int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, hipError_t* herr) {
+    return build_unitigs_masked(B, nd, ed, nullptr, 0, s, out, herr);
+}
+
+#include "simplify.hip"

@@ -7,7 +7,7 @@ import queue
 import threading
 import time
 
-from .api import Mdbg
+from .api import MAGIC_SIMPLIFY_STEPS, Mdbg
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 
@@ -21,11 +21,13 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False):
+             threads=1, packed=None, contigs=False, simplify=None):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
     to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
+    simplify (with contigs): a schedule of tip / bubble steps, e.g. api.MAGIC_SIMPLIFY_STEPS — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
+    Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
     threads: host threads of the reader (uncompressed input: mdbg_reader_open_mt) and of the 2-bit packer; packed: hand the GPU 2-bit
     packed batches (a quarter of the bytes over PCIe), default: when threads > 1"""
     if packed is None:
@@ -123,7 +125,11 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             em = Emitter()
             em.write_gfa(prefix + ".gfa", nodes, raw)
             tm["gfa"] = time.perf_counter() - t0
-            ctg = None
+            ctg = sctg = sstats = None
+            if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
+                sl, sstats = m.graph_simplify(simplify, raw=True)
+                sctg = Contigs(sl)
+                tm["simplify"] = time.perf_counter() - t0
             if contigs:                                  # the plan is copied out of the context here; the bases follow in the second pass
                 ctg = Contigs(m.graph_unitigs(raw=True), nodes["n_nodes"])
                 tm["unitigs"] = time.perf_counter() - t0
@@ -139,6 +145,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 for bases, offs in r.batches(batch_bases, copy=False):      # consumed before the next batch is asked for
                     if ctg is not None:
                         ctg.add_batch(bases, offs, first)
+                    if sctg is not None:
+                        sctg.add_batch(bases, offs, first)
                     yield bases, offs, first
                     first += len(offs) - 1
         t1 = time.perf_counter()
@@ -156,6 +164,12 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             ctg.write_gfa(prefix + ".unitigs.gfa")
             ctg.write_fasta(prefix + ".unitigs.fa")
             extra["n_unitigs"] = len(ctg)
+    if sctg is not None:
+        with sctg:
+            sctg.write_gfa(prefix + ".msimpl.gfa")
+            sctg.write_fasta(prefix + ".msimpl.fa")
+            extra["n_simplified"] = len(sctg)
+            extra["simplify"] = sstats
     return dict(extra, n_reads=n_reads, n_bases=n_bases, n_minimizers=stats["n_minimizers"], n_windows=stats["n_windows"],
                 n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=len(edges["n1"]),
                 presimp_removed=edges["presimp_removed"], seconds_until={k_: round(v, 4) for k_, v in tm.items()})
@@ -185,7 +199,9 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     and put IN FRONT of the reads for the next k: the reads keep their resident sketches and their ordinals (READ_ORDINAL_BASE + i),
     the contigs get the ordinals 0 .. 2C-1, and the previous round's contigs are forgotten (mdbg_rewind).
     contigs_fn="unitigs": the built-in producer — the round's unitigs (Mdbg.graph_unitigs: `gfatools asm -u` + to_basespace, WITHOUT magic_simplify's tip and
-    bubble rounds), stitched from the previous round's contigs and one more pass over the reads per round."""
+    bubble rounds), stitched from the previous round's contigs and one more pass over the reads per round.
+    contigs_fn="simplified": the same with the tip and bubble rounds — the contigs left after Mdbg.graph_simplify(api.MAGIC_SIMPLIFY_STEPS): the schedule of
+    magic_simplify's first gfatools line under this project's own rules (include/mdbg_hip.h), not gfatools parity."""
     ks = list(ks)
     out = {}
     n_reads = n_bases = 0
@@ -216,7 +232,7 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
             out[k] = dict(n_reads=n_reads, n_bases=n_bases, n_contigs=len(contigs), n_minimizers=st["n_minimizers"], n_windows=st["n_windows"],
                           n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=int(raw.n),
                           presimp_removed=int(raw.presimp_removed))
-            if contigs_fn == "unitigs":
+            if contigs_fn in ("unitigs", "simplified"):
                 def fed():                               # what this round ingested, with its ordinals: the contigs in front, then the reads
                     if contigs:
                         yield concat_records(contigs + contigs) + (0,)
@@ -225,7 +241,8 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
                         for bases, offs in r2.batches(batch_bases, copy=False):
                             yield bases, offs, first
                             first += len(offs) - 1
-                with em.contigs(m.graph_unitigs(raw=True), fed(), n_nodes=nodes["n_nodes"]) as ctg:
+                plan, n_nodes = (m.graph_unitigs(raw=True), nodes["n_nodes"]) if contigs_fn == "unitigs" else (m.graph_simplify(MAGIC_SIMPLIFY_STEPS, raw=True)[0], None)
+                with em.contigs(plan, fed(), n_nodes=n_nodes) as ctg:
                     contigs = [c for c in ctg.sequences() if len(c) >= min_contig_len]
             elif contigs_fn is not None:
                 contigs = [bytes(c) for c in contigs_fn(k, gfa, nodes) if len(c) >= min_contig_len]
