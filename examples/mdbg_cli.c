@@ -2,6 +2,8 @@
  *   reads.fa[.gz]  ->  mdbg_reader_*  ->  mdbg_ingest_batch[_packed]  ->  mdbg_finalize  ->  mdbg_graph_edges  ->  <prefix>.gfa (+ <prefix>.0.sequences)
  *   --contigs:  ... ->  mdbg_graph_unitigs  ->  mdbg_emit_contigs_*  ->  <prefix>.unitigs.gfa + <prefix>.unitigs.fa   (what the reference's users get from
  *   `gfatools asm -u` + to_basespace + gfa2fasta.sh; no tip or bubble removal)
+ *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
+ *   sequences there; the same files, and with --no-basespace the input is read once
  * Same flags as the reference binary for this path (src/main.rs:330-420): -k -l --density --minabund --presimp --prefix --threads
  * --reference --skiphpc --syncmers/-s --lmer-counts/--lmer_counts_min/--lmer_counts_max --no-basespace; --contigs is this host's own.
  * --threads N > 1: an uncompressed input is mapped and parsed by N threads (mdbg_reader_open_mt) that also pack their pieces to 2 bits
@@ -71,7 +73,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L append steps of their own, in command-line order */
@@ -95,6 +97,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--lmer_counts_max") && i + 1 < argc) lc_max = (uint32_t)strtoul(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "--timing")) timing = 1;
         else if (!strcmp(argv[i], "--contigs")) contigs = 1;
+        else if (!strcmp(argv[i], "--keep-reads")) keep_reads = 1;
         else if (!strcmp(argv[i], "--simplify")) {
             simplify = 1;
             for (uint32_t j = 0; j < sizeof magic / sizeof magic[0] && n_steps < MAX_STEPS; ++j) steps[n_steps++] = magic[j];
@@ -114,9 +117,11 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--keep-reads] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
     if (simplify) contigs = 1;
+    if (!contigs) keep_reads = 0;
+    if (keep_reads) p.flags |= MDBG_FLAG_KEEP_READS;
 
     int err = 0;
     mdbg_ctx* ctx = mdbg_create(&p, &err);
@@ -199,6 +204,13 @@ int main(int argc, char** argv) {
                (unsigned long long)sl.n_unitigs);
         sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
         if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
+        if (keep_reads) {                                           /* the sequences from the device store instead of the second pass */
+            mdbg_contig_seqs cs;
+            rc = mdbg_graph_contigs(ctx, 0, &cs);
+            if (rc) die(ctx, "mdbg_graph_contigs", rc);
+            rc = mdbg_emit_contigs_set_sequences(sctg, cs.bases, cs.offsets, cs.n_contigs);
+            if (rc) die(NULL, "mdbg_emit_contigs_set_sequences", rc);
+        }
     }
     if (contigs) {                                                  /* unitigs + copy plan from the GPU; the handle keeps its own copy of the plan */
         mdbg_unitig_list ul;
@@ -207,8 +219,15 @@ int main(int argc, char** argv) {
         printf("Number of unitigs: %llu\n", (unsigned long long)ul.n_unitigs);
         ctg = mdbg_emit_contigs_open(&ul, &nodes, &err);
         if (!ctg) die(NULL, "mdbg_emit_contigs_open", err);
+        if (keep_reads) {
+            mdbg_contig_seqs cs;
+            rc = mdbg_graph_contigs(ctx, 0, &cs);
+            if (rc) die(ctx, "mdbg_graph_contigs", rc);
+            rc = mdbg_emit_contigs_set_sequences(ctg, cs.bases, cs.offsets, cs.n_contigs);
+            if (rc) die(NULL, "mdbg_emit_contigs_set_sequences", rc);
+        }
     }
-    if (write_sequences || ctg) {                                   /* second pass over the input: the node sequences, the contigs' bases */
+    if (write_sequences || (ctg && !keep_reads)) {                                   /* second pass over the input: the node sequences, the contigs' bases */
         /* one file per writer thread, "<prefix>.<t>.sequences", as the reference's worker threads write them (main.rs:614-630) */
         enum { MAX_WRITERS = 16 };
         const int nw = !write_sequences ? 0 : threads > MAX_WRITERS ? MAX_WRITERS : threads;
@@ -227,8 +246,8 @@ int main(int argc, char** argv) {
             rc = mdbg_reader_next(rd, 256u << 20, &bases, &offs, &n);
             if (rc) die(NULL, "mdbg_reader_next", rc);
             if (!n) break;
-            if (ctg) { rc = mdbg_emit_contigs_add_batch(ctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
-            if (sctg) { rc = mdbg_emit_contigs_add_batch(sctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
+            if (ctg && !keep_reads) { rc = mdbg_emit_contigs_add_batch(ctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
+            if (sctg && !keep_reads) { rc = mdbg_emit_contigs_add_batch(sctg, bases, offs, n, first); if (rc) die(NULL, "mdbg_emit_contigs_add_batch", rc); }
             for (int t = 0; t < nw; ++t) {
                 seqjob_t jb; jb.sf = sf[t]; jb.nodes = &nodes; jb.part = (uint32_t)t; jb.n_parts = (uint32_t)nw; jb.bases = bases; jb.offs = offs; jb.n = n; jb.first = first; jb.rc = 0;
                 job[t] = jb;

@@ -116,6 +116,9 @@ void mdbg_lmer_filter_free(uint64_t* codes);
  *   mdbg_emit_contigs_add_batch   executes the plan entries whose src_read lies in the batch.  Feed every batch that was ingested, with
  *                                 the same buffers / ordinals (as mdbg_seqfile_write_batch), in any order, cut anywhere; feeding a
  *                                 batch twice is harmless.  Reverse complement as src/utils.rs:3-24: a byte outside ACGTU acgtu gives N.
+ *   mdbg_emit_contigs_set_sequences  instead of add_batch calls: takes every unitig's sequence from a min_len = 0 result of mdbg_graph_contigs (mdbg_hip.h:
+ *                                 bases, offsets[n_unitigs + 1], HOST arrays).  MDBG_E_PARAM unless n_unitigs and every offsets[i + 1] - offsets[i]
+ *                                 equal the list's own count and length[]; afterwards every plan entry counts as filled.
  *   mdbg_emit_contigs_write_gfa   "H\tVN:Z:1.0", "S\t<name>\t<seq>\tLN:i:<len>\tmc:f:<kc_sum / nodes, one decimal>",
  *                                 "L\t<name>\t<+/->\t<name>\t<+/->\t<overlap>M"; names utg%07d + l / c.
  *   mdbg_emit_contigs_write_fasta ">name" and the sequence on one line, for the unitigs of at least min_len bases.
@@ -124,6 +127,7 @@ void mdbg_lmer_filter_free(uint64_t* codes);
 typedef struct mdbg_contigs mdbg_contigs;
 mdbg_contigs* mdbg_emit_contigs_open(const mdbg_unitig_list* unitigs, const mdbg_nodes* nodes, int* err);
 int mdbg_emit_contigs_add_batch(mdbg_contigs* h, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t first_read_ordinal);
+int mdbg_emit_contigs_set_sequences(mdbg_contigs* h, const uint8_t* bases, const uint64_t* offsets, uint64_t n_unitigs);
 int mdbg_emit_contigs_write_gfa(mdbg_contigs* h, const char* path);
 int mdbg_emit_contigs_write_fasta(mdbg_contigs* h, const char* path, uint64_t min_len);
 uint64_t mdbg_emit_contigs_count(const mdbg_contigs* h);

@@ -58,6 +58,7 @@ enum {
 #define MDBG_MAX_L 255u        /* l = 2..32 run on the bit-sliced kernel, longer l-mers on its generic exact walker (reference: unbounded) */
 #define MDBG_MAX_MINABUND 65535u /* DbgAbundance is a u16 in the reference; up to 8 the table tracks the A-th sighting directly, above it is recovered at finalize */
 #define MDBG_FLAG_FORCE_GENERIC 1u /* every tile takes the generic exact sketch kernel (testing / cross-check) */
+#define MDBG_FLAG_KEEP_READS 2u  /* the context keeps every batch it ingests WITH bases, packed 2 bits per base, in device memory: mdbg_graph_contigs stitches from that store */
 #define MDBG_SCHEME_DENSITY 0u   /* canonical ntHash <= density * 2^64           Read::extract_density   src/read.rs:176-211 */
 #define MDBG_SCHEME_SYNCMERS 1u  /* --syncmers: open syncmers (smallest s-mer in the middle), down-sampled by hash(l-mer) <= density * 4^l;
                                   * 2-bit codes, A/a C/c G/g T/t/U/u, any other byte resets (no alphabet error); l <= 31
@@ -341,7 +342,7 @@ int mdbg_graph_edges_device(mdbg_ctx* ctx, float presimp, mdbg_edge_list* out);
  *   len inside the unitig and length[] (the LN tag) its total; kc_sum[] the sum of the nodes' abundances (the writer prints
  *   mc:f = kc_sum / entries, to_basespace.rs:265-288); circular[] 0 / 1.  mdbg_emit_contigs_* (mdbg_emit.h) executes the plan.
  * mdbg_graph_unitigs: HOST arrays; mdbg_graph_unitigs_device: DEVICE arrays; owned by the context until its next unitig, simplify, edge,
- * finalize or reset call.  n_rounds: pointer-jumping rounds the call ran (at most ceil(log2(2 n)) + 1 to rank the paths, as many
+ * finalize or reset call (mdbg_graph_contigs reads the device arrays of the last call whichever variant was used).  n_rounds: pointer-jumping rounds the call ran (at most ceil(log2(2 n)) + 1 to rank the paths, as many
  * again where there are cycles; a ranking that does not settle inside the bound is reported as MDBG_E_DEVICE, never looped on). */
 typedef struct mdbg_unitig_list {
     uint64_t n_unitigs, n_entries;
@@ -398,6 +399,40 @@ typedef struct mdbg_simplify_stats {
 } mdbg_simplify_stats;
 int mdbg_graph_simplify(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
 int mdbg_graph_simplify_device(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
+
+/* ---- contigs stitched on the GPU from reads kept packed in device memory -----------------------------------------------------
+ * A context created with MDBG_FLAG_KEEP_READS in mdbg_params.flags keeps, for every batch that goes through an entry point WITH bases (mdbg_ingest_batch, _device,
+ * _packed, _packed_device, mdbg_sketch_device, mdbg_sketch_packed_device), a device copy in the layout of mdbg_packed_batch: the two 32-bit planes per 32 bases,
+ * the read offsets and the exception side-list (position, original byte), so the copy is lossless.  ASCII batches are packed on the device (the kernel behind
+ * mdbg_pack_device; the side-list is sorted on the device too), packed batches are copied device to device.  The store lives as the sketch store does:
+ * mdbg_reset(ctx, 0) drops everything, mdbg_reset(ctx, k != 0) keeps everything, mdbg_rewind(mark) drops exactly the batches ingested after the mark.
+ * Batches without bases (mdbg_ingest_sketch, mdbg_sketch_commit*, routed records) cannot be kept; they stay legal, and mdbg_graph_contigs then answers
+ * MDBG_E_STATE.  SINGLE GPU ONLY, like the unitig stage.  Without the flag the ingest path is what it was: no allocation, no launch, no branch in a kernel.
+ * mdbg_kept_reads: what the store holds now; *bytes = the bytes of its arrays: per batch 8 * ceil(bases / 32) + 8 * (reads + 1) + 9 * exceptions, i.e.
+ * bases / 4 + 8 per read + 9 per exception up to the rounding of each batch (the device blocks that hold them may be larger: the library's block cache hands out
+ * blocks of up to twice the size asked for).  Any of the three pointers may be NULL.
+ *
+ * mdbg_graph_contigs executes the copy plan of the context's CURRENT unitig list — the device arrays left by the last mdbg_graph_unitigs* / mdbg_graph_simplify*
+ * call; a later edge, finalize, ingest, rewind or reset call ends it — against the kept reads, byte for byte as mdbg_emit_contigs_add_batch (mdbg_emit.h) does
+ * on the host: revcomp 0 copies, 1 reverse-complements through utils::revcomp's byte map (N and every byte outside ACGTUacgtu become N), 2 maps every byte through
+ * that map twice in read order.  Only unitigs with length >= min_len are produced, in list order (`seqtk seq -L`); unitig[i] = the 0-based number of contig i in
+ * the unitig list.  With min_len = 0 every unitig is produced and offsets[] is the running sum of length[].
+ * MDBG_E_STATE: no current list, a context without the flag, a routed / partitioned context, or a plan entry whose read is not kept; MDBG_E_PARAM: a plan entry
+ * outside its read (reported through a flag the kernel sets; nothing is read out of bounds).
+ * mdbg_graph_contigs: HOST arrays; mdbg_graph_contigs_device: DEVICE arrays (bases 16-byte aligned).  Both belong to the context until its NEXT CONTIG CALL or
+ * mdbg_destroy, and to nothing else: they survive mdbg_rewind, mdbg_reset and ingest calls, so a round's contigs can be ingested (mdbg_ingest_batch_device with
+ * bases / offsets / n_contigs / n_bases) as the next round's input without leaving the device.
+ * mdbg_contigs_ms: device time of the stitch kernel of the last contig call (HIP events; 0 if it produced no bases). */
+typedef struct mdbg_contig_seqs {
+    uint64_t n_contigs, n_bases;
+    const uint8_t*  bases;     /* n_bases ASCII bytes, contig after contig */
+    const uint64_t* offsets;   /* n_contigs + 1 */
+    const uint64_t* unitig;    /* n_contigs: 0-based number of the contig in the unitig list it was built from */
+} mdbg_contig_seqs;
+int mdbg_graph_contigs(mdbg_ctx* ctx, uint64_t min_len, mdbg_contig_seqs* out);
+int mdbg_graph_contigs_device(mdbg_ctx* ctx, uint64_t min_len, mdbg_contig_seqs* out);
+int mdbg_kept_reads(mdbg_ctx* ctx, uint64_t* n_reads, uint64_t* n_bases, uint64_t* bytes);
+int mdbg_contigs_ms(mdbg_ctx* ctx, double* ms);
 
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),

@@ -14,6 +14,7 @@ _LIB = None
 
 MDBG_OK, MDBG_E_PARAM, MDBG_E_ALPHABET, MDBG_E_CAPACITY, MDBG_E_DEVICE, MDBG_E_NOMEM, MDBG_E_STATE, MDBG_E_IO = 0, -1, -2, -3, -4, -5, -6, -7
 FLAG_FORCE_GENERIC = 1   # mdbg_params.flags bit 0: every tile takes the generic exact kernel (testing)
+FLAG_KEEP_READS = 2      # mdbg_params.flags bit 1: the context keeps the reads it ingests, packed, on the device (Mdbg.graph_contigs)
 
 
 class MdbgError(RuntimeError):
@@ -84,6 +85,11 @@ def unitig_counts(u):
     return dict(offsets=nu + 1 if nu else 0, node=ne, ori=ne, src_read=ne, src_begin=ne, len=ne, revcomp=ne, dst_offset=ne, length=nu, kc_sum=nu, circular=nu)
 
 
+class ContigSeqs(C.Structure):         # mdbg_contig_seqs
+    _fields_ = [("n_contigs", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64)),
+                ("unitig", C.POINTER(C.c_uint64))]
+
+
 class SimplifyStep(C.Structure):       # mdbg_simplify_step
     _fields_ = [("kind", C.c_uint32), ("max_nodes", C.c_uint32), ("max_bases", C.c_uint64)]
 
@@ -131,7 +137,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
-           "mdbg_graph_simplify", "mdbg_graph_simplify_device",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -222,6 +228,10 @@ def load_library():
     L.mdbg_graph_unitigs_device.argtypes = [vp, C.POINTER(UnitigList)]
     L.mdbg_graph_simplify.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
     L.mdbg_graph_simplify_device.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
+    L.mdbg_graph_contigs.argtypes = [vp, u64, C.POINTER(ContigSeqs)]
+    L.mdbg_graph_contigs_device.argtypes = [vp, u64, C.POINTER(ContigSeqs)]
+    L.mdbg_kept_reads.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.mdbg_contigs_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -263,8 +273,11 @@ def concat_reads(reads):
 class Mdbg:
     """One context = one device-resident sketch store + k-min-mer table (dbg_nodes, src/main.rs:595)."""
 
-    def __init__(self, k, l, density, min_abundance=2, reads_already_hpc=False, device=-1, flags=0, table_capacity_hint=0, syncmer_s=None):
+    def __init__(self, k, l, density, min_abundance=2, reads_already_hpc=False, device=-1, flags=0, table_capacity_hint=0, syncmer_s=None, keep_reads=False):
+        """keep_reads: the context keeps every batch it ingests with bases, packed 2 bits per base, on the device (MDBG_FLAG_KEEP_READS): graph_contigs()"""
         self.L = load_library()
+        if keep_reads:
+            flags |= FLAG_KEEP_READS
         self.params = Params(k=k, l=l, density=density, min_abundance=min_abundance, reads_already_hpc=int(reads_already_hpc),
                              device=device, flags=flags, table_capacity_hint=table_capacity_hint,
                              scheme=0 if syncmer_s is None else 1, syncmer_s=0 if syncmer_s is None else syncmer_s)      # syncmer_s: --syncmers -s
@@ -519,6 +532,33 @@ class Mdbg:
         u, st = UnitigList(), SimplifyStats()
         self._chk(self.L.mdbg_graph_simplify_device(self.h, arr, n, C.byref(u), C.byref(st)))
         return u, self._simplify_stats(st)
+
+    def kept_reads(self):
+        """the resident read store of a keep_reads context -> dict(n_reads, n_bases, bytes); bytes = n_bases / 4 + 8 per read + 9 per exception, up to the
+        rounding of each batch (include/mdbg_hip.h, mdbg_kept_reads)"""
+        r, b, y = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.L.mdbg_kept_reads(self.h, C.byref(r), C.byref(b), C.byref(y)))
+        return dict(n_reads=int(r.value), n_bases=int(b.value), bytes=int(y.value))
+
+    def graph_contigs(self, min_len=0, device=False):
+        """the sequences of the current unitig list (the last graph_unitigs* / graph_simplify* call) stitched on the GPU from the kept reads (keep_reads=True),
+        byte for byte what Emitter.contigs makes of the same reads on the host; only unitigs of at least min_len bases, in list order.
+        -> dict(n_contigs, n_bases, bases u8[n_bases], offsets u64[n_contigs + 1], unitig u64[n_contigs]); device=True: the ContigSeqs struct with DEVICE
+        pointers, owned by the context until its next graph_contigs call (they survive rewind / reset / ingest)"""
+        cs = ContigSeqs()
+        if device:
+            self._chk(self.L.mdbg_graph_contigs_device(self.h, min_len, C.byref(cs)))
+            return cs
+        self._chk(self.L.mdbg_graph_contigs(self.h, min_len, C.byref(cs)))
+        n = int(cs.n_contigs)
+        return dict(n_contigs=n, n_bases=int(cs.n_bases), bases=_np(cs.bases, int(cs.n_bases), np.uint8), offsets=_np(cs.offsets, n + 1, np.uint64),
+                    unitig=_np(cs.unitig, n, np.uint64))
+
+    def contigs_ms(self):
+        """device time of the stitch kernel of the last graph_contigs call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_contigs_ms(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def store_reserve(self, n_minimizers_total, n_reads_total):
         self._chk(self.L.mdbg_store_reserve(self.h, n_minimizers_total, n_reads_total))

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <ctime>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -16,6 +17,7 @@
 #include "edges.h"
 #include "unitigs.h"
 #include "simplify.h"
+#include "contigs.h"
 
 namespace {
 
@@ -129,12 +131,27 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// One batch of the resident read store (MDBG_FLAG_KEEP_READS): the packed layout of mdbg_packed_batch in device blocks of its own — `blk` holds the planes
+// (n_words x 8 bytes) followed by the n_reads + 1 offsets, `xblk` (only when there are exceptions) the n_exc positions followed by the n_exc bytes.
+// Owned by its Batch, so it lives exactly as long as the batch's sketch does (mdbg_reset(0) and mdbg_rewind drop both).
+struct KeptReads {
+    void* blk = nullptr; size_t cap = 0; void* xblk = nullptr; size_t xcap = 0;
+    u64 n_reads = 0, n_bases = 0, n_words = 0, n_exc = 0;
+    KeptReads() = default; KeptReads(const KeptReads&) = delete; KeptReads& operator=(const KeptReads&) = delete;
+    ~KeptReads() { if (blk) mdbg_block_free(blk, cap); if (xblk) mdbg_block_free(xblk, xcap); }
+    uint2* planes() const { return (uint2*)blk; }
+    u64* offsets() const { return (u64*)blk + n_words; }
+    u64* exc_pos() const { return (u64*)xblk; }
+    u8* exc_val() const { return (u8*)xblk + n_exc * 8; }
+    u64 bytes() const { return n_words * 8 + (n_reads + 1) * 8 + n_exc * 9; }
+};
 struct Batch { u64 first_ordinal; u32 n_reads; u32 slot0; u64 m0, m1; u64 owned = ~0ull;    // owned: windows of the batch this rank owns, if known
                u64 list_off = ~0ull;                                                       // their list (mdbg_owner_lists): offset into mdbg_ctx::own_lists, `owned` pairs + segments
                bool mread_ok = true;
                u32 src_rank = ~0u;                                                          // sketch exchange: the rank that sketched the batch (~0: this context); its positions are NOT resident when set
                u64 n_bases = 0;
-               bool partial = false; };                                                    // a foreign sketch of which only the hashes of this rank's listed windows are resident (mdbg_dist, segments)                                                         // raw bases of the batch (0: imported sketch)                                                    // false: imported with a list, the minimizer -> read map is filled on demand (ensure_mread)
+               bool partial = false;
+               std::shared_ptr<KeptReads> kept; };                                                    // a foreign sketch of which only the hashes of this rank's listed windows are resident (mdbg_dist, segments)                                                         // raw bases of the batch (0: imported sketch)                                                    // false: imported with a list, the minimizer -> read map is filled on demand (ensure_mread)
 
 // shard arrays (CTR_SHARDS u64 each): SH_DISTINCT keys in the table; SH_OWNED / SH_OWNINS: windows a partitioned context owns / inserted (zeroed by their users);
 // SH_FIN_WRAPPED / SH_FIN_DISTINCT: finalize's counters — touched by nothing else, and left ZERO by the finalize that used them (the kernel that publishes them
@@ -227,6 +244,11 @@ struct mdbg_ctx {
     UnitigBuffers* ub = nullptr;             // unitig compaction (unitigs.hip), created on first use
     HostRaw<u64> hu_off, hu_sread, hu_sbegin, hu_dst, hu_length, hu_kc; HostRaw<u32> hu_node, hu_len, hu_n1, hu_n2, hu_ov; HostRaw<u8> hu_ori, hu_rc, hu_circ, hu_o1, hu_o2;   // host copy of the last unitig list
     std::vector<u64> hs_unitigs, hs_nodes;   // per-step removal counts of the last mdbg_graph_simplify
+    UnitigResult last_ul{}; bool ulist_ok = false;      // device unitig list of the last unitig / simplify call; ulist_ok: it is current (no edge, finalize, ingest or reset call since)
+    ContigBuffers* cb = nullptr;             // contig stitching (contigs.hip), created on first use; its result buffers live until the next contig call
+    DevBuf kp_exc_pos, kp_exc_val, kp_cnt;   // keeping an ASCII batch: where the pack kernel appends the (unordered) exceptions, and their count
+    HostRaw<u8> hc_bases; HostRaw<u64> hc_off, hc_unitig;      // host copy of the last mdbg_graph_contigs
+    double ms_stitch = 0;                    // device time of the last stitch kernel
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -394,7 +416,7 @@ int table_reserve(mdbg_ctx* c, u64 incoming) {
 }
 
 int clear_table(mdbg_ctx* c) {
-    c->nodes_ok = false;
+    c->nodes_ok = false; c->ulist_ok = false;
     // the key counter's shards, SC_NDISTINCT + SC_NWINDOWS, SC_IMPORTERR, SC_PROBEERR: zeroed by the launch that clears the table (stream-ordered, no host sync) — or by
     // a launch of their own when there is no table yet
     ZeroList z{};
@@ -473,6 +495,50 @@ struct SketchInput {
     const u64* d_exc_pos = nullptr; const u8* d_exc_val = nullptr; u64 n_exc = 0;   // FMT_PLANES: bytes outside ACGT, sorted by position
 };
 int insert_resident_impl(mdbg_ctx* c, bool allow_pending = false);
+
+// MDBG_FLAG_KEEP_READS: a packed device copy of the batch that has just been sketched (the caller's buffers are still valid; the staging buffers of the
+// host entry points are reused by the next batch, so nothing is borrowed).  ASCII is packed by the kernel behind mdbg_pack_device; its exception list
+// comes back unordered and is sorted on the device (rocPRIM), so the only host round trip is the 8-byte count that sizes the side-list — and that one
+// only exists on a context that keeps reads.  Packed input is copied device to device.  Words and offsets are kept from base 0 of the batch, so a device
+// ASCII batch with offsets[0] > 0 keeps its offsets as they are (relative to the kept words).
+int keep_batch(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets, u64 n_reads, u64 n_bases, std::shared_ptr<KeptReads>& out) {
+    hipStream_t s = c->stream;
+    std::shared_ptr<KeptReads> k = std::make_shared<KeptReads>();
+    k->n_reads = n_reads; k->n_bases = n_bases; k->n_words = (n_bases + 31) / 32;
+    HIPCHK(c, mdbg_block_alloc(&k->blk, k->n_words * 8 + (n_reads + 1) * 8, &k->cap));
+    HIPCHK(c, hipMemcpyAsync(k->offsets(), d_offsets, (n_reads + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (in.fmt == FMT_PLANES) {
+        if (k->n_words) HIPCHK(c, hipMemcpyAsync(k->planes(), in.d_planes, k->n_words * 8, hipMemcpyDeviceToDevice, s));
+        k->n_exc = in.n_exc;
+        if (k->n_exc) {
+            HIPCHK(c, mdbg_block_alloc(&k->xblk, k->n_exc * 9, &k->xcap));
+            HIPCHK(c, hipMemcpyAsync(k->exc_pos(), in.d_exc_pos, k->n_exc * 8, hipMemcpyDeviceToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(k->exc_val(), in.d_exc_val, k->n_exc, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(c, hipStreamSynchronize(s));      // the source buffers are the caller's (or a staging slot's) once the ingest call returns
+    } else if (k->n_words) {
+        HIPCHK(c, c->kp_cnt.ensure(8, 0, s));
+        u64 cap = std::max<u64>(c->kp_exc_pos.cap / 8, 4096), n = 0;
+        for (int attempt = 0; attempt < 2; ++attempt) {      // a second time only when the side-list was too small for what the first pass counted
+            HIPCHK(c, c->kp_exc_pos.ensure(cap * 8, 0, s)); HIPCHK(c, c->kp_exc_val.ensure(cap, 0, s));
+            HIPCHK(c, hipMemsetAsync(c->kp_cnt.p, 0, 8, s));
+            launch_pack_planes(in.d_bases, n_bases, k->planes(), c->kp_exc_pos.as<u64>(), c->kp_exc_val.as<u8>(), cap, (unsigned long long*)c->kp_cnt.p, s);
+            HIPCHK(c, hipMemcpyAsync(&n, c->kp_cnt.p, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (n <= cap) break;
+            cap = n;
+        }
+        if (n > cap) return fail(c, MDBG_E_DEVICE, "the exception count of a kept batch changed between two passes");
+        k->n_exc = n;
+        if (n) {
+            HIPCHK(c, mdbg_block_alloc(&k->xblk, n * 9, &k->xcap));
+            if (!c->cb) c->cb = contig_buffers_create();
+            HIPCHK(c, sort_exceptions(c->cb, c->kp_exc_pos.as<u64>(), c->kp_exc_val.as<u8>(), k->exc_pos(), k->exc_val(), n, s));
+        }
+    } else HIPCHK(c, hipStreamSynchronize(s));
+    out = std::move(k);
+    return MDBG_OK;
+}
 // then_insert: the caller inserts the batch's windows right away.  When nothing stands in the way (a table exists, one launch, no filter, nothing
 // else pending) the window count, the capacity check and the insertion are launched BEHIND the sketch before the host has looked at it — one host
 // round trip per batch instead of two; the device-side check also stops the insertion when the sketch has to be repeated.  *inserted tells the caller.
@@ -679,6 +745,8 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
             m_new = sc[SC_CARRY];
         }
         Batch b; b.first_ordinal = first_ordinal; b.n_reads = (u32)n_reads; b.slot0 = slot0; b.m0 = c->M; b.m1 = m_new; b.n_bases = n_bases;
+        c->ulist_ok = false;                     // an ingest ends the current unitig list (mdbg_graph_contigs)
+        if (c->P.flags & MDBG_FLAG_KEEP_READS) { int ke = keep_batch(c, in, d_offsets, n_reads, n_bases, b.kept); if (ke) return ke; }
         c->batches.push_back(b);
         c->M = m_new; c->n_slots = slot0 + (u32)n_reads; c->slot_end_m = m_new;
         c->n_reads += n_reads; c->n_bases += n_bases; c->n_tiles += n_tiles_total; c->n_slow_tiles += slow_total;
@@ -724,7 +792,7 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
     if (c->pending_m && !allow_pending) return fail(c, MDBG_E_STATE, "reserved sketch regions have not been committed");
     hipStream_t s = c->stream;
     const size_t first = c->batches_inserted, last = c->batches.size();
-    c->nodes_ok = false;                     // the table is about to change: edges need a new finalize
+    c->nodes_ok = false; c->ulist_ok = false;      // the table is about to change: edges need a new finalize
     bool any = false;
     for (size_t i = first; i < last; ++i) any = any || c->batches[i].m1 > c->batches[i].m0;
     c->batches_inserted = last;
@@ -930,6 +998,7 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     for (auto e : c->tile_ev) (void)hipEventDestroy(e);
     if (c->eb) edge_buffers_destroy(c->eb);
     if (c->ub) unitig_buffers_destroy(c->ub);
+    if (c->cb) contig_buffers_destroy(c->cb);
     if (c->h_scal) (void)hipHostFree(c->h_scal);
     for (auto& g : c->stage) if (g.st) (void)hipStreamDestroy(g.st);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1400,7 +1469,7 @@ int mdbg_get_stats(mdbg_ctx* c, mdbg_stats* o) {
 // the ordinals), zeroed bitmaps over the resident minimizers, prefix buffers
 static int fin_setup(mdbg_ctx* c, FinArgs& F, u64& n_words_out, bool byte_maps = false) {
     hipStream_t s = c->stream;
-    c->nodes_ok = false;
+    c->nodes_ok = false; c->ulist_ok = false;
     F.ath_override = nullptr;
     const u32 k = c->P.k;
         // batches sorted by first ordinal -> dense order of the ordinals
@@ -1746,7 +1815,7 @@ static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_h
     if (!(presimp >= 0.0f)) return fail(c, MDBG_E_PARAM, "presimp must be >= 0");
     memset(out, 0, sizeof *out);
     if (!c->nodes_ok && !(c->cap == 0 || c->M == 0)) return fail(c, MDBG_E_STATE, "no finalized node table on this context (call mdbg_finalize / mdbg_finalize_device first)");
-    c->edges_ok = false; c->last_edges = EdgeResult{};
+    c->edges_ok = false; c->last_edges = EdgeResult{}; c->ulist_ok = false;
     if (!c->nodes_ok || c->nodes_n == 0) { c->edges_ok = c->nodes_ok; return MDBG_OK; }
     if (c->nodes_n >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
     if (!c->eb) c->eb = edge_buffers_create();
@@ -1786,10 +1855,11 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
         c->hs_unitigs.assign(n_steps, 0); c->hs_nodes.assign(n_steps, 0);
         stats->n_steps = n_steps; stats->unitigs_removed = c->hs_unitigs.data(); stats->nodes_removed = c->hs_nodes.data();
     }
+    c->ulist_ok = false; c->last_ul = UnitigResult{};
     if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "unitigs are single-GPU only: not available on a routed or partitioned context");
-    if (c->cap == 0 || c->M == 0) return MDBG_OK;                       // empty context: empty list
+    if (c->cap == 0 || c->M == 0) { c->ulist_ok = true; return MDBG_OK; }      // empty context: empty list
     if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
-    if (c->nodes_n == 0) return MDBG_OK;
+    if (c->nodes_n == 0) { c->ulist_ok = true; return MDBG_OK; }
     if (!c->ub) c->ub = unitig_buffers_create();
     const FinArgs& F = c->finF;
     UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
@@ -1804,6 +1874,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
         for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += c->hs_unitigs[i]; stats->total_nodes_removed += c->hs_nodes[i]; }
     }
+    c->last_ul = r; c->ulist_ok = true;
     const u64 U = r.n_unitigs, N = r.n_entries, E = r.edges.n;
     out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = E;
     if (!to_host) {
@@ -1836,6 +1907,60 @@ int mdbg_graph_simplify(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
 int mdbg_graph_simplify_device(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
     if (!stats) return MDBG_E_PARAM;
     return unitigs_impl(c, steps, n_steps, out, stats, false);
+}
+
+// ---- contigs stitched on the GPU from the resident read store (contigs.hip) ------------------------------
+int mdbg_kept_reads(mdbg_ctx* c, uint64_t* n_reads, uint64_t* n_bases, uint64_t* bytes) {
+    if (!c) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    u64 r = 0, b = 0, y = 0;
+    for (const Batch& bt : c->batches) if (bt.kept) { r += bt.kept->n_reads; b += bt.kept->n_bases; y += bt.kept->bytes(); }
+    if (n_reads) *n_reads = r;
+    if (n_bases) *n_bases = b;
+    if (bytes) *bytes = y;
+    return MDBG_OK;
+}
+static int contigs_impl(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    if (!(c->P.flags & MDBG_FLAG_KEEP_READS)) return fail(c, MDBG_E_STATE, "the context does not keep its reads (create it with MDBG_FLAG_KEEP_READS)");
+    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "contigs are single-GPU only: not available on a routed or partitioned context");
+    if (!c->ulist_ok) return fail(c, MDBG_E_STATE, "no current unitig list on this context (call mdbg_graph_unitigs* or mdbg_graph_simplify* first)");
+    std::vector<KeptDesc> tab;
+    for (const Batch& b : c->batches) {
+        if (!b.kept) return fail(c, MDBG_E_STATE, "a resident batch came without bases (an imported sketch): its reads are not kept");
+        const KeptReads& k = *b.kept;
+        KeptDesc d{}; d.first_ordinal = b.first_ordinal; d.n_reads = k.n_reads; d.planes = k.planes(); d.n_words = k.n_words; d.offsets = k.offsets();
+        d.exc_pos = k.n_exc ? k.exc_pos() : nullptr; d.exc_val = k.n_exc ? k.exc_val() : nullptr; d.n_exc = k.n_exc;
+        tab.push_back(d);
+    }
+    std::sort(tab.begin(), tab.end(), [](const KeptDesc& a, const KeptDesc& b) { return a.first_ordinal < b.first_ordinal; });
+    if (tab.size() >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "too many kept batches");
+    if (!c->cb) c->cb = contig_buffers_create();
+    ContigResult r; hipError_t he = hipSuccess;
+    if (stitch_contigs(c->cb, c->last_ul, tab.data(), (u32)tab.size(), min_len, c->stream, &r, &he)) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "stitch_contigs", he);
+    c->ms_stitch = r.ms_stitch;
+    if (r.err & 1u) return fail(c, MDBG_E_STATE, "an entry of the copy plan names a read that is not kept");
+    if (r.err & 2u) return fail(c, MDBG_E_PARAM, "an entry of the copy plan lies outside its read (not the reads the table was built from)");
+    out->n_contigs = r.n_contigs; out->n_bases = r.n_bases;
+    if (!to_host) { out->bases = r.bases; out->offsets = r.offsets; out->unitig = r.unitig; return MDBG_OK; }
+    if (!(c->hc_bases.resize(r.n_bases) && c->hc_off.resize(r.n_contigs + 1) && c->hc_unitig.resize(r.n_contigs))) return fail(c, MDBG_E_NOMEM, "host copy of the contigs");
+    if (r.n_bases) HIPCHK(c, hipMemcpy(c->hc_bases.data(), r.bases, r.n_bases, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->hc_off.data(), r.offsets, (r.n_contigs + 1) * 8, hipMemcpyDeviceToHost));
+    if (r.n_contigs) HIPCHK(c, hipMemcpy(c->hc_unitig.data(), r.unitig, r.n_contigs * 8, hipMemcpyDeviceToHost));
+    out->bases = c->hc_bases.data(); out->offsets = c->hc_off.data(); out->unitig = c->hc_unitig.data();
+    return MDBG_OK;
+}
+int mdbg_graph_contigs(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out) { return contigs_impl(c, min_len, out, true); }
+int mdbg_graph_contigs_device(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out) { return contigs_impl(c, min_len, out, false); }
+int mdbg_contigs_ms(mdbg_ctx* c, double* ms) {
+    if (!c || !ms) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    *ms = c->ms_stitch;
+    return MDBG_OK;
 }
 
 // ---- replicated-sketch multi-GPU mode (see include/mdbg_hip.h) ---------------------------------------

@@ -1,0 +1,245 @@
+// contigs.hip — contig sequences stitched on the GPU from the resident read store (mdbg_graph_contigs, include/mdbg_hip.h).
+//
+// The copy plan of a unitig list (unitigs.hip: bases [src_begin, src_begin + len) of read src_read go to [dst_offset, dst_offset + len) of the unitig, through
+// utils::revcomp `revcomp` times) is executed against the reads a MDBG_FLAG_KEEP_READS context kept packed 2 bits per base, byte for byte as
+// mdbg_emit_contigs_add_batch (mdbg_emit.cpp) executes it against the ASCII reads on the host.
+//
+// Shape: a pure gather, output-centric.  One thread owns 16 consecutive output bytes and writes them with one 16-byte store.  It finds its contig by binary
+// search in the contigs' offsets, its plan entry by binary search in the unitig's dst_offset[], the kept batch of the entry's read by binary search in the batch
+// table (all three tables are small next to the output and stay in L2), then funnel-shifts 16 codes out of the two bit planes — for a reverse complement the
+// 16 source positions are taken in one piece, bit-reversed (__brev) and the high plane flipped (the complement of code c is c ^ 2) — and expands them to
+// "ACTG"[c].  Bytes outside ACGT live in the batch's exception side-list and are patched in only when the batch has any (a branch that is uniform for all
+// threads inside one batch).  A 16-byte group that is not covered by ONE plan entry (an entry boundary, a contig boundary, the tail) takes the per-byte path.
+// Nothing is written with atomics except the error flag.
+#include <algorithm>
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+
+#include "contigs.h"
+
+typedef uint8_t u8; typedef uint16_t u16; typedef uint32_t u32; typedef uint64_t u64;
+
+namespace {
+
+struct Buf {
+    void* p = nullptr; size_t cap = 0;
+    ~Buf() { if (p) mdbg_block_free(p, cap); }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) mdbg_block_free(p, cap);
+        p = nullptr; cap = 0;
+        return mdbg_block_alloc(&p, bytes + bytes / 8 + 256, &cap);
+    }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+enum { ERR_NOT_KEPT = 1u, ERR_OUTSIDE = 2u };
+
+struct StitchArgs {
+    const u64* out_off; const u64* unitig; u64 n_contigs, n_bases;                                    // the produced contigs
+    const u64* u_off; const u64* src_read; const u64* src_begin; const u32* len; const u8* rc; const u64* dst;      // the plan
+    const KeptDesc* tab; u32 n_tab;
+    u8* out; u32* err;
+};
+
+// src/utils.rs:10-24, as mdbg_emit.cpp's switch_base
+__device__ inline u8 switch_base_dev(u8 c) {
+    switch (c) { case 'a': return 't'; case 'c': return 'g'; case 't': return 'a'; case 'g': return 'c'; case 'u': return 'a';
+                 case 'A': return 'T'; case 'C': return 'G'; case 'T': return 'A'; case 'G': return 'C'; case 'U': return 'A'; default: return 'N'; }
+}
+__device__ inline u8 through_revcomp(u8 c, u32 rc) { return rc == 0 ? c : rc == 1 ? switch_base_dev(c) : switch_base_dev(switch_base_dev(c)); }
+
+// largest i in [lo, hi) with a[i] <= v; the caller knows that hi > lo (a[lo] > v is reported by the caller's own test)
+__device__ inline u64 last_le(const u64* __restrict__ a, u64 lo, u64 hi, u64 v) {
+    while (hi - lo > 1) { const u64 mid = lo + ((hi - lo) >> 1); if (a[mid] <= v) lo = mid; else hi = mid; }
+    return lo;
+}
+
+struct Piece {                     // the plan entry that covers an output position, resolved against the store
+    const KeptDesc* d;
+    u64 sb;                        // position of the entry's first source base in the batch
+    u64 within;                    // the output position's offset inside the entry
+    u32 n, rc;                     // the entry's length and its revcomp count
+};
+// false: no kept base belongs at output position g (no entry covers it, or the entry is in error — the flag is set): the byte is 0, as the host path leaves it
+__device__ inline bool piece_of(const StitchArgs& A, u64 g, Piece& P) {
+    const u64 c = last_le(A.out_off, 0, A.n_contigs, g);
+    const u64 u = A.unitig[c];
+    const u64 e0 = A.u_off[u], e1 = A.u_off[u + 1], p = g - A.out_off[c];
+    if (e0 >= e1) return false;
+    const u64 e = last_le(A.dst, e0, e1, p);
+    const u64 d0 = A.dst[e];
+    const u32 n = A.len[e];
+    if (d0 > p || p - d0 >= n) return false;
+    const u64 r = A.src_read[e];
+    if (A.n_tab == 0 || A.tab[0].first_ordinal > r) { atomicOr(A.err, (u32)ERR_NOT_KEPT); return false; }
+    u32 lo = 0, hi = A.n_tab;
+    while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (A.tab[mid].first_ordinal <= r) lo = mid; else hi = mid; }
+    const KeptDesc* const d = A.tab + lo;
+    const u64 rl = r - d->first_ordinal;
+    if (rl >= d->n_reads) { atomicOr(A.err, (u32)ERR_NOT_KEPT); return false; }
+    const u64 ro = d->offsets[rl], re = d->offsets[rl + 1], b = A.src_begin[e];
+    if (re < ro || re > d->n_words * 32 || b > re - ro || n > re - ro - b) { atomicOr(A.err, (u32)ERR_OUTSIDE); return false; }
+    P.d = d; P.sb = ro + b; P.within = p - d0; P.n = n; P.rc = A.rc[e];
+    return true;
+}
+// the original byte at position q of a kept batch
+__device__ inline u8 kept_byte(const KeptDesc* d, u64 q) {
+    if (d->n_exc) {
+        const u64* const xp = d->exc_pos;
+        u64 lo = 0, hi = d->n_exc;
+        while (lo < hi) { const u64 mid = lo + ((hi - lo) >> 1); if (xp[mid] < q) lo = mid + 1; else hi = mid; }
+        if (lo < d->n_exc && xp[lo] == q) return d->exc_val[lo];
+    }
+    const uint2 w = d->planes[q >> 5];
+    const u32 b = (u32)q & 31u;
+    const u32 code = ((w.x >> b) & 1u) | (((w.y >> b) & 1u) << 1);
+    return (u8)(0x47544341u >> (8 * code));          // "ACTG"
+}
+
+__global__ __launch_bounds__(256) void stitch_kernel(StitchArgs A) {
+    const u64 G = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (G >= A.n_bases) return;
+    Piece P;
+    const bool have = piece_of(A, G, P);
+    if (have && P.n - P.within >= 16) {                    // the whole group comes from one entry (and so lies inside the output)
+        const bool rev = P.rc == 1;
+        const u64 qs = rev ? P.sb + P.n - 16 - P.within : P.sb + P.within;      // lowest of the 16 source positions
+        const u64 w = qs >> 5; const u32 b = (u32)qs & 31u;
+        const uint2 w0 = P.d->planes[w];
+        uint2 w1 = make_uint2(0, 0);
+        if (b > 16 && w + 1 < P.d->n_words) w1 = P.d->planes[w + 1];
+        u32 lo = (u32)((((u64)w1.x << 32) | w0.x) >> b) & 0xFFFFu, hi = (u32)((((u64)w1.y << 32) | w0.y) >> b) & 0xFFFFu;
+        if (rev) { lo = __brev(lo) >> 16; hi = (__brev(hi) >> 16) ^ 0xFFFFu; }
+        u32 o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            u32 v = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int j = 4 * q + t;
+                const u32 code = ((lo >> j) & 1u) | (((hi >> j) & 1u) << 1);
+                v |= ((0x47544341u >> (8 * code)) & 0xFFu) << (8 * t);
+            }
+            o[q] = v;
+        }
+        uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
+        if (P.d->n_exc) {                                  // rare: patch the bytes the planes cannot hold
+            const u64* const xp = P.d->exc_pos;
+            u64 i = 0, hi_i = P.d->n_exc;
+            while (i < hi_i) { const u64 mid = i + ((hi_i - i) >> 1); if (xp[mid] < qs) i = mid + 1; else hi_i = mid; }
+            for (; i < P.d->n_exc && xp[i] < qs + 16; ++i) {
+                const u32 j = rev ? 15u - (u32)(xp[i] - qs) : (u32)(xp[i] - qs);
+                const u32 v = through_revcomp(P.d->exc_val[i], P.rc), sh = 8 * (j & 3u), m = ~(0xFFu << sh);
+                const u32 q = j >> 2;
+                if (q == 0) ov.x = (ov.x & m) | (v << sh); else if (q == 1) ov.y = (ov.y & m) | (v << sh);
+                else if (q == 2) ov.z = (ov.z & m) | (v << sh); else ov.w = (ov.w & m) | (v << sh);
+            }
+        }
+        *(uint4*)(A.out + G) = ov;
+        return;
+    }
+    // an entry boundary, a contig boundary or the tail of the output inside the group: byte by byte
+    for (u32 j = 0; j < 16 && G + j < A.n_bases; ++j) {
+        u8 v = 0;
+        if (piece_of(A, G + j, P)) {
+            const u64 q = P.rc == 1 ? P.sb + P.n - 1 - P.within : P.sb + P.within;
+            v = through_revcomp(kept_byte(P.d, q), P.rc);
+        }
+        A.out[G + j] = v;
+    }
+}
+
+// flag[u] / slen[u] = 1 / length[u] for the unitigs that are produced; entry U of both = 0 (so that the exclusive scans end with the totals)
+__global__ void select_kernel(const u64* __restrict__ length, u64 U, u64 min_len, u64* __restrict__ flag, u64* __restrict__ slen) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u > U) return;
+    const bool take = u < U && length[u] >= min_len;
+    flag[u] = take ? 1 : 0; slen[u] = take ? length[u] : 0;
+}
+__global__ void scatter_kernel(const u64* __restrict__ length, u64 U, u64 min_len, const u64* __restrict__ cidx, const u64* __restrict__ uoff,
+                               u64* __restrict__ out_off, u64* __restrict__ unitig) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u > U) return;
+    if (u == U) { out_off[cidx[U]] = uoff[U]; return; }
+    if (length[u] >= min_len) { out_off[cidx[u]] = uoff[u]; unitig[cidx[u]] = u; }
+}
+
+}  // namespace
+
+struct ContigBuffers {
+    Buf flag, slen, cidx, uoff, tmp, tab, err;
+    Buf bases, offsets, unitig;                      // the result: owned until the next stitch_contigs
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+ContigBuffers* contig_buffers_create() { return new ContigBuffers(); }
+void contig_buffers_destroy(ContigBuffers* b) {
+    if (!b) return;
+    if (b->ev0) (void)hipEventDestroy(b->ev0);
+    if (b->ev1) (void)hipEventDestroy(b->ev1);
+    delete b;
+}
+
+#define CHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *herr = e_; return 1; } } while (0)
+
+static hipError_t excl_scan_u64(ContigBuffers* B, const u64* in, u64* out, size_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (u64)0, n, rocprim::plus<u64>(), s);
+    if (e != hipSuccess) return e;
+    e = B->tmp.ensure(tb + 256);
+    if (e != hipSuccess) return e;
+    return rocprim::exclusive_scan(B->tmp.p, tb, in, out, (u64)0, n, rocprim::plus<u64>(), s);
+}
+
+int stitch_contigs(ContigBuffers* B, const UnitigResult& ul, const KeptDesc* tab, uint32_t n_tab, uint64_t min_len, hipStream_t s, ContigResult* out, hipError_t* herr) {
+    memset(out, 0, sizeof *out);
+    *herr = hipSuccess;
+    const u64 U = ul.n_unitigs;
+    u64 C = 0, NB = 0;
+    if (U) {
+        CHIP(B->flag.ensure((U + 1) * 8)); CHIP(B->slen.ensure((U + 1) * 8)); CHIP(B->cidx.ensure((U + 1) * 8)); CHIP(B->uoff.ensure((U + 1) * 8));
+        hipLaunchKernelGGL(select_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, s, ul.length, U, min_len, B->flag.as<u64>(), B->slen.as<u64>());
+        CHIP(excl_scan_u64(B, B->flag.as<u64>(), B->cidx.as<u64>(), U + 1, s));
+        CHIP(excl_scan_u64(B, B->slen.as<u64>(), B->uoff.as<u64>(), U + 1, s));
+        CHIP(hipMemcpyAsync(&C, B->cidx.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));
+        CHIP(hipMemcpyAsync(&NB, B->uoff.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));
+        CHIP(hipStreamSynchronize(s));
+    }
+    CHIP(B->offsets.ensure((C + 1) * 8)); CHIP(B->unitig.ensure(C * 8 + 8)); CHIP(B->bases.ensure(NB + 32)); CHIP(B->err.ensure(8));
+    CHIP(hipMemsetAsync(B->err.p, 0, 8, s));
+    if (!C) CHIP(hipMemsetAsync(B->offsets.p, 0, 8, s));
+    else hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, s, ul.length, U, min_len, B->cidx.as<u64>(), B->uoff.as<u64>(), B->offsets.as<u64>(), B->unitig.as<u64>());
+    if (NB) {
+        if (n_tab) {
+            CHIP(B->tab.ensure((size_t)n_tab * sizeof(KeptDesc)));
+            CHIP(hipMemcpyAsync(B->tab.p, tab, (size_t)n_tab * sizeof(KeptDesc), hipMemcpyHostToDevice, s));
+        }
+        if (!B->ev0) { CHIP(hipEventCreate(&B->ev0)); CHIP(hipEventCreate(&B->ev1)); }
+        StitchArgs A{};
+        A.out_off = B->offsets.as<u64>(); A.unitig = B->unitig.as<u64>(); A.n_contigs = C; A.n_bases = NB;
+        A.u_off = ul.offsets; A.src_read = ul.src_read; A.src_begin = ul.src_begin; A.len = ul.len; A.rc = ul.revcomp; A.dst = ul.dst_offset;
+        A.tab = B->tab.as<KeptDesc>(); A.n_tab = n_tab; A.out = B->bases.as<u8>(); A.err = B->err.as<u32>();
+        const u64 groups = (NB + 15) / 16, blocks = (groups + 255) / 256;
+        if (blocks >= 0x7FFFFFFFull) { *herr = hipErrorInvalidValue; return 1; }
+        CHIP(hipEventRecord(B->ev0, s));
+        hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, A);
+        CHIP(hipEventRecord(B->ev1, s));
+    }
+    u32 err = 0;
+    CHIP(hipMemcpyAsync(&err, B->err.p, 4, hipMemcpyDeviceToHost, s));
+    CHIP(hipStreamSynchronize(s));                   // (also: `tab` is the caller's)
+    CHIP(hipGetLastError());
+    if (NB) { float ms = 0; if (hipEventElapsedTime(&ms, B->ev0, B->ev1) == hipSuccess) out->ms_stitch = ms; else (void)hipGetLastError(); }
+    out->n_contigs = C; out->n_bases = NB; out->bases = B->bases.as<u8>(); out->offsets = B->offsets.as<u64>(); out->unitig = B->unitig.as<u64>(); out->err = err;
+    return 0;
+}
+
+hipError_t sort_exceptions(ContigBuffers* B, const uint64_t* pos_in, const uint8_t* val_in, uint64_t* pos_out, uint8_t* val_out, uint64_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, pos_in, pos_out, val_in, val_out, (size_t)n, 0, 64, s);
+    if (e != hipSuccess) return e;
+    e = B->tmp.ensure(tb + 256);
+    if (e != hipSuccess) return e;
+    return rocprim::radix_sort_pairs(B->tmp.p, tb, pos_in, pos_out, val_in, val_out, (size_t)n, 0, 64, s);
+}

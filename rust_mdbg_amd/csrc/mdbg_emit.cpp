@@ -1447,6 +1447,15 @@ int mdbg_emit_contigs_add_batch(mdbg_contigs* h, const uint8_t* bases, const uin
     return MDBG_OK;
 }
 
+int mdbg_emit_contigs_set_sequences(mdbg_contigs* h, const uint8_t* bases, const uint64_t* offsets, uint64_t n_unitigs) {
+    if (!h || !offsets || n_unitigs != h->n_unitigs || offsets[0] != 0) return MDBG_E_PARAM;
+    for (u64 i = 0; i < n_unitigs; ++i) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] != h->length[i]) return MDBG_E_PARAM;
+    if (offsets[n_unitigs] && !bases) return MDBG_E_PARAM;
+    if (offsets[n_unitigs]) memcpy(&h->seq[0], bases, (size_t)offsets[n_unitigs]);        // (seq_off is the running sum of length[], as offsets has just been shown to be)
+    std::fill(h->filled.begin(), h->filled.end(), (u8)1); h->n_filled = h->n_entries;
+    return MDBG_OK;
+}
+
 int mdbg_emit_contigs_write_gfa(mdbg_contigs* h, const char* path) {
     if (!h || !path) return MDBG_E_PARAM;
     if (h->n_filled != h->n_entries) return MDBG_E_STATE;

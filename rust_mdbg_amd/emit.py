@@ -15,7 +15,7 @@ from .api import EdgeList as Edges          # one type for the host emitter's an
 
 
 EXPORTS = ["mdbg_lmer_filter_from_counts", "mdbg_lmer_filter_free", "mdbg_packed_words", "mdbg_pack_reads", "mdbg_seqfile_write_batch_part", "mdbg_emit_create", "mdbg_emit_destroy", "mdbg_emit_edges", "mdbg_emit_write_gfa", "mdbg_seqfile_open",
-           "mdbg_seqfile_write_batch", "mdbg_seqfile_close", "mdbg_emit_contigs_open", "mdbg_emit_contigs_add_batch", "mdbg_emit_contigs_write_gfa",
+           "mdbg_seqfile_write_batch", "mdbg_seqfile_close", "mdbg_emit_contigs_open", "mdbg_emit_contigs_add_batch", "mdbg_emit_contigs_set_sequences", "mdbg_emit_contigs_write_gfa",
            "mdbg_emit_contigs_write_fasta", "mdbg_emit_contigs_count", "mdbg_emit_contigs_get", "mdbg_emit_contigs_close"]
 
 
@@ -46,6 +46,7 @@ def load_library():
         L.mdbg_emit_contigs_open.restype = vp
         L.mdbg_emit_contigs_open.argtypes = [C.POINTER(UnitigList), C.POINTER(Nodes), C.POINTER(C.c_int)]
         L.mdbg_emit_contigs_add_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
+        L.mdbg_emit_contigs_set_sequences.argtypes = [vp, vp, vp, C.c_uint64]
         L.mdbg_emit_contigs_write_gfa.argtypes = [vp, C.c_char_p]
         L.mdbg_emit_contigs_write_fasta.argtypes = [vp, C.c_char_p, C.c_uint64]
         L.mdbg_emit_contigs_count.restype = C.c_uint64
@@ -109,6 +110,12 @@ class Contigs:
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self._chk(self.L.mdbg_emit_contigs_add_batch(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, first_read_ordinal), "mdbg_emit_contigs_add_batch")
+
+    def set_sequences(self, bases, offsets):
+        """instead of add_batch: every unitig's sequence from Mdbg.graph_contigs(min_len=0) (its `bases` and `offsets`); sizes are checked against the list"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._chk(self.L.mdbg_emit_contigs_set_sequences(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1), "mdbg_emit_contigs_set_sequences")
 
     def write_gfa(self, path):
         self._chk(self.L.mdbg_emit_contigs_write_gfa(self.h, os.fsencode(path)), "mdbg_emit_contigs_write_gfa")

@@ -21,13 +21,16 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
     to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
     simplify (with contigs): a schedule of tip / bubble steps, e.g. api.MAGIC_SIMPLIFY_STEPS — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
     Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
+    keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
+    there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
+    Adds kept_reads (the store's size) to the counters.
     threads: host threads of the reader (uncompressed input: mdbg_reader_open_mt) and of the 2-bit packer; packed: hand the GPU 2-bit
     packed batches (a quarter of the bytes over PCIe), default: when threads > 1"""
     if packed is None:
@@ -93,7 +96,9 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     tm = {}
     t0 = time.perf_counter()
     try:
-        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device) as m:
+        stitched = bool(contigs and keep_reads)      # the contigs' bases come from the device store, not from a second pass
+        kept = None
+        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=stitched) as m:
             apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max)
             tm["open"] = time.perf_counter() - t0
             while True:
@@ -129,23 +134,30 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
+                if stitched:
+                    g = m.graph_contigs(0)
+                    sctg.set_sequences(g["bases"], g["offsets"])
                 tm["simplify"] = time.perf_counter() - t0
             if contigs:                                  # the plan is copied out of the context here; the bases follow in the second pass
                 ctg = Contigs(m.graph_unitigs(raw=True), nodes["n_nodes"])
+                if stitched:
+                    g = m.graph_contigs(0)
+                    ctg.set_sequences(g["bases"], g["offsets"])
+                    kept = m.kept_reads()
                 tm["unitigs"] = time.perf_counter() - t0
         tm["close"] = time.perf_counter() - t0
     finally:
         stop.set()                          # error or not: release the reader (it closes the file) and wait for it
         th.join()
     tm["reader_closed"] = time.perf_counter() - t0
-    if write_sequences or ctg is not None:           # second pass over the input for the node sequences and the contigs' bases
+    if write_sequences or (ctg is not None and not stitched):           # second pass over the input for the node sequences and the contigs' bases
         def again():
             first = 0
             with Reader(path, strip_newlines, threads=threads) as r:
                 for bases, offs in r.batches(batch_bases, copy=False):      # consumed before the next batch is asked for
-                    if ctg is not None:
+                    if ctg is not None and not stitched:
                         ctg.add_batch(bases, offs, first)
-                    if sctg is not None:
+                    if sctg is not None and not stitched:
                         sctg.add_batch(bases, offs, first)
                     yield bases, offs, first
                     first += len(offs) - 1
@@ -159,6 +171,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             em.write_sequences(prefix + ".0.sequences", nodes, l, again())
         tm["sequences"] = time.perf_counter() - t1
     extra = {}
+    if kept is not None:
+        extra["kept_reads"] = kept
     if ctg is not None:
         with ctg:
             ctg.write_gfa(prefix + ".unitigs.gfa")
@@ -188,7 +202,8 @@ def concat_records(seqs):
 
 
 def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
-               strip_newlines=False, device=-1, contigs_fn=None, min_contig_len=100000, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000):
+               strip_newlines=False, device=-1, contigs_fn=None, min_contig_len=100000, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
+               keep_reads=False):
     """One pass over the reads, one graph per k (the k sweep of the reference's utils/multik:69-78): the reads are sketched once,
     the sketches stay resident on the GPU, and every k only clears and refills the counting table (mdbg_reset) and rebuilds nodes
     and edges.  Writes <prefix>-k<k>.gfa; -> {k: counters}.
@@ -201,12 +216,17 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     contigs_fn="unitigs": the built-in producer — the round's unitigs (Mdbg.graph_unitigs: `gfatools asm -u` + to_basespace, WITHOUT magic_simplify's tip and
     bubble rounds), stitched from the previous round's contigs and one more pass over the reads per round.
     contigs_fn="simplified": the same with the tip and bubble rounds — the contigs left after Mdbg.graph_simplify(api.MAGIC_SIMPLIFY_STEPS): the schedule of
-    magic_simplify's first gfatools line under this project's own rules (include/mdbg_hip.h), not gfatools parity."""
+    magic_simplify's first gfatools line under this project's own rules (include/mdbg_hip.h), not gfatools parity.
+    keep_reads (with the two built-in producers): the reads stay packed on the device (Mdbg(keep_reads=True)); a round's contigs are stitched there
+    (mdbg_graph_contigs_device(min_contig_len)) and ingested for the next round straight from that device buffer, twice, with first ordinals 0 and C — the
+    ordinals the concatenated contigs + contigs batch gives.  No Reader is opened after the first pass; same counters, same files."""
+    import ctypes
     ks = list(ks)
+    on_device = bool(keep_reads and contigs_fn in ("unitigs", "simplified"))
     out = {}
     n_reads = n_bases = 0
     base = READ_ORDINAL_BASE if contigs_fn is not None else 0
-    with Mdbg(ks[0], l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device) as m, Reader(path, strip_newlines) as r:
+    with Mdbg(ks[0], l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=on_device) as m, Reader(path, strip_newlines) as r:
         apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max)
         for bases, offs in r.batches(batch_bases):
             m.ingest(bases, offs, base + n_reads)
@@ -215,11 +235,16 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
         mark = m.mark()
         em = Emitter()
         contigs = []
+        dev_contigs = None                               # on_device: (d_bases, d_offsets, C, n_bases) of the last round's contigs, owned by the context
         for i, k in enumerate(ks):
             if i:
                 if contigs_fn is not None:
                     m.rewind(mark)                       # last round's contigs go, the reads' sketches stay
                 m.reset(k)                               # sketches stay; windows of the new k are inserted again
+                if dev_contigs is not None and dev_contigs[2]:
+                    db, do, nc, nb = dev_contigs         # (the buffers live until the next graph_contigs call; a keeping context copies what it ingests)
+                    m.ingest_device(db, do, nc, nb, 0)
+                    m.ingest_device(db, do, nc, nb, nc)
                 if contigs:
                     twice = contigs + contigs
                     cb, co = concat_records(twice)
@@ -229,10 +254,17 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
             gfa = "%s-k%d.gfa" % (prefix, k)
             em.write_gfa(gfa, nodes, raw)
             st = m.stats()
-            out[k] = dict(n_reads=n_reads, n_bases=n_bases, n_contigs=len(contigs), n_minimizers=st["n_minimizers"], n_windows=st["n_windows"],
+            out[k] = dict(n_reads=n_reads, n_bases=n_bases, n_contigs=dev_contigs[2] if dev_contigs is not None else len(contigs), n_minimizers=st["n_minimizers"], n_windows=st["n_windows"],
                           n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=int(raw.n),
                           presimp_removed=int(raw.presimp_removed))
-            if contigs_fn in ("unitigs", "simplified"):
+            if on_device:
+                if contigs_fn == "unitigs":
+                    m.graph_unitigs_device()
+                else:
+                    m.graph_simplify_device(MAGIC_SIMPLIFY_STEPS)
+                cs = m.graph_contigs(min_contig_len, device=True)
+                dev_contigs = (ctypes.cast(cs.bases, ctypes.c_void_p).value or 0, ctypes.cast(cs.offsets, ctypes.c_void_p).value or 0, int(cs.n_contigs), int(cs.n_bases))
+            elif contigs_fn in ("unitigs", "simplified"):
                 def fed():                               # what this round ingested, with its ordinals: the contigs in front, then the reads
                     if contigs:
                         yield concat_records(contigs + contigs) + (0,)
