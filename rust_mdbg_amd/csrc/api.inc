@@ -263,6 +263,13 @@ int fail(mdbg_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
 }
 #define MDBG_LOCK(c) std::lock_guard<std::recursive_mutex> lock_((c)->mu)
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail((c), e_ == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, #call, e_); } while (0)
+// one column of a copy-out: *host <- the context's host copy `h` of the n elements at `dev` (device memory).  Blocking; `what` names the list in the error.
+template <class T> int copy_out(mdbg_ctx* c, HostRaw<T>& h, const T* dev, size_t n, const char* what, const T** host) {
+    if (!h.resize(n)) return fail(c, MDBG_E_NOMEM, what);
+    if (n) { const hipError_t e = hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost); if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, what, e); }
+    *host = h.data();
+    return MDBG_OK;
+}
 
 u64* scal(mdbg_ctx* c) { return c->scalars.as<u64>(); }
 // with_fin: also the two finalize counters (shard arrays 2, 3 -> SC_FIN1, SC_FIN2)
@@ -1638,24 +1645,13 @@ static int finalize_hand_over(mdbg_ctx* c, mdbg_nodes* out, bool to_host, u64 n)
         out->shift_full = F.o_shift_full; out->src_read = F.o_src_read; out->src_start = F.o_src_start; out->src_end = F.o_src_end; out->reversed = F.o_rev;
         return MDBG_OK;
     }
-    if (!(c->h_keys.resize(n * k) && c->h_shift_full.resize(2 * n) && c->h_src_read.resize(n) && c->h_src_start.resize(n) && c->h_src_end.resize(n) &&
-          c->h_index.resize(n) && c->h_seqlen.resize(n) && c->h_abund.resize(n) && c->h_shift.resize(2 * n) && c->h_rev.resize(n)))
-        return fail(c, MDBG_E_NOMEM, "host copy of the node table");
-    if (n) {
-        HIPCHK(c, hipMemcpy(c->h_keys.data(), F.o_keys, n * k * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_shift_full.data(), F.o_shift_full, n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_src_read.data(), F.o_src_read, n * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_src_start.data(), F.o_src_start, n * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_src_end.data(), F.o_src_end, n * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_index.data(), F.o_index, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_seqlen.data(), F.o_seqlen, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_abund.data(), F.o_abund, n * 2, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_shift.data(), F.o_shift, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_rev.data(), F.o_rev, n, hipMemcpyDeviceToHost));
-    }
-    out->keys = c->h_keys.data(); out->index = c->h_index.data(); out->abundance = c->h_abund.data(); out->seqlen = c->h_seqlen.data();
-    out->shift = c->h_shift.data(); out->shift_full = c->h_shift_full.data(); out->src_read = c->h_src_read.data();
-    out->src_start = c->h_src_start.data(); out->src_end = c->h_src_end.data(); out->reversed = c->h_rev.data();
+    const char* const what = "host copy of the node table";
+    int e;
+    if ((e = copy_out(c, c->h_keys, F.o_keys, n * k, what, &out->keys)) || (e = copy_out(c, c->h_index, F.o_index, n, what, &out->index)) ||
+        (e = copy_out(c, c->h_abund, F.o_abund, n, what, &out->abundance)) || (e = copy_out(c, c->h_seqlen, F.o_seqlen, n, what, &out->seqlen)) ||
+        (e = copy_out(c, c->h_shift, F.o_shift, 2 * n, what, &out->shift)) || (e = copy_out(c, c->h_shift_full, F.o_shift_full, 2 * n, what, &out->shift_full)) ||
+        (e = copy_out(c, c->h_src_read, F.o_src_read, n, what, &out->src_read)) || (e = copy_out(c, c->h_src_start, F.o_src_start, n, what, &out->src_start)) ||
+        (e = copy_out(c, c->h_src_end, F.o_src_end, n, what, &out->src_end)) || (e = copy_out(c, c->h_rev, F.o_rev, n, what, &out->reversed))) return e;
     return MDBG_OK;
 }
 // finalize, phase 2: ranks from the (possibly all-reduced) bitmaps, then the node rows of this context's solid keys.
@@ -1806,162 +1802,8 @@ int mdbg_nodes_digest(mdbg_ctx* c, const mdbg_nodes* nodes, uint64_t* sum, uint6
     return MDBG_OK;
 }
 
-// ---- graph edges of the last finalized node table (edges.hip) -------------------------------------------
-static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_host) {
-    if (!c || !out) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
-    if (!(presimp >= 0.0f)) return fail(c, MDBG_E_PARAM, "presimp must be >= 0");
-    memset(out, 0, sizeof *out);
-    if (!c->nodes_ok && !(c->cap == 0 || c->M == 0)) return fail(c, MDBG_E_STATE, "no finalized node table on this context (call mdbg_finalize / mdbg_finalize_device first)");
-    c->edges_ok = false; c->last_edges = EdgeResult{}; c->ulist_ok = false;
-    if (!c->nodes_ok || c->nodes_n == 0) { c->edges_ok = c->nodes_ok; return MDBG_OK; }
-    if (c->nodes_n >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
-    if (!c->eb) c->eb = edge_buffers_create();
-    const FinArgs& F = c->finF;
-    EdgeNodes nd; nd.keys = F.o_keys; nd.index = F.o_index; nd.abund = F.o_abund; nd.seqlen = F.o_seqlen; nd.shift = F.o_shift; nd.n = c->nodes_n; nd.k = c->P.k;
-    EdgeResult r;
-    HIPCHK(c, build_edges(c->eb, nd, presimp, c->stream, &r));
-    c->last_edges = r; c->edges_ok = true;
-    out->n = r.n; out->presimp_removed = r.presimp_removed;
-    if (!to_host) { out->n1 = r.n1; out->o1 = r.o1; out->n2 = r.n2; out->o2 = r.o2; out->overlap = r.overlap; return MDBG_OK; }
-    if (!(c->he_n1.resize(r.n) && c->he_n2.resize(r.n) && c->he_ov.resize(r.n) && c->he_o1.resize(r.n) && c->he_o2.resize(r.n))) return fail(c, MDBG_E_NOMEM, "host copy of the edge list");
-    if (r.n) {
-        HIPCHK(c, hipMemcpy(c->he_n1.data(), r.n1, r.n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->he_n2.data(), r.n2, r.n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->he_ov.data(), r.overlap, r.n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->he_o1.data(), r.o1, r.n, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->he_o2.data(), r.o2, r.n, hipMemcpyDeviceToHost));
-    }
-    out->n1 = c->he_n1.data(); out->o1 = c->he_o1.data(); out->n2 = c->he_n2.data(); out->o2 = c->he_o2.data(); out->overlap = c->he_ov.data();
-    return MDBG_OK;
-}
-int mdbg_graph_edges(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return edges_impl(c, presimp, out, true); }
-int mdbg_graph_edges_device(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { return edges_impl(c, presimp, out, false); }
-
-// ---- unitigs + base-space copy plan of the last node table and edge list (unitigs.hip) -------------------
-// steps == nullptr: plain compaction (mdbg_graph_unitigs); otherwise the schedule runs first (mdbg_graph_simplify, simplify.hip) and stats is filled
-static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats, bool to_host) {
-    if (!c || !out || (stats && n_steps && !steps)) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
-    memset(out, 0, sizeof *out);
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        for (uint32_t i = 0; i < n_steps; ++i)
-            if (steps[i].kind != MDBG_SIMPLIFY_TIPS && steps[i].kind != MDBG_SIMPLIFY_BUBBLES) return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
-        c->hs_unitigs.assign(n_steps, 0); c->hs_nodes.assign(n_steps, 0);
-        stats->n_steps = n_steps; stats->unitigs_removed = c->hs_unitigs.data(); stats->nodes_removed = c->hs_nodes.data();
-    }
-    c->ulist_ok = false; c->last_ul = UnitigResult{};
-    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "unitigs are single-GPU only: not available on a routed or partitioned context");
-    if (c->cap == 0 || c->M == 0) { c->ulist_ok = true; return MDBG_OK; }      // empty context: empty list
-    if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
-    if (c->nodes_n == 0) { c->ulist_ok = true; return MDBG_OK; }
-    if (!c->ub) c->ub = unitig_buffers_create();
-    const FinArgs& F = c->finF;
-    UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
-    nd.reversed = F.o_rev; nd.n = c->nodes_n;
-    UnitigResult r; hipError_t he = hipSuccess;
-    SimplifyInfo si{};
-    const int rc = stats ? simplify_unitigs(c->ub, nd, c->last_edges, steps, n_steps, c->stream, &r, c->hs_unitigs.data(), c->hs_nodes.data(), &si, &he)
-                         : build_unitigs(c->ub, nd, c->last_edges, c->stream, &r, &he);
-    if (rc == 1) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "build_unitigs", he);
-    if (rc) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, or the walk broke an invariant");
-    if (stats) {
-        stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
-        for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += c->hs_unitigs[i]; stats->total_nodes_removed += c->hs_nodes[i]; }
-    }
-    c->last_ul = r; c->ulist_ok = true;
-    const u64 U = r.n_unitigs, N = r.n_entries, E = r.edges.n;
-    out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = E;
-    if (!to_host) {
-        out->offsets = r.offsets; out->node = r.node; out->ori = r.ori; out->src_read = r.src_read; out->src_begin = r.src_begin; out->len = r.len; out->revcomp = r.revcomp;
-        out->dst_offset = r.dst_offset; out->length = r.length; out->kc_sum = r.kc_sum; out->circular = r.circular;
-        out->edges.n1 = r.edges.n1; out->edges.o1 = r.edges.o1; out->edges.n2 = r.edges.n2; out->edges.o2 = r.edges.o2; out->edges.overlap = r.edges.overlap;
-        return MDBG_OK;
-    }
-    if (!(c->hu_off.resize(U + 1) && c->hu_node.resize(N) && c->hu_ori.resize(N) && c->hu_sread.resize(N) && c->hu_sbegin.resize(N) && c->hu_len.resize(N) && c->hu_rc.resize(N) &&
-          c->hu_dst.resize(N) && c->hu_length.resize(U) && c->hu_kc.resize(U) && c->hu_circ.resize(U) && c->hu_n1.resize(E) && c->hu_n2.resize(E) && c->hu_ov.resize(E) &&
-          c->hu_o1.resize(E) && c->hu_o2.resize(E))) return fail(c, MDBG_E_NOMEM, "host copy of the unitig list");
-#define UCOPY(dst, src, cnt, sz) do { if (cnt) HIPCHK(c, hipMemcpy((dst).data(), (src), (size_t)(cnt) * (sz), hipMemcpyDeviceToHost)); } while (0)
-    UCOPY(c->hu_off, r.offsets, U + 1, 8); UCOPY(c->hu_node, r.node, N, 4); UCOPY(c->hu_ori, r.ori, N, 1); UCOPY(c->hu_sread, r.src_read, N, 8); UCOPY(c->hu_sbegin, r.src_begin, N, 8);
-    UCOPY(c->hu_len, r.len, N, 4); UCOPY(c->hu_rc, r.revcomp, N, 1); UCOPY(c->hu_dst, r.dst_offset, N, 8); UCOPY(c->hu_length, r.length, U, 8); UCOPY(c->hu_kc, r.kc_sum, U, 8);
-    UCOPY(c->hu_circ, r.circular, U, 1); UCOPY(c->hu_n1, r.edges.n1, E, 4); UCOPY(c->hu_n2, r.edges.n2, E, 4); UCOPY(c->hu_ov, r.edges.overlap, E, 4); UCOPY(c->hu_o1, r.edges.o1, E, 1);
-    UCOPY(c->hu_o2, r.edges.o2, E, 1);
-#undef UCOPY
-    out->offsets = c->hu_off.data(); out->node = c->hu_node.data(); out->ori = c->hu_ori.data(); out->src_read = c->hu_sread.data(); out->src_begin = c->hu_sbegin.data();
-    out->len = c->hu_len.data(); out->revcomp = c->hu_rc.data(); out->dst_offset = c->hu_dst.data(); out->length = c->hu_length.data(); out->kc_sum = c->hu_kc.data();
-    out->circular = c->hu_circ.data(); out->edges.n1 = c->hu_n1.data(); out->edges.o1 = c->hu_o1.data(); out->edges.n2 = c->hu_n2.data(); out->edges.o2 = c->hu_o2.data();
-    out->edges.overlap = c->hu_ov.data();
-    return MDBG_OK;
-}
-int mdbg_graph_unitigs(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, nullptr, 0, out, nullptr, true); }
-int mdbg_graph_unitigs_device(mdbg_ctx* c, mdbg_unitig_list* out) { return unitigs_impl(c, nullptr, 0, out, nullptr, false); }
-int mdbg_graph_simplify(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
-    if (!stats) return MDBG_E_PARAM;
-    return unitigs_impl(c, steps, n_steps, out, stats, true);
-}
-int mdbg_graph_simplify_device(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
-    if (!stats) return MDBG_E_PARAM;
-    return unitigs_impl(c, steps, n_steps, out, stats, false);
-}
-
-// ---- contigs stitched on the GPU from the resident read store (contigs.hip) ------------------------------
-int mdbg_kept_reads(mdbg_ctx* c, uint64_t* n_reads, uint64_t* n_bases, uint64_t* bytes) {
-    if (!c) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    u64 r = 0, b = 0, y = 0;
-    for (const Batch& bt : c->batches) if (bt.kept) { r += bt.kept->n_reads; b += bt.kept->n_bases; y += bt.kept->bytes(); }
-    if (n_reads) *n_reads = r;
-    if (n_bases) *n_bases = b;
-    if (bytes) *bytes = y;
-    return MDBG_OK;
-}
-static int contigs_impl(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out, bool to_host) {
-    if (!c || !out) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
-    memset(out, 0, sizeof *out);
-    if (!(c->P.flags & MDBG_FLAG_KEEP_READS)) return fail(c, MDBG_E_STATE, "the context does not keep its reads (create it with MDBG_FLAG_KEEP_READS)");
-    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "contigs are single-GPU only: not available on a routed or partitioned context");
-    if (!c->ulist_ok) return fail(c, MDBG_E_STATE, "no current unitig list on this context (call mdbg_graph_unitigs* or mdbg_graph_simplify* first)");
-    std::vector<KeptDesc> tab;
-    for (const Batch& b : c->batches) {
-        if (!b.kept) return fail(c, MDBG_E_STATE, "a resident batch came without bases (an imported sketch): its reads are not kept");
-        const KeptReads& k = *b.kept;
-        KeptDesc d{}; d.first_ordinal = b.first_ordinal; d.n_reads = k.n_reads; d.planes = k.planes(); d.n_words = k.n_words; d.offsets = k.offsets();
-        d.exc_pos = k.n_exc ? k.exc_pos() : nullptr; d.exc_val = k.n_exc ? k.exc_val() : nullptr; d.n_exc = k.n_exc;
-        tab.push_back(d);
-    }
-    std::sort(tab.begin(), tab.end(), [](const KeptDesc& a, const KeptDesc& b) { return a.first_ordinal < b.first_ordinal; });
-    if (tab.size() >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "too many kept batches");
-    if (!c->cb) c->cb = contig_buffers_create();
-    ContigResult r; hipError_t he = hipSuccess;
-    if (stitch_contigs(c->cb, c->last_ul, tab.data(), (u32)tab.size(), min_len, c->stream, &r, &he)) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "stitch_contigs", he);
-    c->ms_stitch = r.ms_stitch;
-    if (r.err & 1u) return fail(c, MDBG_E_STATE, "an entry of the copy plan names a read that is not kept");
-    if (r.err & 2u) return fail(c, MDBG_E_PARAM, "an entry of the copy plan lies outside its read (not the reads the table was built from)");
-    out->n_contigs = r.n_contigs; out->n_bases = r.n_bases;
-    if (!to_host) { out->bases = r.bases; out->offsets = r.offsets; out->unitig = r.unitig; return MDBG_OK; }
-    if (!(c->hc_bases.resize(r.n_bases) && c->hc_off.resize(r.n_contigs + 1) && c->hc_unitig.resize(r.n_contigs))) return fail(c, MDBG_E_NOMEM, "host copy of the contigs");
-    if (r.n_bases) HIPCHK(c, hipMemcpy(c->hc_bases.data(), r.bases, r.n_bases, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(c->hc_off.data(), r.offsets, (r.n_contigs + 1) * 8, hipMemcpyDeviceToHost));
-    if (r.n_contigs) HIPCHK(c, hipMemcpy(c->hc_unitig.data(), r.unitig, r.n_contigs * 8, hipMemcpyDeviceToHost));
-    out->bases = c->hc_bases.data(); out->offsets = c->hc_off.data(); out->unitig = c->hc_unitig.data();
-    return MDBG_OK;
-}
-int mdbg_graph_contigs(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out) { return contigs_impl(c, min_len, out, true); }
-int mdbg_graph_contigs_device(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out) { return contigs_impl(c, min_len, out, false); }
-int mdbg_contigs_ms(mdbg_ctx* c, double* ms) {
-    if (!c || !ms) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    *ms = c->ms_stitch;
-    return MDBG_OK;
-}
+// ---- graph entry points (edges, unitigs, simplification, contigs): implemented in graph_api.inc -----------
+#include "graph_api.inc"
 
 // ---- replicated-sketch multi-GPU mode (see include/mdbg_hip.h) ---------------------------------------
 int mdbg_set_partition(mdbg_ctx* c, uint32_t world, uint32_t rank) {

@@ -26,8 +26,8 @@ struct ContigResult {              // device pointers into ContigBuffers, valid 
     float ms_stitch;               // device time of the stitch kernel alone (HIP events)
 };
 // Executes the copy plan of `ul` (the unitigs with length >= min_len, in list order) against the kept batches `tab` (HOST array, sorted by first_ordinal).
-// 0 = ok (look at out->err); 1 = HIP failure (*herr).  Synchronises the stream before returning.
-int stitch_contigs(ContigBuffers* B, const UnitigResult& ul, const KeptDesc* tab, uint32_t n_tab, uint64_t min_len, hipStream_t s, ContigResult* out, hipError_t* herr);
+// Returns hipSuccess (look at out->err) or the failing HIP error.  Synchronises the stream before returning.
+hipError_t stitch_contigs(ContigBuffers* B, const UnitigResult& ul, const KeptDesc* tab, uint32_t n_tab, uint64_t min_len, hipStream_t s, ContigResult* out);
 
 // the exception side-list as pack_planes_kernel leaves it (unordered) -> ascending by position (rocPRIM radix sort of (position, byte) pairs; stream-ordered)
 hipError_t sort_exceptions(ContigBuffers* B, const uint64_t* pos_in, const uint8_t* val_in, uint64_t* pos_out, uint8_t* val_out, uint64_t n, hipStream_t s);

@@ -11,28 +11,12 @@
 // "ACTG"[c].  Bytes outside ACGT live in the batch's exception side-list and are patched in only when the batch has any (a branch that is uniform for all
 // threads inside one batch).  A 16-byte group that is not covered by ONE plan entry (an entry boundary, a contig boundary, the tail) takes the per-byte path.
 // Nothing is written with atomics except the error flag.
-#include <algorithm>
 #include <cstring>
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
 #include "contigs.h"
-
-typedef uint8_t u8; typedef uint16_t u16; typedef uint32_t u32; typedef uint64_t u64;
+#include "graph_common.h"
 
 namespace {
-
-struct Buf {
-    void* p = nullptr; size_t cap = 0;
-    ~Buf() { if (p) mdbg_block_free(p, cap); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) mdbg_block_free(p, cap);
-        p = nullptr; cap = 0;
-        return mdbg_block_alloc(&p, bytes + bytes / 8 + 256, &cap);
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 enum { ERR_NOT_KEPT = 1u, ERR_OUTSIDE = 2u };
 
@@ -181,65 +165,48 @@ void contig_buffers_destroy(ContigBuffers* b) {
     delete b;
 }
 
-#define CHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *herr = e_; return 1; } } while (0)
-
-static hipError_t excl_scan_u64(ContigBuffers* B, const u64* in, u64* out, size_t n, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (u64)0, n, rocprim::plus<u64>(), s);
-    if (e != hipSuccess) return e;
-    e = B->tmp.ensure(tb + 256);
-    if (e != hipSuccess) return e;
-    return rocprim::exclusive_scan(B->tmp.p, tb, in, out, (u64)0, n, rocprim::plus<u64>(), s);
-}
-
-int stitch_contigs(ContigBuffers* B, const UnitigResult& ul, const KeptDesc* tab, uint32_t n_tab, uint64_t min_len, hipStream_t s, ContigResult* out, hipError_t* herr) {
+hipError_t stitch_contigs(ContigBuffers* B, const UnitigResult& ul, const KeptDesc* tab, uint32_t n_tab, uint64_t min_len, hipStream_t s, ContigResult* out) {
     memset(out, 0, sizeof *out);
-    *herr = hipSuccess;
     const u64 U = ul.n_unitigs;
     u64 C = 0, NB = 0;
     if (U) {
-        CHIP(B->flag.ensure((U + 1) * 8)); CHIP(B->slen.ensure((U + 1) * 8)); CHIP(B->cidx.ensure((U + 1) * 8)); CHIP(B->uoff.ensure((U + 1) * 8));
+        GHIP(B->flag.ensure((U + 1) * 8)); GHIP(B->slen.ensure((U + 1) * 8)); GHIP(B->cidx.ensure((U + 1) * 8)); GHIP(B->uoff.ensure((U + 1) * 8));
         hipLaunchKernelGGL(select_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, s, ul.length, U, min_len, B->flag.as<u64>(), B->slen.as<u64>());
-        CHIP(excl_scan_u64(B, B->flag.as<u64>(), B->cidx.as<u64>(), U + 1, s));
-        CHIP(excl_scan_u64(B, B->slen.as<u64>(), B->uoff.as<u64>(), U + 1, s));
-        CHIP(hipMemcpyAsync(&C, B->cidx.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));
-        CHIP(hipMemcpyAsync(&NB, B->uoff.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));
-        CHIP(hipStreamSynchronize(s));
+        GHIP(excl_scan(B->tmp, B->flag.as<u64>(), B->cidx.as<u64>(), U + 1, s));
+        GHIP(excl_scan(B->tmp, B->slen.as<u64>(), B->uoff.as<u64>(), U + 1, s));
+        GHIP(hipMemcpyAsync(&C, B->cidx.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));      // (entry U of both inputs is 0: the last outputs ARE the totals)
+        GHIP(hipMemcpyAsync(&NB, B->uoff.as<u64>() + U, 8, hipMemcpyDeviceToHost, s));
+        GHIP(hipStreamSynchronize(s));
     }
-    CHIP(B->offsets.ensure((C + 1) * 8)); CHIP(B->unitig.ensure(C * 8 + 8)); CHIP(B->bases.ensure(NB + 32)); CHIP(B->err.ensure(8));
-    CHIP(hipMemsetAsync(B->err.p, 0, 8, s));
-    if (!C) CHIP(hipMemsetAsync(B->offsets.p, 0, 8, s));
+    GHIP(B->offsets.ensure((C + 1) * 8)); GHIP(B->unitig.ensure(C * 8 + 8)); GHIP(B->bases.ensure(NB + 32)); GHIP(B->err.ensure(8));
+    GHIP(hipMemsetAsync(B->err.p, 0, 8, s));
+    if (!C) GHIP(hipMemsetAsync(B->offsets.p, 0, 8, s));
     else hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, s, ul.length, U, min_len, B->cidx.as<u64>(), B->uoff.as<u64>(), B->offsets.as<u64>(), B->unitig.as<u64>());
     if (NB) {
         if (n_tab) {
-            CHIP(B->tab.ensure((size_t)n_tab * sizeof(KeptDesc)));
-            CHIP(hipMemcpyAsync(B->tab.p, tab, (size_t)n_tab * sizeof(KeptDesc), hipMemcpyHostToDevice, s));
+            GHIP(B->tab.ensure((size_t)n_tab * sizeof(KeptDesc)));
+            GHIP(hipMemcpyAsync(B->tab.p, tab, (size_t)n_tab * sizeof(KeptDesc), hipMemcpyHostToDevice, s));
         }
-        if (!B->ev0) { CHIP(hipEventCreate(&B->ev0)); CHIP(hipEventCreate(&B->ev1)); }
+        if (!B->ev0) { GHIP(hipEventCreate(&B->ev0)); GHIP(hipEventCreate(&B->ev1)); }
         StitchArgs A{};
         A.out_off = B->offsets.as<u64>(); A.unitig = B->unitig.as<u64>(); A.n_contigs = C; A.n_bases = NB;
         A.u_off = ul.offsets; A.src_read = ul.src_read; A.src_begin = ul.src_begin; A.len = ul.len; A.rc = ul.revcomp; A.dst = ul.dst_offset;
         A.tab = B->tab.as<KeptDesc>(); A.n_tab = n_tab; A.out = B->bases.as<u8>(); A.err = B->err.as<u32>();
         const u64 groups = (NB + 15) / 16, blocks = (groups + 255) / 256;
-        if (blocks >= 0x7FFFFFFFull) { *herr = hipErrorInvalidValue; return 1; }
-        CHIP(hipEventRecord(B->ev0, s));
+        if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+        GHIP(hipEventRecord(B->ev0, s));
         hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, A);
-        CHIP(hipEventRecord(B->ev1, s));
+        GHIP(hipEventRecord(B->ev1, s));
     }
     u32 err = 0;
-    CHIP(hipMemcpyAsync(&err, B->err.p, 4, hipMemcpyDeviceToHost, s));
-    CHIP(hipStreamSynchronize(s));                   // (also: `tab` is the caller's)
-    CHIP(hipGetLastError());
+    GHIP(hipMemcpyAsync(&err, B->err.p, 4, hipMemcpyDeviceToHost, s));
+    GHIP(hipStreamSynchronize(s));                   // (also: `tab` is the caller's)
+    GHIP(hipGetLastError());
     if (NB) { float ms = 0; if (hipEventElapsedTime(&ms, B->ev0, B->ev1) == hipSuccess) out->ms_stitch = ms; else (void)hipGetLastError(); }
     out->n_contigs = C; out->n_bases = NB; out->bases = B->bases.as<u8>(); out->offsets = B->offsets.as<u64>(); out->unitig = B->unitig.as<u64>(); out->err = err;
-    return 0;
+    return hipSuccess;
 }
 
 hipError_t sort_exceptions(ContigBuffers* B, const uint64_t* pos_in, const uint8_t* val_in, uint64_t* pos_out, uint8_t* val_out, uint64_t n, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, pos_in, pos_out, val_in, val_out, (size_t)n, 0, 64, s);
-    if (e != hipSuccess) return e;
-    e = B->tmp.ensure(tb + 256);
-    if (e != hipSuccess) return e;
-    return rocprim::radix_sort_pairs(B->tmp.p, tb, pos_in, pos_out, val_in, val_out, (size_t)n, 0, 64, s);
+    return sort_pairs(B->tmp, pos_in, pos_out, val_in, val_out, (size_t)n, 0, 64, s);
 }

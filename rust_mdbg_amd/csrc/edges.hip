@@ -10,30 +10,14 @@
 //   query_kernel     one thread per (node, key): equal range by binary search, exact (k-1)-mer comparison, orientation
 //                    tests; pass 1 counts, pass 2 writes candidate edges at scanned offsets and records presimp removals
 //   filter / scatter drop candidates whose pair (either direction) was removed, compact in order
-#include <algorithm>
 #include <cstring>
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
 #include "edges.h"
-
-typedef uint8_t u8; typedef uint16_t u16; typedef uint32_t u32; typedef uint64_t u64;
+#include "graph_common.h"
 
 namespace {
 
 constexpr u64 EMPTY64 = ~0ull;
-
-struct Buf {
-    void* p = nullptr; size_t cap = 0;
-    ~Buf() { if (p) mdbg_block_free(p, cap); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) mdbg_block_free(p, cap);
-        p = nullptr; cap = 0;
-        return mdbg_block_alloc(&p, bytes + bytes / 8 + 256, &cap);
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 __device__ inline u64 fmix(u64 x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33; return x; }
 
@@ -169,8 +153,6 @@ __global__ void fill64_kernel(u64* p, u64 n, u64 v) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) p[i] = v;
 }
 
-inline unsigned grid_for(u64 n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 struct EdgeBuffers {
@@ -179,60 +161,49 @@ struct EdgeBuffers {
 EdgeBuffers* edge_buffers_create() { return new EdgeBuffers(); }
 void edge_buffers_destroy(EdgeBuffers* b) { delete b; }
 
-#define EHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t build_edges(EdgeBuffers* B, const EdgeNodes& nd, float presimp, hipStream_t s, EdgeResult* out) {
     memset(out, 0, sizeof *out);
     const u64 n = nd.n, n2x = 2 * n;
     if (n == 0) return hipSuccess;
     // ---- listings, sorted by hash (stable: equal hashes stay in listing order)
-    EHIP(B->lh.ensure(n2x * 8)); EHIP(B->sh.ensure(n2x * 8)); EHIP(B->lv.ensure(n2x * 4)); EHIP(B->sv.ensure(n2x * 4));
+    GHIP(B->lh.ensure(n2x * 8)); GHIP(B->sh.ensure(n2x * 8)); GHIP(B->lv.ensure(n2x * 4)); GHIP(B->sv.ensure(n2x * 4));
     hipLaunchKernelGGL(list_kernel, dim3(grid_for(n2x)), dim3(256), 0, s, nd, B->lh.as<u64>(), B->lv.as<u32>());
-    size_t tb = 0;
-    EHIP(rocprim::radix_sort_pairs(nullptr, tb, B->lh.as<u64>(), B->sh.as<u64>(), B->lv.as<u32>(), B->sv.as<u32>(), (size_t)n2x, 0, 64, s));
-    size_t tb2 = 0, tb3 = 0;
-    EHIP(B->cnt.ensure(n2x * 4)); EHIP(B->amax.ensure(n2x * 2)); EHIP(B->off.ensure(n2x * 8)); EHIP(B->scal.ensure(64));
-    EHIP(rocprim::exclusive_scan(nullptr, tb2, B->cnt.as<u32>(), B->off.as<u64>(), (u64)0, (size_t)n2x, rocprim::plus<u64>(), s));
-    EHIP(B->tmp.ensure(std::max(tb, tb2) + 256));
-    EHIP(rocprim::radix_sort_pairs(B->tmp.p, tb, B->lh.as<u64>(), B->sh.as<u64>(), B->lv.as<u32>(), B->sv.as<u32>(), (size_t)n2x, 0, 64, s));
+    GHIP(sort_pairs(B->tmp, B->lh.as<u64>(), B->sh.as<u64>(), B->lv.as<u32>(), B->sv.as<u32>(), (size_t)n2x, 0, 64, s));
+    GHIP(B->cnt.ensure(n2x * 4)); GHIP(B->amax.ensure(n2x * 2)); GHIP(B->off.ensure(n2x * 8)); GHIP(B->scal.ensure(64));
     // ---- pass 1: candidates per (node, key)
     QueryArgs q; memset(&q, 0, sizeof q);
     q.nd = nd; q.presimp = presimp; q.sh = B->sh.as<u64>(); q.sv = B->sv.as<u32>(); q.n_list = n2x;
     q.cnt = B->cnt.as<u32>(); q.amax = B->amax.as<u16>(); q.off = B->off.as<u64>();
     hipLaunchKernelGGL(query_kernel<false>, dim3(grid_for(n2x)), dim3(256), 0, s, q);
-    EHIP(rocprim::exclusive_scan(B->tmp.p, tb2, B->cnt.as<u32>(), B->off.as<u64>(), (u64)0, (size_t)n2x, rocprim::plus<u64>(), s));
-    u64 last_off = 0; u32 last_cnt = 0;
-    EHIP(hipMemcpyAsync(&last_off, B->off.as<u64>() + (n2x - 1), 8, hipMemcpyDeviceToHost, s));
-    EHIP(hipMemcpyAsync(&last_cnt, B->cnt.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
-    EHIP(hipStreamSynchronize(s));
-    const u64 n_slots = last_off + last_cnt;
+    GHIP(excl_scan(B->tmp, B->cnt.as<u32>(), B->off.as<u64>(), (size_t)n2x, s));
+    ScanLast<u32, u64> slots, kept;
+    GHIP(scan_total(B->cnt.as<u32>(), B->off.as<u64>(), (size_t)n2x, s, &slots));
+    GHIP(hipStreamSynchronize(s));
+    const u64 n_slots = slots.total();
     if (n_slots == 0) return hipSuccess;
     // ---- pass 2: candidate edges at their offsets, presimp removals into a hash set
     u64 set_cap = 1024; while (set_cap < 2 * n_slots + 16) set_cap <<= 1;
-    EHIP(B->s_a.ensure(n_slots * 4)); EHIP(B->s_b.ensure(n_slots * 4)); EHIP(B->s_ov.ensure(n_slots * 4)); EHIP(B->s_o.ensure(n_slots));
-    EHIP(B->keep.ensure(n_slots * 4)); EHIP(B->pos.ensure(n_slots * 8));
+    GHIP(B->s_a.ensure(n_slots * 4)); GHIP(B->s_b.ensure(n_slots * 4)); GHIP(B->s_ov.ensure(n_slots * 4)); GHIP(B->s_o.ensure(n_slots));
+    GHIP(B->keep.ensure(n_slots * 4)); GHIP(B->pos.ensure(n_slots * 8));
     const bool ps = presimp > 0.0f;
-    if (ps) { EHIP(B->set.ensure(set_cap * 8)); hipLaunchKernelGGL(fill64_kernel, dim3(1024), dim3(256), 0, s, B->set.as<u64>(), set_cap, EMPTY64); }
-    EHIP(hipMemsetAsync(B->scal.p, 0, 64, s));
+    if (ps) { GHIP(B->set.ensure(set_cap * 8)); hipLaunchKernelGGL(fill64_kernel, dim3(1024), dim3(256), 0, s, B->set.as<u64>(), set_cap, EMPTY64); }
+    GHIP(hipMemsetAsync(B->scal.p, 0, 64, s));
     q.s_a = B->s_a.as<u32>(); q.s_b = B->s_b.as<u32>(); q.s_ov = B->s_ov.as<u32>(); q.s_o = B->s_o.as<u8>();
     q.set = B->set.as<u64>(); q.set_mask = set_cap - 1; q.n_removed = (unsigned long long*)B->scal.p;
     hipLaunchKernelGGL(query_kernel<true>, dim3(grid_for(n2x)), dim3(256), 0, s, q);
     // ---- filter (either direction removed), compact in order
     hipLaunchKernelGGL(filter_kernel, dim3(grid_for(n_slots)), dim3(256), 0, s, n_slots, q.s_a, q.s_b, q.s_o, q.set, q.set_mask, ps, B->keep.as<u32>());
-    EHIP(rocprim::exclusive_scan(nullptr, tb3, B->keep.as<u32>(), B->pos.as<u64>(), (u64)0, (size_t)n_slots, rocprim::plus<u64>(), s));
-    EHIP(B->tmp.ensure(tb3 + 256));
-    EHIP(rocprim::exclusive_scan(B->tmp.p, tb3, B->keep.as<u32>(), B->pos.as<u64>(), (u64)0, (size_t)n_slots, rocprim::plus<u64>(), s));
-    u64 last_pos = 0, removed = 0; u32 last_keep = 0;
-    EHIP(hipMemcpyAsync(&last_pos, B->pos.as<u64>() + (n_slots - 1), 8, hipMemcpyDeviceToHost, s));
-    EHIP(hipMemcpyAsync(&last_keep, B->keep.as<u32>() + (n_slots - 1), 4, hipMemcpyDeviceToHost, s));
-    EHIP(hipMemcpyAsync(&removed, B->scal.p, 8, hipMemcpyDeviceToHost, s));
-    EHIP(hipStreamSynchronize(s));
-    const u64 n_edges = last_pos + last_keep;
-    EHIP(B->n1.ensure(n_edges * 4 + 4)); EHIP(B->n2.ensure(n_edges * 4 + 4)); EHIP(B->ov.ensure(n_edges * 4 + 4));
-    EHIP(B->o1.ensure(n_edges + 4)); EHIP(B->o2.ensure(n_edges + 4));
+    GHIP(excl_scan(B->tmp, B->keep.as<u32>(), B->pos.as<u64>(), (size_t)n_slots, s));
+    u64 removed = 0;
+    GHIP(scan_total(B->keep.as<u32>(), B->pos.as<u64>(), (size_t)n_slots, s, &kept));
+    GHIP(hipMemcpyAsync(&removed, B->scal.p, 8, hipMemcpyDeviceToHost, s));
+    GHIP(hipStreamSynchronize(s));
+    const u64 n_edges = kept.total();
+    GHIP(B->n1.ensure(n_edges * 4 + 4)); GHIP(B->n2.ensure(n_edges * 4 + 4)); GHIP(B->ov.ensure(n_edges * 4 + 4));
+    GHIP(B->o1.ensure(n_edges + 4)); GHIP(B->o2.ensure(n_edges + 4));
     hipLaunchKernelGGL(scatter_kernel, dim3(grid_for(n_slots)), dim3(256), 0, s, n_slots, B->keep.as<u32>(), B->pos.as<u64>(), q.s_a, q.s_b, q.s_ov, q.s_o,
                        B->n1.as<u32>(), B->o1.as<u8>(), B->n2.as<u32>(), B->o2.as<u8>(), B->ov.as<u32>());
-    EHIP(hipStreamSynchronize(s));
+    GHIP(hipStreamSynchronize(s));
     out->n = n_edges; out->n1 = B->n1.as<u32>(); out->o1 = B->o1.as<u8>(); out->n2 = B->n2.as<u32>(); out->o2 = B->o2.as<u8>();
     out->overlap = B->ov.as<u32>(); out->presimp_removed = removed;
     return hipSuccess;
@@ -240,9 +211,5 @@ hipError_t build_edges(EdgeBuffers* B, const EdgeNodes& nd, float presimp, hipSt
 
 hipError_t sort_segments_u64(EdgeBuffers* B, const uint64_t* keys_in, uint64_t* keys_out, uint64_t n, uint32_t n_segments, const uint32_t* offsets, hipStream_t s) {
     if (!n || !n_segments) return hipSuccess;
-    size_t tb = 0;
-    EHIP(rocprim::segmented_radix_sort_keys(nullptr, tb, keys_in, keys_out, (unsigned int)n, n_segments, offsets, offsets + 1, 0, 64, s));
-    EHIP(B->tmp.ensure(tb + 256));
-    EHIP(rocprim::segmented_radix_sort_keys(B->tmp.p, tb, keys_in, keys_out, (unsigned int)n, n_segments, offsets, offsets + 1, 0, 64, s));
-    return hipSuccess;
+    return sort_segments(B->tmp, keys_in, keys_out, (unsigned)n, n_segments, offsets, 0, 64, s);
 }

@@ -1,5 +1,5 @@
-// simplify.hip — tip clipping and simple-bubble popping on the unitig graph, on the GPU (gfx950).  Included at the end of unitigs.hip: it reads that stage's
-// arrays (sorted arcs, settled ranking, unitig numbers, lengths, abundance sums) and calls its compaction again under a node mask.
+// simplify.hip — tip clipping and simple-bubble popping on the unitig graph, on the GPU (gfx950).  It reads the arrays of the compaction stage (unitigs.hip; shown
+// by unitigs_priv.h: sorted arcs, settled ranking, unitig numbers, lengths, abundance sums) and calls that compaction again under a node mask.
 //
 // The rules are the ones written out in include/mdbg_hip.h (mdbg_graph_simplify): this project's own order-free definition in the spirit of
 // `gfatools asm -t N,L -b L`, NOT gfatools' in-place passes.  A step decides against the graph as it is when the step starts, so every kernel below reads
@@ -17,7 +17,10 @@
 //
 // Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks.  A step that
 // removes nothing is followed by no compaction: the next step decides on the same arrays.
+#include <cstring>
+
 #include "simplify.h"
+#include "unitigs_priv.h"
 
 namespace {
 
@@ -158,37 +161,38 @@ __global__ __launch_bounds__(256) void scatter_kernel(SimpArgs a) {
 
 }  // namespace
 
-int simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
-                     uint64_t* unitigs_removed, uint64_t* nodes_removed, SimplifyInfo* info, hipError_t* herr) {
+hipError_t simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
+                     uint64_t* unitigs_removed, uint64_t* nodes_removed, SimplifyInfo* info, int* broken) {
     memset(info, 0, sizeof *info);
     if (n_steps == 0 || nd.n == 0) {                          // the empty schedule IS the unitig call
-        const int rc = build_unitigs(B, nd, ed, s, out, herr);
-        if (rc == 0 && nd.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed.n ? 1 : 0); }
+        const hipError_t rc = build_unitigs(B, nd, ed, s, out, broken);
+        if (rc == hipSuccess && !*broken && nd.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed.n ? 1 : 0); }
         return rc;
     }
     const u64 n = nd.n;
-    if (n >= (1ull << 30)) return 2;
+    *broken = 0;
+    if (n >= (1ull << 30)) return defect(broken);
     const u32 n2x = (u32)(2 * n);
-    UHIP(B->alive.ensure(n));
-    UHIP(hipMemsetAsync(B->alive.p, 1, n, s));
+    GHIP(B->alive.ensure(n));
+    GHIP(hipMemsetAsync(B->alive.p, 1, n, s));
     u8* alive = B->alive.as<u8>();
     u64 n_alive = n;
     bool stale = true;                                        // the arrays of the last compaction no longer describe the surviving graph
-    auto compact = [&]() -> int {
-        const int rc = build_unitigs_masked(B, nd, ed, alive, n_alive, s, out, herr);
-        if (rc) return rc;
+    auto compact = [&]() -> hipError_t {
+        GHIP(build_unitigs_masked(B, nd, ed, alive, n_alive, s, out, broken));
+        if (*broken) return hipSuccess;
         ++info->n_compactions; info->n_rounds_total += out->n_rounds; info->n_syncs += out->n_rounds + 3 + (ed.n ? 1 : 0);
         stale = false;
-        return 0;
+        return hipSuccess;
     };
     for (uint32_t k = 0; k < n_steps; ++k) {
         unitigs_removed[k] = 0; nodes_removed[k] = 0;
-        if (stale) { const int rc = compact(); if (rc) return rc; }
+        if (stale) { GHIP(compact()); if (*broken) return hipSuccess; }
         const u64 U = out->n_unitigs;
         if (U == 0) continue;
-        UHIP(B->uhead.ensure(n * 4)); UHIP(B->utail.ensure(n * 4)); UHIP(B->att.ensure(n * 4)); UHIP(B->rem.ensure(n)); UHIP(B->owner.ensure((size_t)n2x * 4));
+        GHIP(B->uhead.ensure(n * 4)); GHIP(B->utail.ensure(n * 4)); GHIP(B->att.ensure(n * 4)); GHIP(B->rem.ensure(n)); GHIP(B->owner.ensure((size_t)n2x * 4));
         u32* d_ctr = B->ctr.as<u32>();                        // (the compaction is over: its round counters are free)
-        UHIP(hipMemsetAsync(d_ctr, 0, 8, s));
+        GHIP(hipMemsetAsync(d_ctr, 0, 8, s));
         SimpArgs a; memset(&a, 0, sizeof a);
         a.n2x = n2x; a.U = U; a.n_arcs = B->n_arcs; a.sk = B->skeys.as<u64>(); a.P = B->Pfin; a.prv = B->prv.as<u32>(); a.flag = B->flag.as<u32>(); a.uid = B->uid.as<u32>(); a.cyc = B->cycfin;
         a.offsets = out->offsets; a.length = out->length; a.kc = out->kc_sum; a.circ = out->circular; a.max_nodes = steps[k].max_nodes; a.max_bases = steps[k].max_bases;
@@ -196,30 +200,26 @@ int simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& 
         const unsigned gu = grid_for(U), gv = grid_for(n2x);
         hipLaunchKernelGGL(ends_kernel, dim3(gv), dim3(256), 0, s, a);
         if (steps[k].kind == MDBG_SIMPLIFY_TIPS) {
-            UHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
+            GHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
             hipLaunchKernelGGL(tip_cand_kernel, dim3(gu), dim3(256), 0, s, a);
             hipLaunchKernelGGL(tip_decide_kernel, dim3(gu), dim3(256), 0, s, a);
         } else {
-            UHIP(B->bkey.ensure(n * 8)); UHIP(B->bkey2.ensure(n * 8)); UHIP(B->bval.ensure(n * 4)); UHIP(B->bval2.ensure(n * 4));
+            GHIP(B->bkey.ensure(n * 8)); GHIP(B->bkey2.ensure(n * 8)); GHIP(B->bval.ensure(n * 4)); GHIP(B->bval2.ensure(n * 4));
             a.bkey = B->bkey.as<u64>(); a.bval = B->bval.as<u32>(); a.skey = B->bkey2.as<u64>(); a.sval = B->bval2.as<u32>();
             hipLaunchKernelGGL(bubble_key_kernel, dim3(gu), dim3(256), 0, s, a);
-            size_t tb = 0;
-            UHIP(rocprim::radix_sort_pairs(nullptr, tb, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
-            UHIP(B->tmp.ensure(tb + 256));
-            UHIP(rocprim::radix_sort_pairs(B->tmp.p, tb, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
+            GHIP(sort_pairs(B->tmp, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
             hipLaunchKernelGGL(bubble_decide_kernel, dim3(gu), dim3(256), 0, s, a);
         }
         hipLaunchKernelGGL(scatter_kernel, dim3(gv), dim3(256), 0, s, a);
         u32 got[2];
-        UHIP(hipMemcpyAsync(got, d_ctr, 8, hipMemcpyDeviceToHost, s));
-        UHIP(hipStreamSynchronize(s));
+        GHIP(hipMemcpyAsync(got, d_ctr, 8, hipMemcpyDeviceToHost, s));
+        GHIP(hipStreamSynchronize(s));
         ++info->n_syncs;
-        if (got[1] > n_alive || got[0] > U || (got[0] == 0) != (got[1] == 0)) return 2;
+        if (got[1] > n_alive || got[0] > U || (got[0] == 0) != (got[1] == 0)) return defect(broken);
         unitigs_removed[k] = got[0]; nodes_removed[k] = got[1];
         n_alive -= got[1];
         stale = got[1] != 0;
     }
-    if (stale) { const int rc = compact(); if (rc) return rc; }
-    UHIP(hipGetLastError());
-    return 0;
+    if (stale) { GHIP(compact()); if (*broken) return hipSuccess; }
+    return hipGetLastError();
 }

@@ -21,6 +21,6 @@ struct UnitigResult {              // device pointers into UnitigBuffers, valid 
     EdgeResult edges;              // unitig edges (n1 / n2 = 0-based unitig numbers)
     uint32_t n_rounds;             // pointer-jumping rounds this call ran
 };
-// 0 = ok; 1 = HIP failure (*herr); 2 = the jumping did not converge within its bound or an invariant of the walk does not hold (a defect, never the input's fault).
-// Synchronises the stream before returning.
-int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, hipError_t* herr);
+// Returns hipSuccess or the failing HIP error.  *broken <- 1 (with hipSuccess, *out empty) when the jumping did not converge within its bound or an invariant of
+// the walk does not hold (a defect, never the input's fault), else 0.  Synchronises the stream before returning.
+hipError_t build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, int* broken);

@@ -2,7 +2,7 @@
 //
 // Replaces the two tools every documented rust-mdbg run pipes its .gfa through: `gfatools asm -u` (compaction of non-branching paths) and
 // the part of src/to_basespace.rs that decides which piece of which node sequence goes where in a unitig (:132-153, 203-262).  Tip and
-// bubble removal is simplify.hip (included at the end: it decides on this stage's arrays and compacts again under a node mask).  Input: the node table of the last finalize and the edge list of the last edge call, both resident on the device.
+// bubble removal is simplify.hip (a translation unit of its own: it decides on this stage's arrays, which unitigs_priv.h shows it, and compacts again under a node mask).  Input: the node table of the last finalize and the edge list of the last edge call, both resident on the device.
 //
 // Vertex v = 2 * row + (orientation == '-'), comp(v) = v ^ 1; rows are positions in the index-sorted node table, so vertex order is
 // (index, orientation) order.  The arc set is the set of DISTINCT (n1,o1)->(n2,o2) of the edge records plus their mirrors
@@ -22,32 +22,13 @@
 //   emit_kernel      walk entry of every vertex of a kept chain at offset[unitig] + rank, with its copy-plan piece
 //   finish_kernel    dst_offset / LN / abundance sum from two global scans, cut at the unitig boundaries (= a segmented scan)
 //   uedge_*          edge records that are not interior links -> unitig edges, in source order, overlaps clamped (to_basespace.rs:312-320)
-#include <algorithm>
 #include <cstring>
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
-#include "unitigs.h"
-
-typedef uint8_t u8; typedef uint16_t u16; typedef uint32_t u32; typedef uint64_t u64;
+#include "unitigs_priv.h"
 
 namespace {
 
-constexpr u32 NONE = 0xFFFFFFFFu;      // no successor / no link
-constexpr u32 TERM = 0x80000000u;      // on a jump pointer: it names the chain head, the distance is final (vertices are < 2^31)
 enum { C_ERR = 62, C_NONTERM = 63, N_CTR = 64 };      // counters: [round] = vertices not final after that round
-
-struct Buf {
-    void* p = nullptr; size_t cap = 0;
-    ~Buf() { if (p) mdbg_block_free(p, cap); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) mdbg_block_free(p, cap);
-        p = nullptr; cap = 0;
-        return mdbg_block_alloc(&p, bytes + bytes / 8 + 256, &cap);
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 // row of the node with DbgEntry.index == idx (the table is sorted by index); NONE if absent
 __device__ inline u32 row_of(const u32* __restrict__ index, u32 n, u32 idx) {
@@ -91,8 +72,6 @@ __device__ inline u32 link_from(const u32* __restrict__ succ, u32 u) {      // v
     if (v == NONE || (v >> 1) == (u >> 1)) return NONE;
     return succ[v ^ 1] == NONE ? NONE : v;                // in-degree of v = out-degree of comp(v); its only arc is then the mirror of u->v
 }
-
-__device__ inline void count_to(u32* ctr, bool pred) { if (pred) atomicAdd(ctr, 1u); }      // (the compiler folds a wave's adds into one atomic of the active-lane count)
 
 __global__ __launch_bounds__(256) void link_kernel(u32 n2x, const u32* __restrict__ succ, u32* __restrict__ nxt, u32* __restrict__ prv, u32* __restrict__ P, u32* __restrict__ D,
                                                    u32* __restrict__ M, u32* __restrict__ ctr) {
@@ -219,67 +198,41 @@ __global__ __launch_bounds__(256) void uedge_kernel(UedgeArgs a) {
     a.n1[d] = a1; a.o1[d] = m1 ? '-' : '+'; a.n2[d] = a2; a.o2[d] = m2 ? '-' : '+'; a.ov[d] = (u32)ov;
 }
 
-inline unsigned grid_for(u64 n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
-struct UnitigBuffers {
-    Buf keys, skeys, eu, ev, succ, nxt, prv, P[2], D[2], M[2], cyc, flag, hlen, uid, hoff, ctr, tmp;
-    Buf offsets, node, ori, src_read, src_begin, len, rc, dst, ent_u, pl64, ab64, gs, ga, length, kc, circ;
-    Buf ekeep, epos, un1, un2, uov, uo1, uo2;
-    // what the last build_unitigs left for simplify.hip: the settled ranking (one of P[] / D[]), the cycle marks (or null) and the number of sorted arcs in skeys
-    const u32* Pfin = nullptr; const u32* Dfin = nullptr; const u8* cycfin = nullptr; u64 n_arcs = 0;
-    Buf alive, uhead, utail, att, owner, rem, bkey, bkey2, bval, bval2;      // simplify.hip
-};
 UnitigBuffers* unitig_buffers_create() { return new UnitigBuffers(); }
 void unitig_buffers_destroy(UnitigBuffers* b) { delete b; }
 
-#define UHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *herr = e_; return 1; } } while (0)
-
-template <class In, class Out>
-static hipError_t excl_scan(UnitigBuffers* B, const In* in, Out* out, size_t n, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (Out)0, n, rocprim::plus<Out>(), s);
-    if (e != hipSuccess) return e;
-    e = B->tmp.ensure(tb + 256);
-    if (e != hipSuccess) return e;
-    return rocprim::exclusive_scan(B->tmp.p, tb, in, out, (Out)0, n, rocprim::plus<Out>(), s);
-}
-
-// alive (device, one byte per row of the node table; null = every node) restricts the graph to the surviving nodes and the arcs between them; n_alive = how many
-static int build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, hipError_t* herr) {
+hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, int* broken) {
     memset(out, 0, sizeof *out);
-    *herr = hipSuccess;
+    *broken = 0;
     const u64 n = nd.n, E = ed.n;
-    if (n == 0 || (alive && n_alive == 0)) return 0;
-    if (n >= (1ull << 30) || E >= (1ull << 31)) return 2;
+    if (n == 0 || (alive && n_alive == 0)) return hipSuccess;
+    if (n >= (1ull << 30) || E >= (1ull << 31)) return defect(broken);
     const u32 n2x = (u32)(2 * n);
     const unsigned gv = grid_for(n2x);
     u32 ctr[N_CTR];
-    UHIP(B->ctr.ensure(N_CTR * 4));
-    UHIP(hipMemsetAsync(B->ctr.p, 0, N_CTR * 4, s));
+    GHIP(B->ctr.ensure(N_CTR * 4));
+    GHIP(hipMemsetAsync(B->ctr.p, 0, N_CTR * 4, s));
     u32* d_ctr = B->ctr.as<u32>();
     // ---- arcs of the edge records and their mirrors, sorted by (source, target); unique successor per vertex
-    UHIP(B->succ.ensure((size_t)n2x * 4));
-    UHIP(hipMemsetAsync(B->succ.p, 0xFF, (size_t)n2x * 4, s));
-    UHIP(B->eu.ensure(E * 4 + 4)); UHIP(B->ev.ensure(E * 4 + 4));
+    GHIP(B->succ.ensure((size_t)n2x * 4));
+    GHIP(hipMemsetAsync(B->succ.p, 0xFF, (size_t)n2x * 4, s));
+    GHIP(B->eu.ensure(E * 4 + 4)); GHIP(B->ev.ensure(E * 4 + 4));
     if (E) {
-        UHIP(B->keys.ensure(2 * E * 8)); UHIP(B->skeys.ensure(2 * E * 8));
+        GHIP(B->keys.ensure(2 * E * 8)); GHIP(B->skeys.ensure(2 * E * 8));
         hipLaunchKernelGGL(arc_kernel, dim3(grid_for(E)), dim3(256), 0, s, E, ed.n1, ed.o1, ed.n2, ed.o2, nd.index, (u32)n, alive, B->eu.as<u32>(), B->ev.as<u32>(), B->keys.as<u64>(), d_ctr);
         unsigned end_bit = 33; while (end_bit < 64 && (1ull << (end_bit - 32)) < (u64)n2x + (alive ? 1 : 0)) ++end_bit;      // (masked: the source 2n occurs)
-        size_t tb = 0;
-        UHIP(rocprim::radix_sort_keys(nullptr, tb, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
-        UHIP(B->tmp.ensure(tb + 256));
-        UHIP(rocprim::radix_sort_keys(B->tmp.p, tb, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
+        GHIP(sort_keys(B->tmp, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
         hipLaunchKernelGGL(succ_kernel, dim3(grid_for(2 * E)), dim3(256), 0, s, 2 * E, n2x, B->skeys.as<u64>(), B->succ.as<u32>());
     }
     // ---- links, start state of the ranking
-    UHIP(B->nxt.ensure((size_t)n2x * 4)); UHIP(B->prv.ensure((size_t)n2x * 4));
-    for (int i = 0; i < 2; ++i) { UHIP(B->P[i].ensure((size_t)n2x * 4)); UHIP(B->D[i].ensure((size_t)n2x * 4)); UHIP(B->M[i].ensure((size_t)n2x * 4)); }
+    GHIP(B->nxt.ensure((size_t)n2x * 4)); GHIP(B->prv.ensure((size_t)n2x * 4));
+    for (int i = 0; i < 2; ++i) { GHIP(B->P[i].ensure((size_t)n2x * 4)); GHIP(B->D[i].ensure((size_t)n2x * 4)); GHIP(B->M[i].ensure((size_t)n2x * 4)); }
     hipLaunchKernelGGL(link_kernel, dim3(gv), dim3(256), 0, s, n2x, B->succ.as<u32>(), B->nxt.as<u32>(), B->prv.as<u32>(), B->P[0].as<u32>(), B->D[0].as<u32>(), B->M[0].as<u32>(), d_ctr);
-    UHIP(hipMemcpyAsync(ctr, d_ctr, N_CTR * 4, hipMemcpyDeviceToHost, s));
-    UHIP(hipStreamSynchronize(s));
-    if (ctr[C_ERR]) return 2;
+    GHIP(hipMemcpyAsync(ctr, d_ctr, N_CTR * 4, hipMemcpyDeviceToHost, s));
+    GHIP(hipStreamSynchronize(s));
+    if (ctr[C_ERR]) return defect(broken);
     // ---- pointer jumping: paths first; what stays open lies on cycles
     u32 bound = 1; while ((1ull << (bound - 1)) < n2x) ++bound;      // ceil(log2(2n)) + 1
     u32 open = ctr[C_NONTERM], rounds = 0; int cur = 0;
@@ -294,83 +247,77 @@ static int build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const E
         return e;
     };
     while (open) {
-        if (rounds >= bound) return 2;
-        UHIP(jump());
+        if (rounds >= bound) return defect(broken);
+        GHIP(jump());
         if (ctr[0] == open) { cycles = true; break; }      // a round that settles nothing: no path vertex is left
         open = ctr[0];
     }
     if (cycles) {
-        while ((1ull << rounds) < open) { if (rounds >= bound) return 2; UHIP(jump()); if (ctr[0] != open) return 2; }      // span minimum over whole cycles
-        UHIP(B->cyc.ensure(n2x));
-        UHIP(hipMemsetAsync(B->cyc.p, 0, n2x, s));
+        while ((1ull << rounds) < open) { if (rounds >= bound) return defect(broken); GHIP(jump()); if (ctr[0] != open) return defect(broken); }      // span minimum over whole cycles
+        GHIP(B->cyc.ensure(n2x));
+        GHIP(hipMemsetAsync(B->cyc.p, 0, n2x, s));
         hipLaunchKernelGGL(cut_kernel, dim3(gv), dim3(256), 0, s, n2x, B->prv.as<u32>(), B->P[cur].as<u32>(), B->D[cur].as<u32>(), B->M[cur].as<u32>(), B->cyc.as<u8>());
-        UHIP(hipMemsetAsync(d_ctr, 0, C_ERR * 4, s));
+        GHIP(hipMemsetAsync(d_ctr, 0, C_ERR * 4, s));
         const u32 bound2 = rounds + bound;
         while (open) {
-            if (rounds >= bound2) return 2;
-            UHIP(jump());
-            if (ctr[0] >= open) return 2;                  // every cycle has a head now: each round must settle something
+            if (rounds >= bound2) return defect(broken);
+            GHIP(jump());
+            if (ctr[0] >= open) return defect(broken);                  // every cycle has a head now: each round must settle something
             open = ctr[0];
         }
     }
     const u32* P = B->P[cur].as<u32>(); const u32* D = B->D[cur].as<u32>();
     const u8* cyc = cycles ? B->cyc.as<u8>() : nullptr;
     // ---- kept heads -> unitig numbers (vertex order = order of the first node's index) and entry offsets
-    UHIP(B->flag.ensure((size_t)n2x * 4)); UHIP(B->hlen.ensure((size_t)n2x * 4)); UHIP(B->uid.ensure((size_t)n2x * 4)); UHIP(B->hoff.ensure((size_t)n2x * 4));
+    GHIP(B->flag.ensure((size_t)n2x * 4)); GHIP(B->hlen.ensure((size_t)n2x * 4)); GHIP(B->uid.ensure((size_t)n2x * 4)); GHIP(B->hoff.ensure((size_t)n2x * 4));
     hipLaunchKernelGGL(head_kernel, dim3(gv), dim3(256), 0, s, n2x, P, D, B->prv.as<u32>(), cyc, alive, B->flag.as<u32>(), B->hlen.as<u32>());
-    UHIP(excl_scan(B, B->flag.as<u32>(), B->uid.as<u32>(), n2x, s));
-    UHIP(excl_scan(B, B->hlen.as<u32>(), B->hoff.as<u32>(), n2x, s));
-    u32 last[4];
-    UHIP(hipMemcpyAsync(&last[0], B->flag.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
-    UHIP(hipMemcpyAsync(&last[1], B->uid.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
-    UHIP(hipMemcpyAsync(&last[2], B->hlen.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
-    UHIP(hipMemcpyAsync(&last[3], B->hoff.as<u32>() + (n2x - 1), 4, hipMemcpyDeviceToHost, s));
-    UHIP(hipStreamSynchronize(s));
-    const u64 U = (u64)last[0] + last[1], n_entries = (u64)last[2] + last[3];
-    if (n_entries != (alive ? n_alive : n) || U == 0 || U > n_entries) return 2;       // every (surviving) node lies on exactly one unitig
+    GHIP(excl_scan(B->tmp, B->flag.as<u32>(), B->uid.as<u32>(), n2x, s));
+    GHIP(excl_scan(B->tmp, B->hlen.as<u32>(), B->hoff.as<u32>(), n2x, s));
+    ScanLast<u32, u32> heads, entries, uedges;
+    GHIP(scan_total(B->flag.as<u32>(), B->uid.as<u32>(), n2x, s, &heads));
+    GHIP(scan_total(B->hlen.as<u32>(), B->hoff.as<u32>(), n2x, s, &entries));
+    GHIP(hipStreamSynchronize(s));
+    const u64 U = heads.total(), n_entries = entries.total();
+    if (n_entries != (alive ? n_alive : n) || U == 0 || U > n_entries) return defect(broken);       // every (surviving) node lies on exactly one unitig
     // ---- walks and copy plan
-    UHIP(B->offsets.ensure((U + 1) * 8)); UHIP(B->circ.ensure(U)); UHIP(B->length.ensure(U * 8)); UHIP(B->kc.ensure(U * 8));
-    UHIP(B->node.ensure(n * 4)); UHIP(B->ori.ensure(n)); UHIP(B->src_read.ensure(n * 8)); UHIP(B->src_begin.ensure(n * 8)); UHIP(B->len.ensure(n * 4)); UHIP(B->rc.ensure(n));
-    UHIP(B->dst.ensure(n * 8)); UHIP(B->ent_u.ensure(n * 4)); UHIP(B->pl64.ensure((n + 1) * 8)); UHIP(B->ab64.ensure((n + 1) * 8)); UHIP(B->gs.ensure((n + 1) * 8)); UHIP(B->ga.ensure((n + 1) * 8));
+    GHIP(B->offsets.ensure((U + 1) * 8)); GHIP(B->circ.ensure(U)); GHIP(B->length.ensure(U * 8)); GHIP(B->kc.ensure(U * 8));
+    GHIP(B->node.ensure(n * 4)); GHIP(B->ori.ensure(n)); GHIP(B->src_read.ensure(n * 8)); GHIP(B->src_begin.ensure(n * 8)); GHIP(B->len.ensure(n * 4)); GHIP(B->rc.ensure(n));
+    GHIP(B->dst.ensure(n * 8)); GHIP(B->ent_u.ensure(n * 4)); GHIP(B->pl64.ensure((n + 1) * 8)); GHIP(B->ab64.ensure((n + 1) * 8)); GHIP(B->gs.ensure((n + 1) * 8)); GHIP(B->ga.ensure((n + 1) * 8));
     EmitArgs ea; memset(&ea, 0, sizeof ea);
     ea.nd = nd; ea.n2x = n2x; ea.n_unitigs = U; ea.n_entries = n_entries; ea.P = P; ea.D = D; ea.flag = B->flag.as<u32>(); ea.uid = B->uid.as<u32>(); ea.hoff = B->hoff.as<u32>(); ea.cyc = cyc;
     ea.offsets = B->offsets.as<u64>(); ea.circular = B->circ.as<u8>(); ea.node = B->node.as<u32>(); ea.ori = B->ori.as<u8>(); ea.src_read = B->src_read.as<u64>();
     ea.src_begin = B->src_begin.as<u64>(); ea.len = B->len.as<u32>(); ea.rc = B->rc.as<u8>(); ea.ent_u = B->ent_u.as<u32>(); ea.pl64 = B->pl64.as<u64>(); ea.ab64 = B->ab64.as<u64>();
     hipLaunchKernelGGL(emit_kernel, dim3(gv), dim3(256), 0, s, ea);
-    UHIP(excl_scan(B, B->pl64.as<u64>(), B->gs.as<u64>(), (size_t)(n_entries + 1), s));
-    UHIP(excl_scan(B, B->ab64.as<u64>(), B->ga.as<u64>(), (size_t)(n_entries + 1), s));
+    GHIP(excl_scan(B->tmp, B->pl64.as<u64>(), B->gs.as<u64>(), (size_t)(n_entries + 1), s));
+    GHIP(excl_scan(B->tmp, B->ab64.as<u64>(), B->ga.as<u64>(), (size_t)(n_entries + 1), s));
     hipLaunchKernelGGL(finish_kernel, dim3(grid_for(n)), dim3(256), 0, s, n_entries, U, B->offsets.as<u64>(), B->ent_u.as<u32>(), B->gs.as<u64>(), B->ga.as<u64>(), B->dst.as<u64>(),
                        B->length.as<u64>(), B->kc.as<u64>());
     // ---- unitig edges: every edge record that is not an interior link, in source order
     u64 UE = 0;
     if (E) {
-        UHIP(B->ekeep.ensure(E * 4)); UHIP(B->epos.ensure(E * 4));
+        GHIP(B->ekeep.ensure(E * 4)); GHIP(B->epos.ensure(E * 4));
         UedgeArgs ua; memset(&ua, 0, sizeof ua);
         ua.n_edges = E; ua.eu = B->eu.as<u32>(); ua.ev = B->ev.as<u32>(); ua.ov_in = ed.overlap; ua.nxt = B->nxt.as<u32>(); ua.P = P; ua.flag = B->flag.as<u32>(); ua.uid = B->uid.as<u32>();
         ua.length = B->length.as<u64>(); ua.keep = B->ekeep.as<u32>(); ua.pos = B->epos.as<u32>();
         hipLaunchKernelGGL(uedge_kernel<false>, dim3(grid_for(E)), dim3(256), 0, s, ua);
-        UHIP(excl_scan(B, B->ekeep.as<u32>(), B->epos.as<u32>(), (size_t)E, s));
-        u32 le[2];
-        UHIP(hipMemcpyAsync(&le[0], B->ekeep.as<u32>() + (E - 1), 4, hipMemcpyDeviceToHost, s));
-        UHIP(hipMemcpyAsync(&le[1], B->epos.as<u32>() + (E - 1), 4, hipMemcpyDeviceToHost, s));
-        UHIP(hipStreamSynchronize(s));
-        UE = (u64)le[0] + le[1];
-        UHIP(B->un1.ensure(UE * 4 + 4)); UHIP(B->un2.ensure(UE * 4 + 4)); UHIP(B->uov.ensure(UE * 4 + 4)); UHIP(B->uo1.ensure(UE + 4)); UHIP(B->uo2.ensure(UE + 4));
+        GHIP(excl_scan(B->tmp, B->ekeep.as<u32>(), B->epos.as<u32>(), (size_t)E, s));
+        GHIP(scan_total(B->ekeep.as<u32>(), B->epos.as<u32>(), (size_t)E, s, &uedges));
+        GHIP(hipStreamSynchronize(s));
+        UE = uedges.total();
+        GHIP(B->un1.ensure(UE * 4 + 4)); GHIP(B->un2.ensure(UE * 4 + 4)); GHIP(B->uov.ensure(UE * 4 + 4)); GHIP(B->uo1.ensure(UE + 4)); GHIP(B->uo2.ensure(UE + 4));
         ua.n1 = B->un1.as<u32>(); ua.o1 = B->uo1.as<u8>(); ua.n2 = B->un2.as<u32>(); ua.o2 = B->uo2.as<u8>(); ua.ov = B->uov.as<u32>();
         if (UE) hipLaunchKernelGGL(uedge_kernel<true>, dim3(grid_for(E)), dim3(256), 0, s, ua);
     }
-    UHIP(hipStreamSynchronize(s));
-    UHIP(hipGetLastError());
+    GHIP(hipStreamSynchronize(s));
+    GHIP(hipGetLastError());
     B->Pfin = P; B->Dfin = D; B->cycfin = cyc; B->n_arcs = 2 * E;
     out->n_unitigs = U; out->n_entries = n_entries; out->offsets = B->offsets.as<u64>(); out->node = B->node.as<u32>(); out->ori = B->ori.as<u8>();
     out->src_read = B->src_read.as<u64>(); out->src_begin = B->src_begin.as<u64>(); out->len = B->len.as<u32>(); out->revcomp = B->rc.as<u8>(); out->dst_offset = B->dst.as<u64>();
     out->length = B->length.as<u64>(); out->kc_sum = B->kc.as<u64>(); out->circular = B->circ.as<u8>(); out->n_rounds = rounds;
     out->edges.n = UE; out->edges.n1 = B->un1.as<u32>(); out->edges.o1 = B->uo1.as<u8>(); out->edges.n2 = B->un2.as<u32>(); out->edges.o2 = B->uo2.as<u8>(); out->edges.overlap = B->uov.as<u32>();
-    return 0;
+    return hipSuccess;
 }
 
-int build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, hipError_t* herr) {
-    return build_unitigs_masked(B, nd, ed, nullptr, 0, s, out, herr);
+hipError_t build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, int* broken) {
+    return build_unitigs_masked(B, nd, ed, nullptr, 0, s, out, broken);
 }
-
-#include "simplify.hip"

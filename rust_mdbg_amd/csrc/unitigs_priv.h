@@ -1,0 +1,29 @@
+// unitigs_priv.h — what the compaction (unitigs.hip) shows the simplification stage (simplify.hip): its buffers, its vertex codes and the masked compaction.
+// Included by those two translation units only.
+#pragma once
+#include "graph_common.h"
+#include "unitigs.h"
+
+namespace {
+
+constexpr u32 NONE = 0xFFFFFFFFu;      // no successor / no link
+constexpr u32 TERM = 0x80000000u;      // on a jump pointer: it names the chain head, the distance is final (vertices are < 2^31)
+
+__device__ inline void count_to(u32* ctr, bool pred) { if (pred) atomicAdd(ctr, 1u); }      // (the compiler folds a wave's adds into one atomic of the active-lane count)
+
+inline hipError_t defect(int* broken) { *broken = 1; return hipSuccess; }      // the `broken` outcome of unitigs.h
+
+}  // namespace
+
+struct UnitigBuffers {
+    Buf keys, skeys, eu, ev, succ, nxt, prv, P[2], D[2], M[2], cyc, flag, hlen, uid, hoff, ctr, tmp;
+    Buf offsets, node, ori, src_read, src_begin, len, rc, dst, ent_u, pl64, ab64, gs, ga, length, kc, circ;
+    Buf ekeep, epos, un1, un2, uov, uo1, uo2;
+    // what the last build_unitigs left for simplify.hip: the settled ranking (one of P[] / D[]), the cycle marks (or null) and the number of sorted arcs in skeys
+    const u32* Pfin = nullptr; const u32* Dfin = nullptr; const u8* cycfin = nullptr; u64 n_arcs = 0;
+    Buf alive, uhead, utail, att, owner, rem, bkey, bkey2, bval, bval2;      // simplify.hip
+};
+
+// build_unitigs restricted by `alive` (device, one byte per row of the node table; null = every node) to the surviving nodes and the arcs between them; n_alive = how many
+// (not part of the library's surface: hidden, as it was while it was static)
+__attribute__((visibility("hidden"))) hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, int* broken);
