@@ -10,7 +10,7 @@ static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_h
     if (!(presimp >= 0.0f)) return fail(c, MDBG_E_PARAM, "presimp must be >= 0");
     memset(out, 0, sizeof *out);
     if (!c->nodes_ok && !(c->cap == 0 || c->M == 0)) return fail(c, MDBG_E_STATE, "no finalized node table on this context (call mdbg_finalize / mdbg_finalize_device first)");
-    c->edges_ok = false; c->last_edges = EdgeResult{}; c->ulist_ok = false;
+    invalidate_results(c, FROM_EDGES); c->last_edges = EdgeResult{};
     if (!c->nodes_ok || c->nodes_n == 0) { c->edges_ok = c->nodes_ok; return MDBG_OK; }
     if (c->nodes_n >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
     if (!c->eb) c->eb = edge_buffers_create();
@@ -45,7 +45,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
         c->hs_unitigs.assign(n_steps, 0); c->hs_nodes.assign(n_steps, 0);
         stats->n_steps = n_steps; stats->unitigs_removed = c->hs_unitigs.data(); stats->nodes_removed = c->hs_nodes.data();
     }
-    c->ulist_ok = false; c->last_ul = UnitigResult{};
+    invalidate_results(c, FROM_UNITIGS); c->last_ul = UnitigResult{};
     if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "unitigs are single-GPU only: not available on a routed or partitioned context");
     if (c->cap == 0 || c->M == 0) { c->ulist_ok = true; return MDBG_OK; }      // empty context: empty list
     if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
