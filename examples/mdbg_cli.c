@@ -4,6 +4,8 @@
  *   `gfatools asm -u` + to_basespace + gfa2fasta.sh; no tip or bubble removal)
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
+ *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
+ *   mdbg_seqfile_write_nodes) instead of in a second pass over the input; the same lines per file, in row order
  * Same flags as the reference binary for this path (src/main.rs:330-420): -k -l --density --minabund --presimp --prefix --threads
  * --reference --skiphpc --syncmers/-s --lmer-counts/--lmer_counts_min/--lmer_counts_max --no-basespace; --contigs is this host's own.
  * --threads N > 1: an uncompressed input is mapped and parsed by N threads (mdbg_reader_open_mt) that also pack their pieces to 2 bits
@@ -64,6 +66,14 @@ static void* seqjob_main(void* arg) {
     return NULL;
 }
 
+/* one writer of the kept-reads path: the lines of the rows i with i % n_parts == part of the current chunk of node sequences */
+typedef struct nodejob_t { mdbg_seqfile* sf; const mdbg_nodes* nodes; uint32_t part, n_parts; const mdbg_node_seqs* chunk; int rc; } nodejob_t;
+static void* nodejob_main(void* arg) {
+    nodejob_t* j = (nodejob_t*)arg;
+    j->rc = mdbg_seqfile_write_nodes(j->sf, j->nodes, j->part, j->n_parts, j->chunk->first_row, j->chunk->n_rows, j->chunk->bases, j->chunk->offsets);
+    return NULL;
+}
+
 static void die(mdbg_ctx* ctx, const char* what, int rc) {
     fprintf(stderr, "%s: %s (%s)\n", what, mdbg_strerror(rc), ctx && mdbg_last_error(ctx) ? mdbg_last_error(ctx) : "");
     exit(1);
@@ -73,7 +83,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L append steps of their own, in command-line order */
@@ -98,6 +108,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--timing")) timing = 1;
         else if (!strcmp(argv[i], "--contigs")) contigs = 1;
         else if (!strcmp(argv[i], "--keep-reads")) keep_reads = 1;
+        else if (!strcmp(argv[i], "--sequences-from-kept")) seq_kept = 1;
         else if (!strcmp(argv[i], "--simplify")) {
             simplify = 1;
             for (uint32_t j = 0; j < sizeof magic / sizeof magic[0] && n_steps < MAX_STEPS; ++j) steps[n_steps++] = magic[j];
@@ -117,11 +128,12 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--keep-reads] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
     if (simplify) contigs = 1;
     if (!contigs) keep_reads = 0;
-    if (keep_reads) p.flags |= MDBG_FLAG_KEEP_READS;
+    if (!write_sequences) seq_kept = 0;
+    if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
 
     int err = 0;
     mdbg_ctx* ctx = mdbg_create(&p, &err);
@@ -192,6 +204,37 @@ int main(int argc, char** argv) {
     if (rc) die(NULL, "mdbg_emit_write_gfa", rc);
     if (timing) fprintf(stderr, "timing: %llu reads, %llu bases; ingest %.3f s, to .gfa %.3f s (%.2f Gbases/s; context creation not included); ingest loop: waiting for the reader %.3f, mdbg_ingest_batch_packed %.3f s\n",
                         (unsigned long long)n_reads, (unsigned long long)n_bases, t_ingest - t0, now_s() - t0, (double)n_bases / (now_s() - t0) / 1e9, t_wait, t_gpu);
+    if (seq_kept) {                                                 /* the node sequences from the device store, chunk by chunk, while the node table is current */
+        enum { MAX_KEPT_WRITERS = 16 };
+        const int nw = threads > MAX_KEPT_WRITERS ? MAX_KEPT_WRITERS : threads;
+        mdbg_seqfile* sf[MAX_KEPT_WRITERS]; nodejob_t job[MAX_KEPT_WRITERS]; pthread_t th[MAX_KEPT_WRITERS];
+        const double ts = now_s();
+        double ms_gather = 0; uint64_t n_chunks = 0, n_seq_bases = 0;
+        for (int t = 0; t < nw; ++t) {
+            snprintf(path, sizeof path, "%s.%d.sequences", prefix, t);
+            sf[t] = mdbg_seqfile_open(path, p.k, p.l, &err);
+            if (!sf[t]) die(NULL, "mdbg_seqfile_open", err);
+        }
+        for (uint64_t row = 0;;) {
+            mdbg_node_seqs ch; double ms = 0;
+            rc = mdbg_graph_node_seqs(ctx, row, 0, 256u << 20, &ch);
+            if (rc) die(ctx, "mdbg_graph_node_seqs", rc);
+            if (!ch.n_rows) break;
+            mdbg_node_seqs_ms(ctx, &ms); ms_gather += ms; ++n_chunks; n_seq_bases += ch.n_bases;
+            for (int t = 0; t < nw; ++t) {
+                nodejob_t jb; jb.sf = sf[t]; jb.nodes = &nodes; jb.part = (uint32_t)t; jb.n_parts = (uint32_t)nw; jb.chunk = &ch; jb.rc = 0;
+                job[t] = jb;
+                if (t) pthread_create(&th[t], NULL, nodejob_main, &job[t]);
+            }
+            nodejob_main(&job[0]);
+            for (int t = 1; t < nw; ++t) pthread_join(th[t], NULL);
+            for (int t = 0; t < nw; ++t) if (job[t].rc) die(NULL, "mdbg_seqfile_write_nodes", job[t].rc);
+            row += ch.n_rows;
+        }
+        for (int t = 0; t < nw; ++t) { rc = mdbg_seqfile_close(sf[t]); if (rc) die(NULL, "mdbg_seqfile_close", rc); }
+        if (timing) fprintf(stderr, "timing: .sequences from the kept reads %.3f s (%d file%s; %llu chunks, %llu bases, gather kernel %.3f ms)\n", now_s() - ts, nw, nw > 1 ? "s" : "",
+                            (unsigned long long)n_chunks, (unsigned long long)n_seq_bases, ms_gather);
+    }
     mdbg_contigs* ctg = NULL; mdbg_contigs* sctg = NULL;
     if (simplify) {                                                 /* tips and simple bubbles removed on the GPU (this project's own rules, not gfatools parity: mdbg_hip.h) */
         mdbg_unitig_list sl; mdbg_simplify_stats ss;
@@ -227,10 +270,10 @@ int main(int argc, char** argv) {
             if (rc) die(NULL, "mdbg_emit_contigs_set_sequences", rc);
         }
     }
-    if (write_sequences || (ctg && !keep_reads)) {                                   /* second pass over the input: the node sequences, the contigs' bases */
+    if ((write_sequences && !seq_kept) || (ctg && !keep_reads)) {                                   /* second pass over the input: the node sequences, the contigs' bases */
         /* one file per writer thread, "<prefix>.<t>.sequences", as the reference's worker threads write them (main.rs:614-630) */
         enum { MAX_WRITERS = 16 };
-        const int nw = !write_sequences ? 0 : threads > MAX_WRITERS ? MAX_WRITERS : threads;
+        const int nw = !write_sequences || seq_kept ? 0 : threads > MAX_WRITERS ? MAX_WRITERS : threads;
         mdbg_seqfile* sf[MAX_WRITERS]; seqjob_t job[MAX_WRITERS]; pthread_t th[MAX_WRITERS];
         for (int t = 0; t < nw; ++t) {
             snprintf(path, sizeof path, "%s.%d.sequences", prefix, t);

@@ -43,6 +43,16 @@ int mdbg_seqfile_write_batch(mdbg_seqfile* f, const mdbg_nodes* nodes, const uin
  * calling this with its own file and part on the same batch, give the same set of lines in parallel. */
 int mdbg_seqfile_write_batch_part(mdbg_seqfile* f, const mdbg_nodes* nodes, uint32_t part, uint32_t n_parts, const uint8_t* bases,
                                   const uint64_t* offsets, uint64_t n_reads, uint64_t first_read_ordinal);
+/* The same lines from READY sequences instead of reads: a chunk of mdbg_graph_node_seqs (mdbg_hip.h, HOST arrays) — rows [first_row, first_row + n_rows) of
+ * `nodes`, the sequence of row i being bases[offsets[i - first_row] .. offsets[i - first_row + 1]), already oriented, so it is printed as it is (no reverse
+ * complement on the host).  Writes the lines of the rows i with i % n_parts == part (part 0 of 1: all of them); line format and block flushing are those of
+ * mdbg_seqfile_write_batch.  MDBG_E_PARAM if a row's byte count differs from src_end - src_start, the chunk does not lie inside the table, or a column is
+ * missing (a table of mdbg_finalize_gfa).  No second pass over the input is needed: a context that keeps its reads serves every chunk from device memory.
+ * ORDER: fed chunk after chunk, the lines come out in ROW order.  The batch writers above print, per batch fed, the rows whose source read lies in that
+ * batch, so their file is ordered by the batch of the source read first and by row second: both hold the same lines, and they are byte-identical when the
+ * batch writer is fed the whole input as one batch.  (The reference writes in hash-map order and its readers key by node name: no reader depends on the order.) */
+int mdbg_seqfile_write_nodes(mdbg_seqfile* f, const mdbg_nodes* nodes, uint32_t part, uint32_t n_parts, uint64_t first_row, uint64_t n_rows,
+                             const uint8_t* bases, const uint64_t* offsets);
 int mdbg_seqfile_close(mdbg_seqfile* f);
 
 /* ---- host ingest: FASTA / FASTQ, optionally gzip-compressed, into the batch layout of

@@ -58,7 +58,7 @@ enum {
 #define MDBG_MAX_L 255u        /* l = 2..32 run on the bit-sliced kernel, longer l-mers on its generic exact walker (reference: unbounded) */
 #define MDBG_MAX_MINABUND 65535u /* DbgAbundance is a u16 in the reference; up to 8 the table tracks the A-th sighting directly, above it is recovered at finalize */
 #define MDBG_FLAG_FORCE_GENERIC 1u /* every tile takes the generic exact sketch kernel (testing / cross-check) */
-#define MDBG_FLAG_KEEP_READS 2u  /* the context keeps every batch it ingests WITH bases, packed 2 bits per base, in device memory: mdbg_graph_contigs stitches from that store */
+#define MDBG_FLAG_KEEP_READS 2u  /* the context keeps every batch it ingests WITH bases, packed 2 bits per base, in device memory: mdbg_graph_contigs and mdbg_graph_node_seqs gather from that store */
 #define MDBG_SCHEME_DENSITY 0u   /* canonical ntHash <= density * 2^64           Read::extract_density   src/read.rs:176-211 */
 #define MDBG_SCHEME_SYNCMERS 1u  /* --syncmers: open syncmers (smallest s-mer in the middle), down-sampled by hash(l-mer) <= density * 4^l;
                                   * 2-bit codes, A/a C/c G/g T/t/U/u, any other byte resets (no alphabet error); l <= 31
@@ -433,6 +433,31 @@ int mdbg_graph_contigs(mdbg_ctx* ctx, uint64_t min_len, mdbg_contig_seqs* out);
 int mdbg_graph_contigs_device(mdbg_ctx* ctx, uint64_t min_len, mdbg_contig_seqs* out);
 int mdbg_kept_reads(mdbg_ctx* ctx, uint64_t* n_reads, uint64_t* n_bases, uint64_t* bytes);
 int mdbg_contigs_ms(mdbg_ctx* ctx, double* ms);
+
+/* ---- node sequences gathered on the GPU from the kept reads: what the .sequences writer needs, without a second pass over the input ------------
+ * The sequence of row i of the context's CURRENT node table (the table of the last mdbg_finalize* call, in index order; a table of mdbg_finalize_gfa is fine, the
+ * device rows are all there) is bytes [src_start[i], src_end[i]) of read src_read[i], copied as they are if reversed[i] == 0 and otherwise through utils::revcomp
+ * (src/utils.rs:3-24: reversed, N and every byte outside ACGTUacgtu become N) — byte for byte what mdbg_seqfile_write_batch (mdbg_emit.h) prints in a row's line.
+ * The rows of a table overlap heavily (consecutive nodes share k - 1 minimizers), so together they are many times the input: a call hands out a CHUNK, rows
+ * [first_row, first_row + n_rows) with n_rows the largest count <= max_rows whose sequences together are <= max_bases bytes.  At least one row is produced while
+ * first_row < n, so a row longer than the budget comes alone; max_rows = 0 / max_bases = 0: no limit on that side; first_row >= n: MDBG_OK with n_rows = 0,
+ * which ends a caller's loop `first_row += n_rows`.  mdbg_seqfile_write_nodes (mdbg_emit.h) takes a chunk as it is.
+ * mdbg_graph_node_seqs: HOST arrays; mdbg_graph_node_seqs_device: DEVICE arrays (bases 16-byte aligned).  Both belong to the context until its NEXT
+ * NODE-SEQUENCE CALL or mdbg_destroy; they share no memory with the contig result, so a caller may hold a mdbg_graph_contigs result and a chunk at once.
+ * The calls leave the node table, the edge list and the unitig list as they are.  The rows' lengths are summed once per node table, not once per chunk; a call
+ * waits for the device twice at most (the chunk's size, the error flag).
+ * MDBG_E_STATE: a context without MDBG_FLAG_KEEP_READS, a routed / partitioned context (SINGLE GPU ONLY), no current node table (an ingest, rewind or reset call
+ * that followed the finalize ended it), or a resident batch that came without bases; MDBG_E_PARAM: a row outside its read (reported through a flag the kernel
+ * sets; nothing is read out of bounds).  The finalize of a context with nothing resident leaves a table of no rows: MDBG_OK, n_rows = 0.
+ * mdbg_node_seqs_ms: device time of the gather kernel of the last node-sequence call (HIP events; 0 if it produced no bases). */
+typedef struct mdbg_node_seqs {
+    uint64_t first_row, n_rows, n_bases;
+    const uint8_t*  bases;     /* n_bases ASCII bytes, row after row, each already oriented as its .sequences line prints it */
+    const uint64_t* offsets;   /* n_rows + 1, offsets[0] = 0 */
+} mdbg_node_seqs;
+int mdbg_graph_node_seqs(mdbg_ctx* ctx, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out);
+int mdbg_graph_node_seqs_device(mdbg_ctx* ctx, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out);
+int mdbg_node_seqs_ms(mdbg_ctx* ctx, double* ms);
 
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),

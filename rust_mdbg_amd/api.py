@@ -90,6 +90,10 @@ class ContigSeqs(C.Structure):         # mdbg_contig_seqs
                 ("unitig", C.POINTER(C.c_uint64))]
 
 
+class NodeSeqs(C.Structure):           # mdbg_node_seqs
+    _fields_ = [("first_row", C.c_uint64), ("n_rows", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64))]
+
+
 class SimplifyStep(C.Structure):       # mdbg_simplify_step
     _fields_ = [("kind", C.c_uint32), ("max_nodes", C.c_uint32), ("max_bases", C.c_uint64)]
 
@@ -137,7 +141,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
-           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -232,6 +236,9 @@ def load_library():
     L.mdbg_graph_contigs_device.argtypes = [vp, u64, C.POINTER(ContigSeqs)]
     L.mdbg_kept_reads.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mdbg_contigs_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mdbg_graph_node_seqs.argtypes = [vp, u64, u64, u64, C.POINTER(NodeSeqs)]
+    L.mdbg_graph_node_seqs_device.argtypes = [vp, u64, u64, u64, C.POINTER(NodeSeqs)]
+    L.mdbg_node_seqs_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -558,6 +565,31 @@ class Mdbg:
         """device time of the stitch kernel of the last graph_contigs call, in milliseconds"""
         ms = C.c_double()
         self._chk(self.L.mdbg_contigs_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def graph_node_seqs(self, first_row=0, max_rows=0, max_bases=0, device=False, raw=False):
+        """the sequences of rows [first_row, first_row + n_rows) of the current node table (the last finalize*), gathered on the GPU from the kept reads
+        (keep_reads=True): reads[src_read][src_start:src_end], reverse-complemented through utils::revcomp where `reversed` — what a row's .sequences line prints.
+        n_rows is the largest count <= max_rows whose sequences together are <= max_bases bytes (0: no limit; at least one row while first_row < n); a loop
+        `first_row += n_rows` ends at n_rows == 0.
+        -> dict(first_row, n_rows, n_bases, bases u8[n_bases], offsets u64[n_rows + 1]); device=True: the dict holds DEVICE addresses (ints) instead of arrays;
+        raw=True: the NodeSeqs struct with HOST arrays, not copied (Emitter.write_sequences_from_kept).  Either way the buffers are the context's until its
+        next graph_node_seqs call."""
+        ns = NodeSeqs()
+        if device:
+            self._chk(self.L.mdbg_graph_node_seqs_device(self.h, first_row, max_rows, max_bases, C.byref(ns)))
+            return dict(first_row=int(ns.first_row), n_rows=int(ns.n_rows), n_bases=int(ns.n_bases), bases=C.cast(ns.bases, C.c_void_p).value or 0,
+                        offsets=C.cast(ns.offsets, C.c_void_p).value or 0)
+        self._chk(self.L.mdbg_graph_node_seqs(self.h, first_row, max_rows, max_bases, C.byref(ns)))
+        if raw:
+            return ns
+        n = int(ns.n_rows)
+        return dict(first_row=int(ns.first_row), n_rows=n, n_bases=int(ns.n_bases), bases=_np(ns.bases, int(ns.n_bases), np.uint8), offsets=_np(ns.offsets, n + 1, np.uint64))
+
+    def node_seqs_ms(self):
+        """device time of the gather kernel of the last graph_node_seqs call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_node_seqs_ms(self.h, C.byref(ms)))
         return float(ms.value)
 
     def store_reserve(self, n_minimizers_total, n_reads_total):

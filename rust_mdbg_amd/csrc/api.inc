@@ -18,6 +18,7 @@
 #include "unitigs.h"
 #include "simplify.h"
 #include "contigs.h"
+#include "node_seqs.h"
 
 #include "blocks.inc"
 #include "context.inc"
@@ -25,7 +26,7 @@
 #include "ingest_api.inc"
 extern "C" {                   // entry points and their static helpers only from here on
 #include "finalize_api.inc"
-#include "graph_api.inc"      // edges, unitigs, simplification, contigs
+#include "graph_api.inc"      // edges, unitigs, simplification, contigs, node sequences
 #include "import_api.inc"
 }
 #include "route_api.inc"      // multi-GPU routing

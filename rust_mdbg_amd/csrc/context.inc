@@ -105,6 +105,11 @@ struct mdbg_ctx {
     DevBuf kp_exc_pos, kp_exc_val, kp_cnt;   // keeping an ASCII batch: where the pack kernel appends the (unordered) exceptions, and their count
     HostRaw<u8> hc_bases; HostRaw<u64> hc_off, hc_unitig;      // host copy of the last mdbg_graph_contigs
     double ms_stitch = 0;                    // device time of the last stitch kernel
+    NodeSeqBuffers* nsb = nullptr;           // node sequences from the kept reads (node_seqs.hip), created on first use; its result buffers live until the next node-sequence call
+    bool nodes_none = false;                 // the last finalize found nothing resident: its table of no rows is current (ended where nodes_ok is)
+    bool nseq_prefix_ok = false;             // nsb holds the prefix of the rows' lengths of the node table as it stands (dropped wherever nodes_ok is cleared or set)
+    HostRaw<u8> hn_bases; HostRaw<u64> hn_off;      // host copy of the last mdbg_graph_node_seqs chunk
+    double ms_node_seqs = 0;                 // device time of the last node-sequence gather kernel
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -177,7 +182,7 @@ int write_scalar(mdbg_ctx* c, int idx, u64 v) {
 // Which derived results (node table <- edge list <- unitig list) an operation ends, each with all that is built on it: whatever changes the table (insertion, clear,
 // finalize's setup) ends the node table; an edge call the edge list; an ingest the unitig list (mdbg_graph_contigs).  The flags are set where a result is made.
 enum ResultsFrom { FROM_NODES, FROM_EDGES, FROM_UNITIGS };
-void invalidate_results(mdbg_ctx* c, ResultsFrom from) { if (from <= FROM_NODES) c->nodes_ok = false; if (from <= FROM_EDGES) c->edges_ok = false; c->ulist_ok = false; }
+void invalidate_results(mdbg_ctx* c, ResultsFrom from) { if (from <= FROM_NODES) { c->nodes_ok = false; c->nodes_none = false; c->nseq_prefix_ok = false; } if (from <= FROM_EDGES) c->edges_ok = false; c->ulist_ok = false; }
 static void fill_mread_of(mdbg_ctx* c, Batch& b);
 // largest hash a selected minimizer can have (0: unknown)
 double owner_hash_bound(const mdbg_ctx* c) {
@@ -387,6 +392,7 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     if (c->eb) edge_buffers_destroy(c->eb);
     if (c->ub) unitig_buffers_destroy(c->ub);
     if (c->cb) contig_buffers_destroy(c->cb);
+    if (c->nsb) node_seq_buffers_destroy(c->nsb);
     if (c->h_scal) (void)hipHostFree(c->h_scal);
     for (auto& g : c->stage) if (g.st) (void)hipStreamDestroy(g.st);
     if (c->stream) (void)hipStreamDestroy(c->stream);

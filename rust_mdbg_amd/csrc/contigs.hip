@@ -15,10 +15,9 @@
 
 #include "contigs.h"
 #include "graph_common.h"
+#include "kept_gather.h"      // the batch lookup, the 16-code expansion, the exception patch: shared with node_seqs.hip
 
 namespace {
-
-enum { ERR_NOT_KEPT = 1u, ERR_OUTSIDE = 2u };
 
 struct StitchArgs {
     const u64* out_off; const u64* unitig; u64 n_contigs, n_bases;                                    // the produced contigs
@@ -26,19 +25,6 @@ struct StitchArgs {
     const KeptDesc* tab; u32 n_tab;
     u8* out; u32* err;
 };
-
-// src/utils.rs:10-24, as mdbg_emit.cpp's switch_base
-__device__ inline u8 switch_base_dev(u8 c) {
-    switch (c) { case 'a': return 't'; case 'c': return 'g'; case 't': return 'a'; case 'g': return 'c'; case 'u': return 'a';
-                 case 'A': return 'T'; case 'C': return 'G'; case 'T': return 'A'; case 'G': return 'C'; case 'U': return 'A'; default: return 'N'; }
-}
-__device__ inline u8 through_revcomp(u8 c, u32 rc) { return rc == 0 ? c : rc == 1 ? switch_base_dev(c) : switch_base_dev(switch_base_dev(c)); }
-
-// largest i in [lo, hi) with a[i] <= v; the caller knows that hi > lo (a[lo] > v is reported by the caller's own test)
-__device__ inline u64 last_le(const u64* __restrict__ a, u64 lo, u64 hi, u64 v) {
-    while (hi - lo > 1) { const u64 mid = lo + ((hi - lo) >> 1); if (a[mid] <= v) lo = mid; else hi = mid; }
-    return lo;
-}
 
 struct Piece {                     // the plan entry that covers an output position, resolved against the store
     const KeptDesc* d;
@@ -57,31 +43,13 @@ __device__ inline bool piece_of(const StitchArgs& A, u64 g, Piece& P) {
     const u32 n = A.len[e];
     if (d0 > p || p - d0 >= n) return false;
     const u64 r = A.src_read[e];
-    if (A.n_tab == 0 || A.tab[0].first_ordinal > r) { atomicOr(A.err, (u32)ERR_NOT_KEPT); return false; }
-    u32 lo = 0, hi = A.n_tab;
-    while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (A.tab[mid].first_ordinal <= r) lo = mid; else hi = mid; }
-    const KeptDesc* const d = A.tab + lo;
-    const u64 rl = r - d->first_ordinal;
-    if (rl >= d->n_reads) { atomicOr(A.err, (u32)ERR_NOT_KEPT); return false; }
-    const u64 ro = d->offsets[rl], re = d->offsets[rl + 1], b = A.src_begin[e];
-    if (re < ro || re > d->n_words * 32 || b > re - ro || n > re - ro - b) { atomicOr(A.err, (u32)ERR_OUTSIDE); return false; }
-    P.d = d; P.sb = ro + b; P.within = p - d0; P.n = n; P.rc = A.rc[e];
+    const KeptDesc* const d = kept_batch_of(A.tab, A.n_tab, r);
+    if (!d) { atomicOr(A.err, (u32)ERR_NOT_KEPT); return false; }
+    u64 sb;
+    if (!kept_span(d, r, A.src_begin[e], n, &sb)) { atomicOr(A.err, (u32)ERR_OUTSIDE); return false; }
+    P.d = d; P.sb = sb; P.within = p - d0; P.n = n; P.rc = A.rc[e];
     return true;
 }
-// the original byte at position q of a kept batch
-__device__ inline u8 kept_byte(const KeptDesc* d, u64 q) {
-    if (d->n_exc) {
-        const u64* const xp = d->exc_pos;
-        u64 lo = 0, hi = d->n_exc;
-        while (lo < hi) { const u64 mid = lo + ((hi - lo) >> 1); if (xp[mid] < q) lo = mid + 1; else hi = mid; }
-        if (lo < d->n_exc && xp[lo] == q) return d->exc_val[lo];
-    }
-    const uint2 w = d->planes[q >> 5];
-    const u32 b = (u32)q & 31u;
-    const u32 code = ((w.x >> b) & 1u) | (((w.y >> b) & 1u) << 1);
-    return (u8)(0x47544341u >> (8 * code));          // "ACTG"
-}
-
 __global__ __launch_bounds__(256) void stitch_kernel(StitchArgs A) {
     const u64 G = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 16;
     if (G >= A.n_bases) return;
@@ -90,37 +58,7 @@ __global__ __launch_bounds__(256) void stitch_kernel(StitchArgs A) {
     if (have && P.n - P.within >= 16) {                    // the whole group comes from one entry (and so lies inside the output)
         const bool rev = P.rc == 1;
         const u64 qs = rev ? P.sb + P.n - 16 - P.within : P.sb + P.within;      // lowest of the 16 source positions
-        const u64 w = qs >> 5; const u32 b = (u32)qs & 31u;
-        const uint2 w0 = P.d->planes[w];
-        uint2 w1 = make_uint2(0, 0);
-        if (b > 16 && w + 1 < P.d->n_words) w1 = P.d->planes[w + 1];
-        u32 lo = (u32)((((u64)w1.x << 32) | w0.x) >> b) & 0xFFFFu, hi = (u32)((((u64)w1.y << 32) | w0.y) >> b) & 0xFFFFu;
-        if (rev) { lo = __brev(lo) >> 16; hi = (__brev(hi) >> 16) ^ 0xFFFFu; }
-        u32 o[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            u32 v = 0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int j = 4 * q + t;
-                const u32 code = ((lo >> j) & 1u) | (((hi >> j) & 1u) << 1);
-                v |= ((0x47544341u >> (8 * code)) & 0xFFu) << (8 * t);
-            }
-            o[q] = v;
-        }
-        uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
-        if (P.d->n_exc) {                                  // rare: patch the bytes the planes cannot hold
-            const u64* const xp = P.d->exc_pos;
-            u64 i = 0, hi_i = P.d->n_exc;
-            while (i < hi_i) { const u64 mid = i + ((hi_i - i) >> 1); if (xp[mid] < qs) i = mid + 1; else hi_i = mid; }
-            for (; i < P.d->n_exc && xp[i] < qs + 16; ++i) {
-                const u32 j = rev ? 15u - (u32)(xp[i] - qs) : (u32)(xp[i] - qs);
-                const u32 v = through_revcomp(P.d->exc_val[i], P.rc), sh = 8 * (j & 3u), m = ~(0xFFu << sh);
-                const u32 q = j >> 2;
-                if (q == 0) ov.x = (ov.x & m) | (v << sh); else if (q == 1) ov.y = (ov.y & m) | (v << sh);
-                else if (q == 2) ov.z = (ov.z & m) | (v << sh); else ov.w = (ov.w & m) | (v << sh);
-            }
-        }
+        const uint4 ov = kept_group16(P.d, qs, rev, P.rc);
         *(uint4*)(A.out + G) = ov;
         return;
     }

@@ -224,7 +224,7 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
             c->fin_rows_guess = n_solid + n_solid / 4 + 1024;
             if (d_row) *d_row = nullptr;
             out->n = n_solid;
-            invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = true;
+            invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = true; c->nseq_prefix_ok = false;
             return finalize_hand_over(c, out, to_host, n_solid);
         }
         STAGE_EVENT(c, c->ev0, s);        // (the span of the plain path starts here; what was written above is overwritten)
@@ -271,7 +271,7 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
     c->ms_finalize += ev_ms(c);
     if (d_row) *d_row = F.o_row;
     out->n = n_solid;
-    invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = !partitioned;
+    invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = !partitioned; c->nseq_prefix_ok = false;
     return finalize_hand_over(c, out, to_host, n);
 }
 
@@ -286,6 +286,7 @@ static int finalize_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host) {
     if (!(c->cap && c->M)) {
         c->h_keys.clear(); c->h_shift_full.clear(); c->h_src_read.clear(); c->h_src_start.clear(); c->h_src_end.clear();
         c->h_index.clear(); c->h_seqlen.clear(); c->h_abund.clear(); c->h_shift.clear(); c->h_rev.clear();
+        c->nodes_none = true;
         return MDBG_OK;
     }
     int e = finalize_begin_impl(c, true); if (e) return e;

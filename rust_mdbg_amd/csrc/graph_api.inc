@@ -1,5 +1,5 @@
 // graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip and bubble
-// removal (simplify.hip) and stitched contigs (contigs.hip).  Host code; included by api.inc, whose context, fail() and copy_out() it uses.
+// removal (simplify.hip), stitched contigs (contigs.hip) and node sequences (node_seqs.hip).  Host code; included by api.inc, whose context, fail() and copy_out() it uses.
 
 // ---- graph edges of the last finalized node table (edges.hip) -------------------------------------------
 static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_host) {
@@ -105,6 +105,19 @@ int mdbg_kept_reads(mdbg_ctx* c, uint64_t* n_reads, uint64_t* n_bases, uint64_t*
     if (bytes) *bytes = y;
     return MDBG_OK;
 }
+// the resident read store as the gather kernels take it: one descriptor per batch, sorted by first ordinal
+static int kept_table(mdbg_ctx* c, std::vector<KeptDesc>& tab) {
+    for (const Batch& b : c->batches) {
+        if (!b.kept) return fail(c, MDBG_E_STATE, "a resident batch came without bases (an imported sketch): its reads are not kept");
+        const KeptReads& k = *b.kept;
+        KeptDesc d{}; d.first_ordinal = b.first_ordinal; d.n_reads = k.n_reads; d.planes = k.planes(); d.n_words = k.n_words; d.offsets = k.offsets();
+        d.exc_pos = k.n_exc ? k.exc_pos() : nullptr; d.exc_val = k.n_exc ? k.exc_val() : nullptr; d.n_exc = k.n_exc;
+        tab.push_back(d);
+    }
+    std::sort(tab.begin(), tab.end(), [](const KeptDesc& a, const KeptDesc& b) { return a.first_ordinal < b.first_ordinal; });
+    if (tab.size() >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "too many kept batches");
+    return MDBG_OK;
+}
 static int contigs_impl(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out, bool to_host) {
     if (!c || !out) return MDBG_E_PARAM;
     MDBG_LOCK(c);
@@ -115,15 +128,7 @@ static int contigs_impl(mdbg_ctx* c, uint64_t min_len, mdbg_contig_seqs* out, bo
     if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "contigs are single-GPU only: not available on a routed or partitioned context");
     if (!c->ulist_ok) return fail(c, MDBG_E_STATE, "no current unitig list on this context (call mdbg_graph_unitigs* or mdbg_graph_simplify* first)");
     std::vector<KeptDesc> tab;
-    for (const Batch& b : c->batches) {
-        if (!b.kept) return fail(c, MDBG_E_STATE, "a resident batch came without bases (an imported sketch): its reads are not kept");
-        const KeptReads& k = *b.kept;
-        KeptDesc d{}; d.first_ordinal = b.first_ordinal; d.n_reads = k.n_reads; d.planes = k.planes(); d.n_words = k.n_words; d.offsets = k.offsets();
-        d.exc_pos = k.n_exc ? k.exc_pos() : nullptr; d.exc_val = k.n_exc ? k.exc_val() : nullptr; d.n_exc = k.n_exc;
-        tab.push_back(d);
-    }
-    std::sort(tab.begin(), tab.end(), [](const KeptDesc& a, const KeptDesc& b) { return a.first_ordinal < b.first_ordinal; });
-    if (tab.size() >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "too many kept batches");
+    { const int e = kept_table(c, tab); if (e) return e; }
     if (!c->cb) c->cb = contig_buffers_create();
     ContigResult r;
     const hipError_t he = stitch_contigs(c->cb, c->last_ul, tab.data(), (u32)tab.size(), min_len, c->stream, &r);
@@ -145,5 +150,50 @@ int mdbg_contigs_ms(mdbg_ctx* c, double* ms) {
     if (!c || !ms) return MDBG_E_PARAM;
     MDBG_LOCK(c);
     *ms = c->ms_stitch;
+    return MDBG_OK;
+}
+
+// ---- the node table's sequences gathered on the GPU from the resident read store, in bounded chunks (node_seqs.hip) ----
+static int node_seqs_impl(mdbg_ctx* c, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    out->first_row = first_row;
+    if (!(c->P.flags & MDBG_FLAG_KEEP_READS)) return fail(c, MDBG_E_STATE, "the context does not keep its reads (create it with MDBG_FLAG_KEEP_READS)");
+    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "node sequences are single-GPU only: not available on a routed or partitioned context");
+    if (!c->nodes_ok && !c->nodes_none)
+        return fail(c, MDBG_E_STATE, "no finalized node table on this context (call mdbg_finalize* first; an ingest, rewind or reset call ends the table)");
+    std::vector<KeptDesc> tab;
+    { const int e = kept_table(c, tab); if (e) return e; }
+    if (!c->nsb) c->nsb = node_seq_buffers_create();
+    const FinArgs& F = c->finF;
+    NodeSeqRows rows; rows.src_read = F.o_src_read; rows.src_start = F.o_src_start; rows.src_end = F.o_src_end; rows.reversed = F.o_rev; rows.n = c->nodes_ok ? c->nodes_n : 0;      // (nodes_none: the finalize of an empty context, no rows)
+    hipError_t he;
+    if (!c->nseq_prefix_ok && rows.n) {              // once per node table
+        he = node_seq_prefix(c->nsb, rows, c->stream);
+        if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "node_seq_prefix", he);
+        c->nseq_prefix_ok = true;
+    }
+    NodeSeqResult r;
+    he = node_seq_chunk(c->nsb, rows, tab.data(), (u32)tab.size(), first_row, max_rows, max_bases, c->stream, &r);
+    if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "node_seq_chunk", he);
+    c->ms_node_seqs = r.ms_gather;
+    if (r.err & 1u) return fail(c, MDBG_E_STATE, "a row of the node table names a read that is not kept");
+    if (r.err & 2u) return fail(c, MDBG_E_PARAM, "a row of the node table lies outside its read (not the reads the table was built from)");
+    out->n_rows = r.n_rows; out->n_bases = r.n_bases;
+    if (!to_host) { out->bases = r.bases; out->offsets = r.offsets; return MDBG_OK; }
+    const char* const what = "host copy of the node sequences";
+    int e;
+    if ((e = copy_out(c, c->hn_bases, r.bases, r.n_bases, what, &out->bases)) || (e = copy_out(c, c->hn_off, r.offsets, r.n_rows + 1, what, &out->offsets))) return e;      // (offsets: never empty)
+    return MDBG_OK;
+}
+int mdbg_graph_node_seqs(mdbg_ctx* c, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out) { return node_seqs_impl(c, first_row, max_rows, max_bases, out, true); }
+int mdbg_graph_node_seqs_device(mdbg_ctx* c, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out) { return node_seqs_impl(c, first_row, max_rows, max_bases, out, false); }
+int mdbg_node_seqs_ms(mdbg_ctx* c, double* ms) {
+    if (!c || !ms) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    *ms = c->ms_node_seqs;
     return MDBG_OK;
 }

@@ -339,23 +339,41 @@ static inline void put_u64s(std::string& out, u64 v) {
     do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
     while (n) out.push_back(t[--n]);
 }
+static bool seqfile_has_columns(const mdbg_nodes* nd) {                                               // (not a table of mdbg_finalize_gfa)
+    return !nd->n || (nd->keys && nd->src_read && nd->src_start && nd->src_end && nd->reversed && nd->shift_full && nd->index);
+}
+// the line of node i with `seq` (n bytes) as its sequence field: the bytes in order, or through utils::revcomp (main.rs:701) when revcomp is set
+static bool seqfile_put_line(mdbg_seqfile* s, const mdbg_nodes* nd, u64 i, const uint8_t* seq, u64 n, bool revcomp) {
+    const u32 k = nd->k;
+    put_u64s(s->buf, nd->index[i]); s->buf += "\t[";                                                  // main.rs:702: {index}\t{node:?}\t{seq}\t*\t{origin}\t{shift:?}
+    for (u32 j = 0; j < k; ++j) { if (j) s->buf += ", "; put_u64s(s->buf, nd->keys[i * k + j]); }
+    s->buf += "]\t";
+    if (revcomp) for (u64 p = n; p > 0; --p) s->buf += switch_base((char)seq[p - 1]);
+    else s->buf.append((const char*)seq, n);
+    s->buf += "\t*\t*\t("; put_u64s(s->buf, nd->shift_full[2 * i]); s->buf += ", "; put_u64s(s->buf, nd->shift_full[2 * i + 1]); s->buf += ")\n";
+    return s->buf.size() < (4u << 20) || s->flush_block();
+}
 // the lines of the nodes i with i % n_parts == part whose A-th sighting lies in this batch
 static int seqfile_write_part(mdbg_seqfile* s, const mdbg_nodes* nd, uint32_t part, uint32_t n_parts, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t first) {
     if (!s || !nd || !offsets || (n_reads && !bases && offsets[n_reads]) || !n_parts || part >= n_parts) return MDBG_E_PARAM;
-    if (nd->n && (!nd->keys || !nd->src_read || !nd->src_start || !nd->src_end || !nd->reversed || !nd->shift_full || !nd->index)) return MDBG_E_PARAM;      // a table of mdbg_finalize_gfa
-    const u32 k = nd->k;
+    if (!seqfile_has_columns(nd)) return MDBG_E_PARAM;
     for (u64 i = part; i < nd->n; i += n_parts) {
         const u64 r = nd->src_read[i];
         if (r < first || r >= first + n_reads) continue;
         const u64 ro = offsets[r - first], a = nd->src_start[i], b = nd->src_end[i];
         if (ro + b > offsets[r - first + 1] || a > b) return MDBG_E_PARAM;
-        put_u64s(s->buf, nd->index[i]); s->buf += "\t[";                                              // main.rs:702: {index}\t{node:?}\t{seq}\t*\t{origin}\t{shift:?}
-        for (u32 j = 0; j < k; ++j) { if (j) s->buf += ", "; put_u64s(s->buf, nd->keys[i * k + j]); }
-        s->buf += "]\t";
-        if (nd->reversed[i]) for (u64 p = b; p > a; --p) s->buf += switch_base((char)bases[ro + p - 1]);   // utils::revcomp, main.rs:701
-        else s->buf.append((const char*)bases + ro + a, b - a);
-        s->buf += "\t*\t*\t("; put_u64s(s->buf, nd->shift_full[2 * i]); s->buf += ", "; put_u64s(s->buf, nd->shift_full[2 * i + 1]); s->buf += ")\n";
-        if (s->buf.size() >= (4u << 20) && !s->flush_block()) return MDBG_E_IO;
+        if (!seqfile_put_line(s, nd, i, bases + ro + a, b - a, nd->reversed[i] != 0)) return MDBG_E_IO;
+    }
+    return MDBG_OK;
+}
+int mdbg_seqfile_write_nodes(mdbg_seqfile* s, const mdbg_nodes* nd, uint32_t part, uint32_t n_parts, uint64_t first_row, uint64_t n_rows, const uint8_t* bases,
+                             const uint64_t* offsets) {
+    if (!s || !nd || !offsets || !n_parts || part >= n_parts || first_row > nd->n || n_rows > nd->n - first_row || (n_rows && !bases && offsets[n_rows])) return MDBG_E_PARAM;
+    if (!seqfile_has_columns(nd)) return MDBG_E_PARAM;
+    for (u64 i = first_row + (part + n_parts - first_row % n_parts) % n_parts; i < first_row + n_rows; i += n_parts) {      // the first i >= first_row with i % n_parts == part
+        const u64 o0 = offsets[i - first_row], o1 = offsets[i - first_row + 1], a = nd->src_start[i], b = nd->src_end[i];
+        if (o1 < o0 || a > b || o1 - o0 != b - a) return MDBG_E_PARAM;
+        if (!seqfile_put_line(s, nd, i, bases + o0, o1 - o0, false)) return MDBG_E_IO;               // already oriented: no reverse complement here
     }
     return MDBG_OK;
 }

@@ -15,7 +15,7 @@ from .api import EdgeList as Edges          # one type for the host emitter's an
 
 
 EXPORTS = ["mdbg_lmer_filter_from_counts", "mdbg_lmer_filter_free", "mdbg_packed_words", "mdbg_pack_reads", "mdbg_seqfile_write_batch_part", "mdbg_emit_create", "mdbg_emit_destroy", "mdbg_emit_edges", "mdbg_emit_write_gfa", "mdbg_seqfile_open",
-           "mdbg_seqfile_write_batch", "mdbg_seqfile_close", "mdbg_emit_contigs_open", "mdbg_emit_contigs_add_batch", "mdbg_emit_contigs_set_sequences", "mdbg_emit_contigs_write_gfa",
+           "mdbg_seqfile_write_batch", "mdbg_seqfile_write_nodes", "mdbg_seqfile_close", "mdbg_emit_contigs_open", "mdbg_emit_contigs_add_batch", "mdbg_emit_contigs_set_sequences", "mdbg_emit_contigs_write_gfa",
            "mdbg_emit_contigs_write_fasta", "mdbg_emit_contigs_count", "mdbg_emit_contigs_get", "mdbg_emit_contigs_close"]
 
 
@@ -36,6 +36,7 @@ def load_library():
         L.mdbg_seqfile_write_batch.argtypes = [vp, C.POINTER(Nodes), vp, vp, C.c_uint64, C.c_uint64]
         L.mdbg_seqfile_close.argtypes = [vp]
         L.mdbg_seqfile_write_batch_part.argtypes = [vp, C.POINTER(Nodes), C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_uint64]
+        L.mdbg_seqfile_write_nodes.argtypes = [vp, C.POINTER(Nodes), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
         L.mdbg_packed_words.restype = C.c_uint64
         L.mdbg_packed_words.argtypes = [C.c_uint64]
         L.mdbg_pack_reads.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
@@ -242,6 +243,45 @@ class Emitter:
                     for rc in pool.map(job, range(threads)):
                         if rc:
                             raise RuntimeError("mdbg_seqfile_write_batch_part failed: %d" % rc)
+        finally:
+            rcs = [self.L.mdbg_seqfile_close(f) for f in files]
+        if any(rcs):
+            raise RuntimeError("mdbg_seqfile_close failed: %s" % rcs)
+        return paths
+
+    def write_sequences_from_kept(self, prefix, nodes, l, m, threads=1, chunk_bases=256 << 20):
+        """the .sequences files without a second pass over the input: the rows' sequences come from the reads the context `m` (Mdbg(keep_reads=True), with the node
+        table `nodes` came from still current) keeps on the device, chunk after chunk of at most chunk_bases bytes (Mdbg.graph_node_seqs; a longer row comes alone),
+        and mdbg_seqfile_write_nodes formats them.  threads <= 1: one file "<prefix>.0.sequences"; otherwise min(threads, 16) files "<prefix>.<t>.sequences", thread t
+        writing the rows i with i % threads == t of every chunk, as write_sequences_parallel does.  -> the paths.
+        Lines come out in ROW order.  write_sequences / write_sequences_parallel order them by the batch of the source read first and by row second, so the files hold
+        the same lines and are byte-identical when the second pass sees the whole input as one batch (the reference writes in hash-map order; its readers key by node name)."""
+        from concurrent.futures import ThreadPoolExecutor
+        nt = nodes if isinstance(nodes, NodeTable) else NodeTable(nodes)
+        if nt.gfa_only:
+            raise ValueError("a gfa_only node table cannot be written as .sequences")
+        n_parts = 1 if threads <= 1 else min(int(threads), 16)
+        paths = ["%s.%d.sequences" % (prefix, t) for t in range(n_parts)]
+        files, err = [], C.c_int()
+        try:
+            for p in paths:
+                f = self.L.mdbg_seqfile_open(p.encode(), nt.c.k, l, C.byref(err))
+                if not f:
+                    raise RuntimeError("mdbg_seqfile_open failed: %d" % err.value)
+                files.append(f)
+            with ThreadPoolExecutor(max_workers=n_parts) as pool:
+                row = 0
+                while True:
+                    ch = m.graph_node_seqs(row, 0, chunk_bases, raw=True)      # HOST arrays of the context, valid until its next node-sequence call
+                    if not ch.n_rows:
+                        break
+                    job = lambda t: self.L.mdbg_seqfile_write_nodes(files[t], C.byref(nt.c), t, n_parts, ch.first_row, ch.n_rows, ch.bases, ch.offsets)      # ctypes releases the GIL
+                    for rc in (pool.map(job, range(n_parts)) if n_parts > 1 else [job(0)]):
+                        if rc:
+                            raise RuntimeError("mdbg_seqfile_write_nodes failed: %d" % rc)
+                    row += int(ch.n_rows)
+                if row != nt.c.n:
+                    raise RuntimeError("the context's node table has %d rows, the table given %d" % (row, nt.c.n))
         finally:
             rcs = [self.L.mdbg_seqfile_close(f) for f in files]
         if any(rcs):

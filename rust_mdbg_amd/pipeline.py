@@ -21,7 +21,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -31,6 +31,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
+    sequences_from_kept (with write_sequences): the context keeps the reads (whether or not contigs is set) and the .sequences files are written from that
+    store right after the edges (Emitter.write_sequences_from_kept: Mdbg.graph_node_seqs in chunks), not in the second pass — which then only runs if the
+    contigs still need it (contigs without keep_reads).  Same lines per file, in row order (byte-identical files when the second pass sees the input as one
+    batch).  The time goes to seconds_until["sequences_kept"]; "sequences" keeps meaning the second pass and is absent when there is none.  Adds kept_reads.
     threads: host threads of the reader (uncompressed input: mdbg_reader_open_mt) and of the 2-bit packer; packed: hand the GPU 2-bit
     packed batches (a quarter of the bytes over PCIe), default: when threads > 1"""
     if packed is None:
@@ -97,8 +101,9 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     t0 = time.perf_counter()
     try:
         stitched = bool(contigs and keep_reads)      # the contigs' bases come from the device store, not from a second pass
+        seq_kept = bool(write_sequences and sequences_from_kept)      # so do the node sequences
         kept = None
-        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=stitched) as m:
+        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=stitched or seq_kept) as m:
             apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max)
             tm["open"] = time.perf_counter() - t0
             while True:
@@ -130,6 +135,11 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             em = Emitter()
             em.write_gfa(prefix + ".gfa", nodes, raw)
             tm["gfa"] = time.perf_counter() - t0
+            if seq_kept:                                 # the node table is current here; the calls below leave it alone, this one leaves them theirs
+                t1 = time.perf_counter()
+                em.write_sequences_from_kept(prefix, nodes, l, m, threads)
+                kept = m.kept_reads()
+                tm["sequences_kept"] = time.perf_counter() - t1
             ctg = sctg = sstats = None
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
@@ -150,7 +160,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
         stop.set()                          # error or not: release the reader (it closes the file) and wait for it
         th.join()
     tm["reader_closed"] = time.perf_counter() - t0
-    if write_sequences or (ctg is not None and not stitched):           # second pass over the input for the node sequences and the contigs' bases
+    second_seqs = write_sequences and not seq_kept
+    if second_seqs or (ctg is not None and not stitched):               # second pass over the input for the node sequences and the contigs' bases
         def again():
             first = 0
             with Reader(path, strip_newlines, threads=threads) as r:
@@ -162,7 +173,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     yield bases, offs, first
                     first += len(offs) - 1
         t1 = time.perf_counter()
-        if not write_sequences:
+        if not second_seqs:
             for _ in again():
                 pass
         elif threads > 1:                              # one file per writer thread, like the reference's worker threads (main.rs:614-630)
