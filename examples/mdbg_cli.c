@@ -2,6 +2,8 @@
  *   reads.fa[.gz]  ->  mdbg_reader_*  ->  mdbg_ingest_batch[_packed]  ->  mdbg_finalize  ->  mdbg_graph_edges  ->  <prefix>.gfa (+ <prefix>.0.sequences)
  *   --contigs:  ... ->  mdbg_graph_unitigs  ->  mdbg_emit_contigs_*  ->  <prefix>.unitigs.gfa + <prefix>.unitigs.fa   (what the reference's users get from
  *   `gfatools asm -u` + to_basespace + gfa2fasta.sh; no tip or bubble removal)
+ *   -c N,L: a small-component step in the schedule (every unitig of a non-circular connected component of at most N nodes and L bases is removed; 0 = no limit
+ *   on that side); --components: the number of connected components of the unitig graph and the largest one (mdbg_graph_components)
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
  *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
@@ -83,10 +85,10 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
-    /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L append steps of their own, in command-line order */
+    /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L append steps of their own, in command-line order */
     static const mdbg_simplify_step magic[] = {{MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000},
         {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000},
         {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}, {MDBG_SIMPLIFY_TIPS, 10, 150000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}};
@@ -122,15 +124,25 @@ int main(int argc, char** argv) {
             if (*end || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b\n"); return 2; }
             steps[n_steps++] = st; simplify = 1;
         }
+        else if (!strcmp(argv[i], "-c") && i + 1 < argc) {
+            char* end = NULL; const char* a = argv[++i];
+            mdbg_simplify_step st; st.kind = MDBG_SIMPLIFY_COMPONENTS;
+            st.max_nodes = (uint32_t)strtoul(a, &end, 10);
+            if (*end != ',') { fprintf(stderr, "-c wants N,L\n"); return 2; }
+            st.max_bases = strtoull(end + 1, &end, 10);
+            if (*end || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c\n"); return 2; }
+            steps[n_steps++] = st; simplify = 1;
+        }
+        else if (!strcmp(argv[i], "--components")) components = 1;
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [--components] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
-    if (simplify) contigs = 1;
+    if (simplify || components) contigs = 1;
     if (!contigs) keep_reads = 0;
     if (!write_sequences) seq_kept = 0;
     if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
@@ -241,7 +253,7 @@ int main(int argc, char** argv) {
         rc = mdbg_graph_simplify(ctx, steps, n_steps, &sl, &ss);
         if (rc) die(ctx, "mdbg_graph_simplify", rc);
         for (uint32_t j = 0; j < ss.n_steps; ++j)
-            printf("simplify step %u (%s %u,%llu): %llu unitigs, %llu nodes removed\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_TIPS ? "tips" : "bubbles", steps[j].max_nodes,
+            printf("simplify step %u (%s %u,%llu): %llu unitigs, %llu nodes removed\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_TIPS ? "tips" : steps[j].kind == MDBG_SIMPLIFY_BUBBLES ? "bubbles" : "components", steps[j].max_nodes,
                    (unsigned long long)steps[j].max_bases, (unsigned long long)ss.unitigs_removed[j], (unsigned long long)ss.nodes_removed[j]);
         printf("simplify: %llu unitigs, %llu nodes removed; %llu contigs left\n", (unsigned long long)ss.total_unitigs_removed, (unsigned long long)ss.total_nodes_removed,
                (unsigned long long)sl.n_unitigs);
@@ -262,6 +274,14 @@ int main(int argc, char** argv) {
         printf("Number of unitigs: %llu\n", (unsigned long long)ul.n_unitigs);
         ctg = mdbg_emit_contigs_open(&ul, &nodes, &err);
         if (!ctg) die(NULL, "mdbg_emit_contigs_open", err);
+        if (components) {                                           /* of the list just made; the call leaves it as it is */
+            mdbg_component_list cl; uint64_t big = 0;
+            rc = mdbg_graph_components(ctx, &cl);
+            if (rc) die(ctx, "mdbg_graph_components", rc);
+            for (uint64_t j = 1; j < cl.n_components; ++j) if (cl.nodes[j] > cl.nodes[big]) big = j;
+            printf("components: %llu (largest: %llu nodes, %llu bases)\n", (unsigned long long)cl.n_components, (unsigned long long)(cl.n_components ? cl.nodes[big] : 0),
+                   (unsigned long long)(cl.n_components ? cl.bases[big] : 0));
+        }
         if (keep_reads) {
             mdbg_contig_seqs cs;
             rc = mdbg_graph_contigs(ctx, 0, &cs);

@@ -356,7 +356,7 @@ typedef struct mdbg_unitig_list {
 int mdbg_graph_unitigs(mdbg_ctx* ctx, mdbg_unitig_list* out);
 int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
 
-/* ---- graph simplification: tip clipping and simple-bubble popping (the -t / -b rounds of utils/magic_simplify) --------------
+/* ---- graph simplification: tip clipping, simple-bubble popping (the -t / -b rounds of utils/magic_simplify) and small-component removal ----
  * Runs a caller-given schedule of steps on the GPU and returns the unitig list (same layout, same ownership rule, same state
  * requirements as mdbg_graph_unitigs: a current edge list, SINGLE GPU ONLY) of the graph that is left.  With n_steps = 0 the result
  * equals mdbg_graph_unitigs array for array.  The first `gfatools asm` line of utils/magic_simplify is the schedule
@@ -374,8 +374,8 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   a BEATS b: higher mean abundance kc_sum / entries (compared exactly by cross-multiplication), then larger length, then the
  *   smaller unitig number.
  *   TIPS.  Orient a small unitig u so that its first vertex has no in-arc.  u is a tip candidate iff that is possible in exactly
- *   one of its two orientations (a unitig with two dead ends is an isolated piece and is never removed: a deliberate difference from
- *   gfatools); x = the last vertex in that orientation, its attached vertex.  u is removed iff for every arc x -> w the vertex w has
+ *   one of its two orientations (a unitig with two dead ends is an isolated piece and is never removed by this kind: a deliberate
+ *   difference from gfatools; COMPONENTS below removes such pieces); x = the last vertex in that orientation, its attached vertex.  u is removed iff for every arc x -> w the vertex w has
  *   another in-neighbour x' != x that is not the attached vertex of a tip candidate, or is the attached vertex of a candidate that
  *   beats u.  Hence a vertex that survives and had an in-arc keeps one: clipping never makes a new dead end, and where every way
  *   into w is a small tip the best one stays.
@@ -384,12 +384,19 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   and (comp(q), comp(p)) under the vertex order 2 * index + minus.  Of the branches with one key all but the one that beats the
  *   others are removed.  Branches that branch themselves (superbubbles) are not treated; repeated tip and bubble steps reduce many
  *   of them to simple ones.
+ *   COMPONENTS.  The step decides against the current unitigs and their edges as they are when the step starts, grouped into connected components
+ *   by the definition of mdbg_graph_components below.  A component is SMALL for the step iff its `circular` is 0, its `nodes` <= max_nodes and its
+ *   `bases` <= max_bases (0 = no limit on that side): the limits apply to the component's sums, not to one unitig.  Every unitig of a small component
+ *   is removed; unitigs_removed[k] / nodes_removed[k] count as for the other kinds.  max_nodes == 0 && max_bases == 0 is MDBG_E_PARAM for this kind
+ *   (it would delete the graph).  A step may remove everything that is left: the call then returns MDBG_OK with the empty list (n_unitigs ==
+ *   n_entries == 0, edges.n == 0).  The schedule of utils/magic_simplify has no such step.
  *   Result: n_entries = |S|; edges = every edge record whose two nodes survive and whose arc is not an interior link, in source order.
- * MDBG_E_PARAM: an unknown kind, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
+ * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
  * entries owned by the context (valid like the list); n_compactions: compactions run (a step that removes nothing is followed by none);
- * n_syncs: host synchronisations of the call (per step: those of one compaction + 1). */
+ * n_syncs: host synchronisations of the call (per step: those of one compaction + 1; a COMPONENTS step adds none of its own). */
 #define MDBG_SIMPLIFY_TIPS 1u
 #define MDBG_SIMPLIFY_BUBBLES 2u
+#define MDBG_SIMPLIFY_COMPONENTS 4u
 typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
 typedef struct mdbg_simplify_stats {
     uint32_t n_steps, n_compactions;
@@ -399,6 +406,33 @@ typedef struct mdbg_simplify_stats {
 } mdbg_simplify_stats;
 int mdbg_graph_simplify(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
 int mdbg_graph_simplify_device(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
+
+/* ---- connected components of the unitig graph ---------------------------------------------------------------------------------
+ * Which unitigs belong together: what the reference's users get from splitting a .gfa by weakly connected component.  The call works on the context's
+ * CURRENT unitig list — the device arrays left by the last mdbg_graph_unitigs* / mdbg_graph_simplify* call, the list mdbg_graph_contigs uses — and leaves the
+ * node table, the edge list and the unitig list untouched (a contig call after it gives the same bytes).  SINGLE GPU ONLY.
+ *
+ * Definition:
+ *   Two unitigs of the list are JOINED iff some record of the list's `edges` names both of them, one as n1 and the other as n2; orientation is ignored,
+ *   and a record with n1 == n2 joins nothing.  A COMPONENT is a class of the transitive closure of "joined"; a unitig with no edge to another unitig is a
+ *   component of its own.  Components are numbered 0, 1, ... by the number of their smallest unitig.  Per component:
+ *     first_unitig  its smallest unitig number;                      unitigs   how many unitigs it holds;
+ *     nodes         the sum of offsets[u+1] - offsets[u] over them;   bases     the sum of length[u];
+ *     kc_sum        the sum of kc_sum[u];                             circular  1 iff any member unitig is circular.
+ *   Everything is an integer sum or a minimum: the result does not depend on scheduling, and two calls give identical arrays.
+ * mdbg_graph_components: HOST arrays; mdbg_graph_components_device: DEVICE arrays.  They belong to the context until its next component call, its next
+ * simplify call with a COMPONENTS step, or a call that ends the unitig list; they share no buffer with the unitig list, the contig result or the
+ * node-sequence result.  The device variant waits for the device ONCE (the component count and the defect flag in one read-back); the number of kernel launches
+ * is fixed.  The union-find behind it bounds every loop by n_unitigs + 1 steps; running into the bound is reported as MDBG_E_DEVICE, never waited on.
+ * MDBG_E_STATE: no current unitig list, or a routed / partitioned context; MDBG_E_PARAM: a null pointer.  An empty list gives MDBG_OK with zero counts. */
+typedef struct mdbg_component_list {
+    uint64_t n_unitigs, n_components;
+    const uint32_t* component;                         /* n_unitigs: component number of unitig u */
+    const uint32_t* first_unitig; const uint32_t* unitigs;      /* n_components */
+    const uint64_t* nodes; const uint64_t* bases; const uint64_t* kc_sum; const uint8_t* circular;   /* n_components */
+} mdbg_component_list;
+int mdbg_graph_components(mdbg_ctx* ctx, mdbg_component_list* out);
+int mdbg_graph_components_device(mdbg_ctx* ctx, mdbg_component_list* out);
 
 /* ---- contigs stitched on the GPU from reads kept packed in device memory -----------------------------------------------------
  * A context created with MDBG_FLAG_KEEP_READS in mdbg_params.flags keeps, for every batch that goes through an entry point WITH bases (mdbg_ingest_batch, _device,

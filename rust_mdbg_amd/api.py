@@ -85,6 +85,17 @@ def unitig_counts(u):
     return dict(offsets=nu + 1 if nu else 0, node=ne, ori=ne, src_read=ne, src_begin=ne, len=ne, revcomp=ne, dst_offset=ne, length=nu, kc_sum=nu, circular=nu)
 
 
+class ComponentList(C.Structure):      # mdbg_component_list
+    _fields_ = [("n_unitigs", C.c_uint64), ("n_components", C.c_uint64), ("component", C.POINTER(C.c_uint32)), ("first_unitig", C.POINTER(C.c_uint32)),
+                ("unitigs", C.POINTER(C.c_uint32)), ("nodes", C.POINTER(C.c_uint64)), ("bases", C.POINTER(C.c_uint64)), ("kc_sum", C.POINTER(C.c_uint64)),
+                ("circular", C.POINTER(C.c_uint8))]
+
+
+# (field, dtype, per unitig rather than per component)
+COMPONENT_FIELDS = (("component", np.uint32, True), ("first_unitig", np.uint32, False), ("unitigs", np.uint32, False), ("nodes", np.uint64, False),
+                    ("bases", np.uint64, False), ("kc_sum", np.uint64, False), ("circular", np.uint8, False))
+
+
 class ContigSeqs(C.Structure):         # mdbg_contig_seqs
     _fields_ = [("n_contigs", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64)),
                 ("unitig", C.POINTER(C.c_uint64))]
@@ -104,6 +115,7 @@ class SimplifyStats(C.Structure):      # mdbg_simplify_stats
 
 
 MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
+MDBG_SIMPLIFY_COMPONENTS = 4      # (kind, max_nodes, max_bases): every unitig of a non-circular connected component of at most max_nodes nodes and max_bases bases goes
 _T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
 # the schedule of the first `gfatools asm` line of utils/magic_simplify, as (kind, max_nodes, max_bases): -t N,L = tips of at most N nodes and L bases,
 # -b L = bubbles whose branches have at most L bases.  Same schedule, this project's own order-free rules (include/mdbg_hip.h): not gfatools parity.
@@ -141,7 +153,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
-           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -232,6 +244,8 @@ def load_library():
     L.mdbg_graph_unitigs_device.argtypes = [vp, C.POINTER(UnitigList)]
     L.mdbg_graph_simplify.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
     L.mdbg_graph_simplify_device.argtypes = [vp, C.POINTER(SimplifyStep), u32, C.POINTER(UnitigList), C.POINTER(SimplifyStats)]
+    L.mdbg_graph_components.argtypes = [vp, C.POINTER(ComponentList)]
+    L.mdbg_graph_components_device.argtypes = [vp, C.POINTER(ComponentList)]
     L.mdbg_graph_contigs.argtypes = [vp, u64, C.POINTER(ContigSeqs)]
     L.mdbg_graph_contigs_device.argtypes = [vp, u64, C.POINTER(ContigSeqs)]
     L.mdbg_kept_reads.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
@@ -521,7 +535,7 @@ class Mdbg:
                     n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs))
 
     def graph_simplify(self, steps, raw=False):
-        """the unitigs that are left after a schedule of tip and simple-bubble steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
+        """the unitigs that are left after a schedule of tip, simple-bubble and small-component steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
         project's own order-free rules in the spirit of `gfatools asm -t N,L -b L`, NOT bit-parity with gfatools).  steps: [(kind, max_nodes, max_bases)], e.g.
         MAGIC_SIMPLIFY_STEPS; an empty schedule gives graph_unitigs().  -> the dict of graph_unitigs() plus `stats` (per step: unitigs / nodes removed; totals);
         raw=True: (the C struct with HOST arrays, stats)"""
@@ -539,6 +553,21 @@ class Mdbg:
         u, st = UnitigList(), SimplifyStats()
         self._chk(self.L.mdbg_graph_simplify_device(self.h, arr, n, C.byref(u), C.byref(st)))
         return u, self._simplify_stats(st)
+
+    def graph_components(self):
+        """connected components of the current unitig list (the last graph_unitigs* / graph_simplify* call), found on the GPU: two unitigs are joined iff an edge of
+        the list names both (mdbg_graph_components, include/mdbg_hip.h); components are numbered by their smallest unitig.  Leaves the list as it is.
+        -> dict(n_unitigs, n_components, component u32[n_unitigs], and per component first_unitig, unitigs, nodes, bases, kc_sum, circular)"""
+        cl = ComponentList()
+        self._chk(self.L.mdbg_graph_components(self.h, C.byref(cl)))
+        nu, nc = int(cl.n_unitigs), int(cl.n_components)
+        return dict({f: _np(getattr(cl, f), nu if per_unitig else nc, t) for f, t, per_unitig in COMPONENT_FIELDS}, n_unitigs=nu, n_components=nc)
+
+    def graph_components_device(self):
+        """-> ComponentList with DEVICE pointers (valid until the next component call, a simplify call with a component step, or a call that ends the unitig list)"""
+        cl = ComponentList()
+        self._chk(self.L.mdbg_graph_components_device(self.h, C.byref(cl)))
+        return cl
 
     def kept_reads(self):
         """the resident read store of a keep_reads context -> dict(n_reads, n_bases, bytes); bytes = n_bases / 4 + 8 per read + 9 per exception, up to the

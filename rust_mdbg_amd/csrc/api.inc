@@ -17,6 +17,7 @@
 #include "edges.h"
 #include "unitigs.h"
 #include "simplify.h"
+#include "components.h"
 #include "contigs.h"
 #include "node_seqs.h"
 

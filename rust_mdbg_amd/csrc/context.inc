@@ -101,6 +101,8 @@ struct mdbg_ctx {
     HostRaw<u64> hu_off, hu_sread, hu_sbegin, hu_dst, hu_length, hu_kc; HostRaw<u32> hu_node, hu_len, hu_n1, hu_n2, hu_ov; HostRaw<u8> hu_ori, hu_rc, hu_circ, hu_o1, hu_o2;   // host copy of the last unitig list
     std::vector<u64> hs_unitigs, hs_nodes;   // per-step removal counts of the last mdbg_graph_simplify
     UnitigResult last_ul{}; bool ulist_ok = false;      // device unitig list of the last unitig / simplify call; ulist_ok: it is current (no edge, finalize, ingest or reset call since)
+    ComponentBuffers* compb = nullptr;       // connected components of the unitig list (components.hip), created on first use; its result buffers live until the next component call or simplify call with a component step
+    HostRaw<u32> hk_comp, hk_first, hk_unitigs; HostRaw<u64> hk_nodes, hk_bases, hk_kc; HostRaw<u8> hk_circ;      // host copy of the last mdbg_graph_components
     ContigBuffers* cb = nullptr;             // contig stitching (contigs.hip), created on first use; its result buffers live until the next contig call
     DevBuf kp_exc_pos, kp_exc_val, kp_cnt;   // keeping an ASCII batch: where the pack kernel appends the (unordered) exceptions, and their count
     HostRaw<u8> hc_bases; HostRaw<u64> hc_off, hc_unitig;      // host copy of the last mdbg_graph_contigs
@@ -391,6 +393,7 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     for (auto e : c->tile_ev) (void)hipEventDestroy(e);
     if (c->eb) edge_buffers_destroy(c->eb);
     if (c->ub) unitig_buffers_destroy(c->ub);
+    if (c->compb) component_buffers_destroy(c->compb);
     if (c->cb) contig_buffers_destroy(c->cb);
     if (c->nsb) node_seq_buffers_destroy(c->nsb);
     if (c->h_scal) (void)hipHostFree(c->h_scal);

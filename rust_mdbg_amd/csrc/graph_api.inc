@@ -1,5 +1,5 @@
-// graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip and bubble
-// removal (simplify.hip), stitched contigs (contigs.hip) and node sequences (node_seqs.hip).  Host code; included by api.inc, whose context, fail() and copy_out() it uses.
+// graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip, bubble and small-component
+// removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip) and node sequences (node_seqs.hip).  Host code; included by api.inc, whose context, fail() and copy_out() it uses.
 
 // ---- graph edges of the last finalized node table (edges.hip) -------------------------------------------
 static int edges_impl(mdbg_ctx* c, float presimp, mdbg_edge_list* out, bool to_host) {
@@ -38,10 +38,16 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
     memset(out, 0, sizeof *out);
+    bool with_components = false;
     if (stats) {
         memset(stats, 0, sizeof *stats);
-        for (uint32_t i = 0; i < n_steps; ++i)
-            if (steps[i].kind != MDBG_SIMPLIFY_TIPS && steps[i].kind != MDBG_SIMPLIFY_BUBBLES) return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+        for (uint32_t i = 0; i < n_steps; ++i) {
+            const uint32_t kind = steps[i].kind;
+            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS) return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+            if (kind == MDBG_SIMPLIFY_COMPONENTS && steps[i].max_nodes == 0 && steps[i].max_bases == 0)
+                return fail(c, MDBG_E_PARAM, "a component step without a limit would remove the whole graph");
+            with_components |= kind == MDBG_SIMPLIFY_COMPONENTS;
+        }
         c->hs_unitigs.assign(n_steps, 0); c->hs_nodes.assign(n_steps, 0);
         stats->n_steps = n_steps; stats->unitigs_removed = c->hs_unitigs.data(); stats->nodes_removed = c->hs_nodes.data();
     }
@@ -51,15 +57,16 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (!(c->nodes_ok && c->edges_ok)) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
     if (c->nodes_n == 0) { c->ulist_ok = true; return MDBG_OK; }
     if (!c->ub) c->ub = unitig_buffers_create();
+    if (with_components && !c->compb) c->compb = component_buffers_create();
     const FinArgs& F = c->finF;
     UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
     nd.reversed = F.o_rev; nd.n = c->nodes_n;
     UnitigResult r; int broken = 0;
     SimplifyInfo si{};
-    const hipError_t he = stats ? simplify_unitigs(c->ub, nd, c->last_edges, steps, n_steps, c->stream, &r, c->hs_unitigs.data(), c->hs_nodes.data(), &si, &broken)
+    const hipError_t he = stats ? simplify_unitigs(c->ub, c->compb, nd, c->last_edges, steps, n_steps, c->stream, &r, c->hs_unitigs.data(), c->hs_nodes.data(), &si, &broken)
                                 : build_unitigs(c->ub, nd, c->last_edges, c->stream, &r, &broken);
     if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "build_unitigs", he);
-    if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, or the walk broke an invariant");
+    if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, or the walk broke an invariant");
     if (stats) {
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
         for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += c->hs_unitigs[i]; stats->total_nodes_removed += c->hs_nodes[i]; }
@@ -67,6 +74,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     c->last_ul = r; c->ulist_ok = true;
     const u64 U = r.n_unitigs, N = r.n_entries, E = r.edges.n;
     out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = E;
+    if (U == 0) return MDBG_OK;                      // a schedule that removed everything: the empty list, as an empty context gives it
     if (!to_host) {
         out->offsets = r.offsets; out->node = r.node; out->ori = r.ori; out->src_read = r.src_read; out->src_begin = r.src_begin; out->len = r.len; out->revcomp = r.revcomp;
         out->dst_offset = r.dst_offset; out->length = r.length; out->kc_sum = r.kc_sum; out->circular = r.circular;
@@ -93,6 +101,39 @@ int mdbg_graph_simplify_device(mdbg_ctx* c, const mdbg_simplify_step* steps, uin
     if (!stats) return MDBG_E_PARAM;
     return unitigs_impl(c, steps, n_steps, out, stats, false);
 }
+
+// ---- connected components of the current unitig list (components.hip) -------------------------------------
+static int components_impl(mdbg_ctx* c, mdbg_component_list* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "components are single-GPU only: not available on a routed or partitioned context");
+    if (!c->ulist_ok) return fail(c, MDBG_E_STATE, "no current unitig list on this context (call mdbg_graph_unitigs* or mdbg_graph_simplify* first)");
+    if (c->last_ul.n_unitigs == 0) return MDBG_OK;
+    if (!c->compb) c->compb = component_buffers_create();
+    ComponentResult r; int broken = 0;
+    const hipError_t he = build_components(c->compb, c->last_ul, c->stream, &r, &broken);
+    if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "build_components", he);
+    if (broken) return fail(c, MDBG_E_DEVICE, "the union-find of the components ran into its bound of n_unitigs + 1 steps, or an edge names a unitig outside the list");
+    const u64 U = r.n_unitigs, K = r.n_components;
+    out->n_unitigs = U; out->n_components = K;
+    if (!to_host) {
+        out->component = r.component; out->first_unitig = r.first_unitig; out->unitigs = r.unitigs; out->nodes = r.nodes; out->bases = r.bases; out->kc_sum = r.kc_sum;
+        out->circular = r.circular;
+        return MDBG_OK;
+    }
+    const char* const what = "host copy of the component list";
+    int e;
+    if ((e = copy_out(c, c->hk_comp, r.component, U, what, &out->component)) || (e = copy_out(c, c->hk_first, r.first_unitig, K, what, &out->first_unitig)) ||
+        (e = copy_out(c, c->hk_unitigs, r.unitigs, K, what, &out->unitigs)) || (e = copy_out(c, c->hk_nodes, r.nodes, K, what, &out->nodes)) ||
+        (e = copy_out(c, c->hk_bases, r.bases, K, what, &out->bases)) || (e = copy_out(c, c->hk_kc, r.kc_sum, K, what, &out->kc_sum)) ||
+        (e = copy_out(c, c->hk_circ, r.circular, K, what, &out->circular))) return e;
+    return MDBG_OK;
+}
+int mdbg_graph_components(mdbg_ctx* c, mdbg_component_list* out) { return components_impl(c, out, true); }
+int mdbg_graph_components_device(mdbg_ctx* c, mdbg_component_list* out) { return components_impl(c, out, false); }
 
 // ---- contigs stitched on the GPU from the resident read store (contigs.hip) ------------------------------
 int mdbg_kept_reads(mdbg_ctx* c, uint64_t* n_reads, uint64_t* n_bases, uint64_t* bytes) {

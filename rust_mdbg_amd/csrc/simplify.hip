@@ -13,6 +13,7 @@
 //   tip_decide_kernel    candidate u is removed iff every target of x has another in-neighbour that is no candidate's attached vertex or a better candidate's
 //   bubble_key_kernel    small unitig with one way in (p) and one way out (q), p / q not on it, q != comp(p) -> key min((p,q), (comp q, comp p)); rocPRIM sorts (key, unitig)
 //   bubble_decide_kernel first entry of every run of equal keys: the best member stays, the others are removed
+//   comp_decide_kernel   unitig of a small component (components.hip: nodes, bases and circular summed per component) -> removed
 //   scatter_kernel       vertices of removed unitigs -> alive[row] = 0; counts the nodes
 //
 // Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks.  A step that
@@ -148,6 +149,19 @@ __global__ __launch_bounds__(256) void bubble_decide_kernel(SimpArgs a) {
     if (gone) atomicAdd(a.ctr, gone);
 }
 
+// MDBG_SIMPLIFY_COMPONENTS: the limits apply to the component's sums, not to the unitig
+__global__ __launch_bounds__(256) void comp_decide_kernel(SimpArgs a, const u32* __restrict__ component, const u64* __restrict__ c_nodes, const u64* __restrict__ c_bases,
+                                                          const u8* __restrict__ c_circ) {
+    const u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool gone = false;
+    if (u < a.U) {
+        const u32 c = component[u];
+        gone = c < a.U && !c_circ[c] && (a.max_nodes == 0 || c_nodes[c] <= a.max_nodes) && (a.max_bases == 0 || c_bases[c] <= a.max_bases);
+        a.rem[u] = gone ? 1 : 0;
+    }
+    count_to(a.ctr, gone);
+}
+
 __global__ __launch_bounds__(256) void scatter_kernel(SimpArgs a) {
     const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
     bool gone = false;
@@ -161,7 +175,7 @@ __global__ __launch_bounds__(256) void scatter_kernel(SimpArgs a) {
 
 }  // namespace
 
-hipError_t simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
+hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
                      uint64_t* unitigs_removed, uint64_t* nodes_removed, SimplifyInfo* info, int* broken) {
     memset(info, 0, sizeof *info);
     if (n_steps == 0 || nd.n == 0) {                          // the empty schedule IS the unitig call
@@ -179,6 +193,7 @@ hipError_t simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeR
     u64 n_alive = n;
     bool stale = true;                                        // the arrays of the last compaction no longer describe the surviving graph
     auto compact = [&]() -> hipError_t {
+        if (n_alive == 0) { memset(out, 0, sizeof *out); stale = false; return hipSuccess; }      // a step removed all that was left: the empty list, nothing to launch
         GHIP(build_unitigs_masked(B, nd, ed, alive, n_alive, s, out, broken));
         if (*broken) return hipSuccess;
         ++info->n_compactions; info->n_rounds_total += out->n_rounds; info->n_syncs += out->n_rounds + 3 + (ed.n ? 1 : 0);
@@ -198,23 +213,34 @@ hipError_t simplify_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeR
         a.offsets = out->offsets; a.length = out->length; a.kc = out->kc_sum; a.circ = out->circular; a.max_nodes = steps[k].max_nodes; a.max_bases = steps[k].max_bases;
         a.uhead = B->uhead.as<u32>(); a.utail = B->utail.as<u32>(); a.att = B->att.as<u32>(); a.owner = B->owner.as<u32>(); a.rem = B->rem.as<u8>(); a.ctr = d_ctr; a.alive = alive;
         const unsigned gu = grid_for(U), gv = grid_for(n2x);
-        hipLaunchKernelGGL(ends_kernel, dim3(gv), dim3(256), 0, s, a);
-        if (steps[k].kind == MDBG_SIMPLIFY_TIPS) {
-            GHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
-            hipLaunchKernelGGL(tip_cand_kernel, dim3(gu), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(tip_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+        const u32* d_cstatus = nullptr;                       // a component step: where its stage reports a defect
+        if (steps[k].kind == MDBG_SIMPLIFY_COMPONENTS) {
+            if (!CB) return hipErrorInvalidValue;
+            ComponentResult cr;
+            GHIP(queue_components(CB, *out, s, &cr));
+            hipLaunchKernelGGL(comp_decide_kernel, dim3(gu), dim3(256), 0, s, a, cr.component, cr.nodes, cr.bases, cr.circular);
+            d_cstatus = cr.status;
         } else {
-            GHIP(B->bkey.ensure(n * 8)); GHIP(B->bkey2.ensure(n * 8)); GHIP(B->bval.ensure(n * 4)); GHIP(B->bval2.ensure(n * 4));
-            a.bkey = B->bkey.as<u64>(); a.bval = B->bval.as<u32>(); a.skey = B->bkey2.as<u64>(); a.sval = B->bval2.as<u32>();
-            hipLaunchKernelGGL(bubble_key_kernel, dim3(gu), dim3(256), 0, s, a);
-            GHIP(sort_pairs(B->tmp, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
-            hipLaunchKernelGGL(bubble_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(ends_kernel, dim3(gv), dim3(256), 0, s, a);
+            if (steps[k].kind == MDBG_SIMPLIFY_TIPS) {
+                GHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
+                hipLaunchKernelGGL(tip_cand_kernel, dim3(gu), dim3(256), 0, s, a);
+                hipLaunchKernelGGL(tip_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+            } else {
+                GHIP(B->bkey.ensure(n * 8)); GHIP(B->bkey2.ensure(n * 8)); GHIP(B->bval.ensure(n * 4)); GHIP(B->bval2.ensure(n * 4));
+                a.bkey = B->bkey.as<u64>(); a.bval = B->bval.as<u32>(); a.skey = B->bkey2.as<u64>(); a.sval = B->bval2.as<u32>();
+                hipLaunchKernelGGL(bubble_key_kernel, dim3(gu), dim3(256), 0, s, a);
+                GHIP(sort_pairs(B->tmp, a.bkey, B->bkey2.as<u64>(), a.bval, B->bval2.as<u32>(), (size_t)U, 0, 64, s));
+                hipLaunchKernelGGL(bubble_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+            }
         }
         hipLaunchKernelGGL(scatter_kernel, dim3(gv), dim3(256), 0, s, a);
-        u32 got[2];
+        u32 got[2], cdefect = 0;
         GHIP(hipMemcpyAsync(got, d_ctr, 8, hipMemcpyDeviceToHost, s));
+        if (d_cstatus) GHIP(hipMemcpyAsync(&cdefect, d_cstatus, 4, hipMemcpyDeviceToHost, s));      // (the same wait: a component step costs no synchronisation of its own)
         GHIP(hipStreamSynchronize(s));
         ++info->n_syncs;
+        if (cdefect) return defect(broken);
         if (got[1] > n_alive || got[0] > U || (got[0] == 0) != (got[1] == 0)) return defect(broken);
         unitigs_removed[k] = got[0]; nodes_removed[k] = got[1];
         n_alive -= got[1];

@@ -7,7 +7,7 @@ import queue
 import threading
 import time
 
-from .api import MAGIC_SIMPLIFY_STEPS, Mdbg
+from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, unitig_name
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 
@@ -21,13 +21,16 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
     to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
     simplify (with contigs): a schedule of tip / bubble steps, e.g. api.MAGIC_SIMPLIFY_STEPS — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
     Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
+    components (with contigs): also write <prefix>.unitigs.components.tsv, one line `utgNAME<TAB>component` per unitig: the connected component of the unitig
+    graph each unitig lies in (Mdbg.graph_components; numbered by their smallest unitig), and with simplify <prefix>.msimpl.components.tsv for the simplified
+    list.  Adds n_components (and n_components_simplified).  The other files are unchanged.
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -141,15 +144,27 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 kept = m.kept_reads()
                 tm["sequences_kept"] = time.perf_counter() - t1
             ctg = sctg = sstats = None
+            comp = {}
+
+            def write_components(ul, path_, key):        # ul: the context's current unitig list (host arrays): the names need its circular flags
+                cc = m.graph_components()
+                with open(path_, "w") as f:
+                    f.write("".join("%s\t%d\n" % (unitig_name(i, ul.circular[i]), c) for i, c in enumerate(cc["component"].tolist())))
+                comp[key] = cc["n_components"]
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
+                if components:
+                    write_components(sl, prefix + ".msimpl.components.tsv", "n_components_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
                 tm["simplify"] = time.perf_counter() - t0
             if contigs:                                  # the plan is copied out of the context here; the bases follow in the second pass
-                ctg = Contigs(m.graph_unitigs(raw=True), nodes["n_nodes"])
+                ul = m.graph_unitigs(raw=True)
+                ctg = Contigs(ul, nodes["n_nodes"])
+                if components:
+                    write_components(ul, prefix + ".unitigs.components.tsv", "n_components")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
@@ -181,7 +196,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
         else:
             em.write_sequences(prefix + ".0.sequences", nodes, l, again())
         tm["sequences"] = time.perf_counter() - t1
-    extra = {}
+    extra = dict(comp)
     if kept is not None:
         extra["kept_reads"] = kept
     if ctg is not None:
