@@ -180,6 +180,8 @@ int mdbg_sketch_only(mdbg_ctx* ctx, const uint8_t* bases, const uint64_t* offset
 int mdbg_query_batch(mdbg_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, const uint32_t** counts,
                      const uint64_t** per_read_offsets, uint64_t* n_windows);
 
+/* The node table of every batch ingested so far (HOST arrays owned by the context, valid until the next call on ctx).  mdbg_finalize and the ingest calls may
+ * alternate, with the batches' first_read_ordinal in any order: each finalize describes all batches ingested so far, as if they had arrived in ordinal order. */
 int mdbg_finalize(mdbg_ctx* ctx, mdbg_nodes* out);
 /* Same node table, but every pointer in *out is DEVICE memory (no copy to the host). */
 int mdbg_finalize_device(mdbg_ctx* ctx, mdbg_nodes* out);

@@ -62,6 +62,9 @@ struct mdbg_ctx {
     DevBuf link_ctr;                         // MDBG_COUNT_LINKS (test hook): one u64, see TableArgs::link_ctr
     DevBuf claim;                            // one byte per resident minimizer index: the window starting there created its key (TableArgs::claim); as large as the store
     bool claims_ok = false;                  // every window in the table was inserted by insert_windows_kernel with the claim map on (set by clear_table / the first table)
+    size_t claims_fin_batches = 0; u64 claims_fin_top = 0;      // the last claim-map finalize of this table: how many batches it saw (0: none yet) and the largest first ordinal
+                                             // among them.  It left marks on the first sightings it knew; a batch that comes later with a SMALLER first ordinal can move a
+                                             // first sighting once more, and nothing clears the mark left on the old one: fin_setup then gives the claim map up (claims_ok)
     DevBuf bm_first, bm_solid, pre_first, pre_solid, popc_tmp, bt_dev, fin_out, solid_list, fin_order;
     DevBuf bm_local, pre_local, pre_local2;       // partitioned finalize: THIS rank's solid bitmap as it was before the merge over the ranks, and its prefix (the order of the partition's rows)
     HostRaw<u64> h_keys, h_shift_full, h_src_read, h_src_start, h_src_end; HostRaw<u32> h_index, h_seqlen; HostRaw<u16> h_abund, h_shift; HostRaw<u8> h_rev;
@@ -269,6 +272,7 @@ int table_reserve(mdbg_ctx* c, u64 incoming) {
         c->cap = want;
         launch_clear_table(c->tab.as<Slot>(), c->cap, c->mx.as<u64>(), A > 2 ? c->cap * (A - 2) : 0, c->stream);
         c->claims_ok = !c->routed && c->claim.p != nullptr;      // an empty table: from here on every insertion writes its claims
+        c->claims_fin_batches = 0;
         return MDBG_OK;
     }
     if (need <= c->cap) return MDBG_OK;
@@ -298,7 +302,7 @@ int clear_table(mdbg_ctx* c) {
     if (c->cap) launch_clear_table(c->tab.as<Slot>(), c->cap, c->mx.as<u64>(), cascade_of(c->P.min_abundance) > 2 ? c->cap * (cascade_of(c->P.min_abundance) - 2) : 0, c->stream, &z);
     else launch_zero_regions(z, c->stream);
     c->n_distinct = 0; c->n_windows = 0; c->batches_inserted = 0; c->n_records = 0; c->routed = false;
-    c->claims_ok = c->claim.p != nullptr;
+    c->claims_ok = c->claim.p != nullptr; c->claims_fin_batches = 0;      // (an empty table: no finalize has left a mark in the claim map that the insertions will not rewrite)
     return MDBG_OK;
 }
 

@@ -65,11 +65,20 @@ static int fin_setup(mdbg_ctx* c, FinArgs& F, u64& n_words_out, bool byte_maps =
                 // Round 6: the same under a partitioned table and for batches whose dense order is not the store's (F.claims = 2): every insertion kernel of resident
                 // windows writes its claims (a rank inserts only windows it owns, so "this window created its key" is as well defined as on one rank), the map is indexed by
                 // store index and launch_claims_to_bits gathers it into the dense bitmaps.
+                // A claim-map finalize MOVES marks (fin_mark_claims_kernel: off the claimer, onto the first sighting it sees) and clears only the claimer's byte the next
+                // time.  That holds as long as first sightings stay where they are: a batch that arrives afterwards BELOW the largest first ordinal that finalize saw may
+                // hold an earlier sighting of a key whose mark has been moved, and the mark on the sighting in between would stay (the key counted twice, every row behind it
+                // shifted).  From such a batch on the table is finalized through the zeroed byte maps, until it is cleared.  Host-side and by ordinals alone, so the same
+                // rule covers a partitioned table (own_world > 1), whose peers' batches are registered here like its own.
+                if (c->claims_ok && c->claims_fin_batches)
+                    for (size_t i = c->claims_fin_batches; i < c->batches.size(); ++i)
+                        if (c->batches[i].first_ordinal < c->claims_fin_top) { c->claims_ok = false; break; }
                 const bool use_claims = c->claims_ok && !c->routed && c->claim.p && c->batches_inserted == c->batches.size() && getenv("MDBG_NO_CLAIMS") == nullptr;
                 bool dense_is_store = c->own_world <= 1 && acc == c->M;
                 for (u32 i = 0; i < nb && dense_is_store; ++i) dense_is_store = !bs[i].partial && rb[i] == bs[i].m0;
                 if (use_claims) {
                     F.claims = dense_is_store ? 1 : 2;
+                    c->claims_fin_batches = c->batches.size(); c->claims_fin_top = nb ? fo[nb - 1] : 0;      // (what this finalize's marks rest on, see above)
                     F.by_first = c->claim.as<u8>(); F.by_solid = nullptr;          // one map: bit 0 first sighting, bit 1 solid (fin_mark_claims_kernel); nothing to zero
                     z.n[0] = 0; z.n[1] = 0;                                        // (the bytes behind the store's end are masked by launch_bytes_to_bits: n_bits = M)
                 } else {
