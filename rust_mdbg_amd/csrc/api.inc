@@ -1,4 +1,4 @@
-// api.inc — context management and the C ABI of include/mdbg_hip.h (host code; included by libmdbg.hip after sketch.hip / table.hip / synth.hip so that
+// api.inc — context management and the C ABI of include/mdbg_hip.h (host code; included by libmdbg.hip after the device files, sketch.hip .. route.hip, so that
 // it sees their launchers and argument structs).  Its parts, in the order they depend on each other:
 #include <algorithm>
 #include <cstdio>

@@ -94,7 +94,7 @@ struct mdbg_dist {
     mdbg_ctx* ctx = nullptr; mdbg_comm comm{}; RcclComm* own_rccl = nullptr;
     DevBuf rel_off;                              // offsets of my batch relative to its region (what the peers commit)
     std::vector<DevBuf> peer_off, peer_list;     // receive buffers per peer
-    // segments (the default exchange): only the hashes the receiver's listed windows need travel (table.hip, "segments")
+    // segments (the default exchange): only the hashes the receiver's listed windows need travel (owner.hip, "segments")
     bool settings_checked = false;               // the ranks' versions and settings have been compared (first round)
     bool owner_ready = false; DevBuf own_hist;  // the measured owner table has been built (first round; build_owner_table)
     bool whole = false;                          // mdbg_dist_set_exchange(MDBG_EXCHANGE_WHOLE): ship whole sketches (a later mdbg_dist_reset(k) needs them)
@@ -127,7 +127,7 @@ struct DistTimer {           // adds the host time of its scope to a stage (the 
     ~DistTimer() { if (d->timing) d->t_ms[st] += now_ms() - t0; }
 };
 
-// Called by finalize_end_impl right before fin_emit (through mdbg_ctx::before_emit), on every rank: collective.  See table.hip, "positions of
+// Called by finalize_end_impl right before fin_emit (through mdbg_ctx::before_emit), on every rank: collective.  See finalize.hip, "positions of
 // remote sketches".
 static int dist_fetch_positions(void* self, FinArgs& F, u64 n_solid) {
     mdbg_dist* d = (mdbg_dist*)self; mdbg_ctx* c = d->ctx;

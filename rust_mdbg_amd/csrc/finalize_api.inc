@@ -108,7 +108,7 @@ static int fin_setup(mdbg_ctx* c, FinArgs& F, u64& n_words_out, bool byte_maps =
 
 // finalize, phase 1: mark first sightings / solid nodes of THIS context's keys in the bitmaps, list the solid slots
 // Nodes seen >= 65536 + minabund times: the reference's u16 abundance wrapped, and its entry describes sighting
-// j* = A + 65536 * floor((count - A) / 65536) instead of the A-th (table.hip, wrap_list_kernel).  n_bound: upper bound of
+// j* = A + 65536 * floor((count - A) / 65536) instead of the A-th (finalize.hip, wrap_list_kernel).  n_bound: upper bound of
 // the number of such nodes.  Sets F.ath_override (null when there is none).  Rare and off the fast path: a table scan, a
 // re-scan of the resident windows (or routed records), one segmented sort.
 static int resolve_wrapped(mdbg_ctx* c, FinArgs& F, u64 n_bound, bool routed) {
