@@ -1,5 +1,7 @@
 """GPU edge construction (mdbg_graph_edges, csrc/edges.hip) == the host emitter == the oracle's end-to-end edges
-(src/main.rs:1017-1117), in the same order, with and without presimplification."""
+(src/main.rs:1017-1117), in the same order, with and without presimplification.  The graphs here are whatever the sketched
+reads give; the cases built on purpose (palindromic (k-1)-mers, self-neighbours, hubs, f32 rounding in the presimplification test, position gaps above 65,535) are
+in tests/test_gpu_sketch_graphs.py."""
 import random
 
 import numpy as np
