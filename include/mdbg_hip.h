@@ -495,6 +495,50 @@ int mdbg_graph_node_seqs(mdbg_ctx* ctx, uint64_t first_row, uint64_t max_rows, u
 int mdbg_graph_node_seqs_device(mdbg_ctx* ctx, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out);
 int mdbg_node_seqs_ms(mdbg_ctx* ctx, double* ms);
 
+/* ---- the resident reads threaded through the unitig graph ----------------------------------------------------------------------
+ * Which unitigs, in which order and orientation, does each read walk?  The call works on the context's CURRENT unitig list (the list of the last
+ * mdbg_graph_unitigs* / mdbg_graph_simplify* call), the node table that list was built from, and the resident sketch store; it keeps no new data and leaves the node
+ * table, the edge list, the unitig list, the contig result and the component result as they are.  SINGLE GPU ONLY.
+ *
+ * Definition:
+ *   READS are addressed by their slot in the store, r = 0 .. n - 1, the order of mdbg_sketch_view's d_read_offsets; ordinal[] gives a read's ordinal (its batch's
+ *   first_read_ordinal plus its position in the batch).  A read with n minimizers has W = n - k + 1 WINDOWS if n > k, else none (src/main.rs:756-759, strictly more
+ *   than k); window w covers minimizers w .. w + k - 1.  Its canonical key and its `rev` flag are KmerVec::normalize's: a window equal to its reverse counts as reversed.
+ *   Window w is PLACED iff its key is a row of the current node table (abundance filter as --read_stats: min_abundance == 1 or (u16)count >= (u16)min_abundance) and that
+ *   row's `index` occurs as node[e] of an entry e of the current list (after a simplify schedule some rows occur in no entry; an index occurs in at most one entry: the
+ *   unitigs partition the surviving nodes).  For a placed window: unitig u = the unitig that holds e, entry j = e - offsets[u], strand s = rev XOR (ori[e] == '-');
+ *   s = 0: the read walks the unitig in walk order.
+ *   A STEP is a maximal run of consecutive placed windows w, w + 1, ... of one read with the same u and the same s whose j advances by +1 (s = 0) or by -1 (s = 1);
+ *   on a CIRCULAR unitig of m entries the successor is taken mod m, so a read that goes round a ring more than once is ONE step with n_windows > m; a linear unitig
+ *   never continues onto itself.  A window that is not placed belongs to no step and ends a run.  Step p is the record first_window[p], step_windows[p] (its number
+ *   of windows), unitig[p], first_entry[p] (the j of its first window), strand[p]; the steps of read first_read + q are [step_offsets[q], step_offsets[q + 1]), in
+ *   window order.
+ *   Per unitig of the list: support_windows[u] = placed windows on u, support_steps[u] = steps on u, over the reads of the call's range.  Everything is an integer sum
+ *   or a position of one scan: two calls give identical arrays, nothing depends on scheduling.
+ *   n_reads = reads in the range, n_windows / n_placed / n_steps = their windows, placed windows and steps; read_windows[q] = W of read first_read + q.
+ * Range: reads [first_read, first_read + max_reads) (max_reads = 0: to the end).  The temporaries are 9 bytes and the step arrays another 17 bytes per minimizer index of
+ * the range, so the range bounds them.  first_read >= the number of reads: MDBG_OK with zero counts, which ends a caller's loop.  The step lists of the ranges of a
+ * partition, concatenated, are the whole call's; their support arrays add up to the whole call's.
+ * Invariant: over the whole store, and while no abundance has wrapped its u16, support_windows[u] == kc_sum[u] for every unitig — an abundance is a count of windows.
+ * mdbg_graph_read_paths: HOST arrays; mdbg_graph_read_paths_device: DEVICE arrays.  They belong to the context until its next read-path call or mdbg_destroy and share
+ * memory with no other result.  The number of kernel launches is fixed; the device variant waits for the device ONCE (the three counts and the defect flag in one
+ * read-back) when the range starts and ends where batches do — the whole store always does —, otherwise once more, up front, for the range's two offsets.
+ * mdbg_read_paths_ms: device time of the last read-path call (HIP events; 0 if it launched nothing).
+ * MDBG_E_STATE: no current unitig list (an edge, finalize, ingest, rewind or reset call ended it), the node table is not current, or a routed / partitioned context;
+ * MDBG_E_PARAM: a null pointer.  MDBG_E_CAPACITY: a list of 2^30 entries or more, or a range of 2^32 minimizers or more.  An empty context or an empty list gives MDBG_OK with every count zero (n_reads included) and no arrays.  MDBG_E_DEVICE: a list entry
+ * whose node index is not a row of the table, a probe that ran past the table's capacity, or a solid slot that is no row — the device sets a flag and never indexes
+ * outside or spins. */
+typedef struct mdbg_read_path_list {
+    uint64_t first_read, n_reads, n_windows, n_placed, n_steps, n_unitigs;
+    const uint64_t* ordinal; const uint32_t* read_windows;      /* n_reads: the read's ordinal, its number of windows W */
+    const uint64_t* step_offsets;                      /* n_reads + 1 */
+    const uint32_t* first_window; const uint32_t* step_windows; const uint32_t* unitig; const uint32_t* first_entry; const uint8_t* strand;      /* n_steps */
+    const uint64_t* support_windows; const uint64_t* support_steps;      /* n_unitigs */
+} mdbg_read_path_list;
+int mdbg_graph_read_paths(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out);
+int mdbg_graph_read_paths_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out);
+int mdbg_read_paths_ms(mdbg_ctx* ctx, double* ms);
+
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),
  * so the ranks may exchange SKETCHES instead (one all-gather), each rank then windows the global sketch but inserts only

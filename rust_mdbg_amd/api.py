@@ -96,6 +96,32 @@ COMPONENT_FIELDS = (("component", np.uint32, True), ("first_unitig", np.uint32, 
                     ("bases", np.uint64, False), ("kc_sum", np.uint64, False), ("circular", np.uint8, False))
 
 
+class ReadPathList(C.Structure):       # mdbg_read_path_list
+    _fields_ = [("first_read", C.c_uint64), ("n_reads", C.c_uint64), ("n_windows", C.c_uint64), ("n_placed", C.c_uint64), ("n_steps", C.c_uint64),
+                ("n_unitigs", C.c_uint64), ("ordinal", C.POINTER(C.c_uint64)), ("read_windows", C.POINTER(C.c_uint32)), ("step_offsets", C.POINTER(C.c_uint64)), ("first_window", C.POINTER(C.c_uint32)),
+                ("step_windows", C.POINTER(C.c_uint32)), ("unitig", C.POINTER(C.c_uint32)), ("first_entry", C.POINTER(C.c_uint32)), ("strand", C.POINTER(C.c_uint8)),
+                ("support_windows", C.POINTER(C.c_uint64)), ("support_steps", C.POINTER(C.c_uint64))]
+
+
+# (field, dtype, what it has one element of: "read", "step" or "unitig")
+READ_PATH_FIELDS = (("ordinal", np.uint64, "read"), ("read_windows", np.uint32, "read"), ("first_window", np.uint32, "step"), ("step_windows", np.uint32, "step"), ("unitig", np.uint32, "step"),
+                    ("first_entry", np.uint32, "step"), ("strand", np.uint8, "step"), ("support_windows", np.uint64, "unitig"), ("support_steps", np.uint64, "unitig"))
+
+
+def read_path_text(rp, circular):
+    """the lines of a .read_paths.tsv for a graph_read_paths() result: one per read in slot order, `ordinal<TAB>windows<TAB>placed<TAB>path`; path is `*` for a read
+    without steps, else its steps joined by `,`, each `first_window:n_windows:>NAME:first_entry` (`<` for strand 1) with NAME the unitig's utg%07d[lc] name.
+    circular: the list's `circular` array.  (windows of a read = the windows its minimizers give, placed = the sum over its steps.)"""
+    off = rp["step_offsets"].tolist()
+    fw, nw, un, fe, st = (rp[f].tolist() for f in ("first_window", "step_windows", "unitig", "first_entry", "strand"))
+    lines = []
+    for q, o in enumerate(rp["ordinal"].tolist()):
+        steps = range(off[q], off[q + 1])
+        path = ",".join("%d:%d:%s%s:%d" % (fw[p], nw[p], "<" if st[p] else ">", unitig_name(un[p], circular[un[p]]), fe[p]) for p in steps) or "*"
+        lines.append("%d\t%d\t%d\t%s\n" % (o, rp["read_windows"][q], sum(nw[p] for p in steps), path))
+    return "".join(lines)
+
+
 class ContigSeqs(C.Structure):         # mdbg_contig_seqs
     _fields_ = [("n_contigs", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64)),
                 ("unitig", C.POINTER(C.c_uint64))]
@@ -153,7 +179,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
-           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -253,6 +279,9 @@ def load_library():
     L.mdbg_graph_node_seqs.argtypes = [vp, u64, u64, u64, C.POINTER(NodeSeqs)]
     L.mdbg_graph_node_seqs_device.argtypes = [vp, u64, u64, u64, C.POINTER(NodeSeqs)]
     L.mdbg_node_seqs_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mdbg_graph_read_paths.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
+    L.mdbg_graph_read_paths_device.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
+    L.mdbg_read_paths_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -568,6 +597,31 @@ class Mdbg:
         cl = ComponentList()
         self._chk(self.L.mdbg_graph_components_device(self.h, C.byref(cl)))
         return cl
+
+    def graph_read_paths(self, first_read=0, max_reads=0):
+        """the resident reads [first_read, first_read + max_reads) (0: to the end; slot order) threaded through the current unitig list (the last graph_unitigs* /
+        graph_simplify* call) on the GPU: which unitigs, in which order and orientation, each read walks (mdbg_graph_read_paths, include/mdbg_hip.h).  Leaves the list
+        as it is.  -> dict(first_read, n_reads, n_windows, n_placed, n_steps, n_unitigs; per read ordinal, read_windows, step_offsets[n_reads + 1]; per step first_window,
+        step_windows, unitig, first_entry, strand; per unitig support_windows, support_steps)"""
+        rp = ReadPathList()
+        self._chk(self.L.mdbg_graph_read_paths(self.h, first_read, max_reads, C.byref(rp)))
+        n = dict(read=int(rp.n_reads), step=int(rp.n_steps), unitig=int(rp.n_unitigs))
+        out = {f: _np(getattr(rp, f), n[per], t) for f, t, per in READ_PATH_FIELDS}
+        out["step_offsets"] = _np(rp.step_offsets, n["read"] + 1, np.uint64) if rp.step_offsets else np.zeros(1, np.uint64)
+        out.update(first_read=int(rp.first_read), n_reads=n["read"], n_windows=int(rp.n_windows), n_placed=int(rp.n_placed), n_steps=n["step"], n_unitigs=n["unitig"])
+        return out
+
+    def graph_read_paths_device(self, first_read=0, max_reads=0):
+        """-> ReadPathList with DEVICE pointers (valid until the next read-path call)"""
+        rp = ReadPathList()
+        self._chk(self.L.mdbg_graph_read_paths_device(self.h, first_read, max_reads, C.byref(rp)))
+        return rp
+
+    def read_paths_ms(self):
+        """device time of the last graph_read_paths* call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_read_paths_ms(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def kept_reads(self):
         """the resident read store of a keep_reads context -> dict(n_reads, n_bases, bytes); bytes = n_bases / 4 + 8 per read + 9 per exception, up to the

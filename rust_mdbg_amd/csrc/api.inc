@@ -20,6 +20,7 @@
 #include "components.h"
 #include "contigs.h"
 #include "node_seqs.h"
+#include "read_paths.h"
 
 #include "blocks.inc"
 #include "context.inc"
@@ -27,7 +28,7 @@
 #include "ingest_api.inc"
 extern "C" {                   // entry points and their static helpers only from here on
 #include "finalize_api.inc"
-#include "graph_api.inc"      // edges, unitigs, simplification, contigs, node sequences
+#include "graph_api.inc"      // edges, unitigs, simplification, contigs, node sequences, read paths
 #include "import_api.inc"
 }
 #include "route_api.inc"      // multi-GPU routing

@@ -115,6 +115,9 @@ struct mdbg_ctx {
     bool nseq_prefix_ok = false;             // nsb holds the prefix of the rows' lengths of the node table as it stands (dropped wherever nodes_ok is cleared or set)
     HostRaw<u8> hn_bases; HostRaw<u64> hn_off;      // host copy of the last mdbg_graph_node_seqs chunk
     double ms_node_seqs = 0;                 // device time of the last node-sequence gather kernel
+    ReadPathBuffers* rpb = nullptr;          // read paths over the unitig list (read_paths.hip), created on first use; its result buffers live until the next read-path call
+    HostRaw<u64> hr_ord, hr_off, hr_supw, hr_sups; HostRaw<u32> hr_rw, hr_fw, hr_nw, hr_unitig, hr_fe; HostRaw<u8> hr_strand;      // host copy of the last mdbg_graph_read_paths
+    double ms_read_paths = 0;                // device time of the last read-path call
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -400,6 +403,7 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     if (c->compb) component_buffers_destroy(c->compb);
     if (c->cb) contig_buffers_destroy(c->cb);
     if (c->nsb) node_seq_buffers_destroy(c->nsb);
+    if (c->rpb) read_path_buffers_destroy(c->rpb);
     if (c->h_scal) (void)hipHostFree(c->h_scal);
     for (auto& g : c->stage) if (g.st) (void)hipStreamDestroy(g.st);
     if (c->stream) (void)hipStreamDestroy(c->stream);

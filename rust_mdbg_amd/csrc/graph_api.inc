@@ -238,3 +238,77 @@ int mdbg_node_seqs_ms(mdbg_ctx* c, double* ms) {
     *ms = c->ms_node_seqs;
     return MDBG_OK;
 }
+
+// ---- the resident reads threaded through the current unitig list (place_windows.hip, read_paths.hip) ---------
+// roff[r] where the host knows it without asking the device: r is the first slot of a batch, or one past its last
+static bool known_read_offset(const mdbg_ctx* c, u64 r, u64* v) {
+    for (const Batch& b : c->batches) {
+        if (b.slot0 == r) { *v = b.m0; return true; }
+        if ((u64)b.slot0 + b.n_reads == r) { *v = b.m1; return true; }
+    }
+    return false;
+}
+static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    out->first_read = first_read;
+    c->ms_read_paths = 0;
+    if (c->routed || c->own_world > 1) return fail(c, MDBG_E_STATE, "read paths are single-GPU only: not available on a routed or partitioned context");
+    if (!c->ulist_ok) return fail(c, MDBG_E_STATE, "no current unitig list on this context (call mdbg_graph_unitigs* or mdbg_graph_simplify* first)");
+    if (!c->nodes_ok && !(c->cap == 0 || c->M == 0)) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
+    const UnitigResult& ul = c->last_ul;
+    if (ul.n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;      // an empty context, an empty list, a range behind the store
+    if (ul.n_entries >= (1ull << 30) || c->nodes_n >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
+    hipStream_t s = c->stream;
+    const u64 r0 = first_read, r1 = max_reads && max_reads < c->n_slots - r0 ? r0 + max_reads : c->n_slots;
+    ReadPathRange rg{};
+    const bool known0 = known_read_offset(c, r0, &rg.i0), known1 = known_read_offset(c, r1, &rg.i1);
+    if (!known0) HIPCHK(c, hipMemcpyAsync(&rg.i0, c->roff.as<u64>() + r0, 8, hipMemcpyDeviceToHost, s));
+    if (!known1) HIPCHK(c, hipMemcpyAsync(&rg.i1, c->roff.as<u64>() + r1, 8, hipMemcpyDeviceToHost, s));
+    if (!(known0 && known1)) HIPCHK(c, hipStreamSynchronize(s));      // (a range that starts or ends inside a batch: one more wait, for its two offsets)
+    if (rg.i1 < rg.i0 || rg.i1 > c->M) return fail(c, MDBG_E_DEVICE, "the read offsets of the store are not ascending");
+    if (rg.i1 - rg.i0 >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 minimizers in the range of reads");
+    for (Batch& b : c->batches) fill_mread_of(c, b);
+    FinArgs F = c->finF;
+    F.mh = c->mh.as<u64>(); F.roff = c->roff.as<u64>(); F.mread = c->mread.as<u32>();
+    rg.roff = F.roff; rg.mread = F.mread; rg.first_read = (u32)r0; rg.n_reads = (u32)(r1 - r0); rg.k = c->P.k;
+    rg.by_slot0 = F.bt.by_slot0; rg.by_slot_first = F.bt.by_slot_first; rg.n_batches = F.bt.n;
+    if (!c->rpb) c->rpb = read_path_buffers_create();
+    ReadPathPlan plan;
+    hipError_t he = read_paths_begin(c->rpb, ul, F.o_index, c->nodes_n, rg, s, &plan);
+    if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "read_paths_begin", he);
+    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
+    ReadPathResult r;
+    he = read_paths_end(c->rpb, ul, rg, s, &r);
+    if (he != hipSuccess) return fail(c, he == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, "read_paths_end", he);
+    c->ms_read_paths = r.ms;
+    if (r.defect & RP_DEFECT_ENTRY) return fail(c, MDBG_E_DEVICE, "an entry of the unitig list names a node index that is not a row of the node table");
+    if (r.defect & RP_DEFECT_PROBE) return fail(c, MDBG_E_DEVICE, "a probe sequence of the read paths visited every slot of the table");
+    if (r.defect) return fail(c, MDBG_E_DEVICE, "a solid slot's first sighting is no row of the node table");
+    const u64 nr = r.n_reads, ns = r.n_steps, U = r.n_unitigs;
+    out->n_reads = nr; out->n_windows = r.n_windows; out->n_placed = r.n_placed; out->n_steps = ns; out->n_unitigs = U;
+    if (!to_host) {
+        out->ordinal = r.ordinal; out->read_windows = r.read_windows; out->step_offsets = r.step_offsets; out->first_window = r.first_window; out->step_windows = r.step_windows; out->unitig = r.unitig;
+        out->first_entry = r.first_entry; out->strand = r.strand; out->support_windows = r.support_windows; out->support_steps = r.support_steps;
+        return MDBG_OK;
+    }
+    const char* const what = "host copy of the read paths";
+    int e;
+    if ((e = copy_out(c, c->hr_ord, r.ordinal, nr, what, &out->ordinal)) || (e = copy_out(c, c->hr_rw, r.read_windows, nr, what, &out->read_windows)) || (e = copy_out(c, c->hr_off, r.step_offsets, nr + 1, what, &out->step_offsets)) ||
+        (e = copy_out(c, c->hr_fw, r.first_window, ns, what, &out->first_window)) || (e = copy_out(c, c->hr_nw, r.step_windows, ns, what, &out->step_windows)) ||
+        (e = copy_out(c, c->hr_unitig, r.unitig, ns, what, &out->unitig)) || (e = copy_out(c, c->hr_fe, r.first_entry, ns, what, &out->first_entry)) ||
+        (e = copy_out(c, c->hr_strand, r.strand, ns, what, &out->strand)) || (e = copy_out(c, c->hr_supw, r.support_windows, U, what, &out->support_windows)) ||
+        (e = copy_out(c, c->hr_sups, r.support_steps, U, what, &out->support_steps))) return e;
+    return MDBG_OK;
+}
+int mdbg_graph_read_paths(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out) { return read_paths_impl(c, first_read, max_reads, out, true); }
+int mdbg_graph_read_paths_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out) { return read_paths_impl(c, first_read, max_reads, out, false); }
+int mdbg_read_paths_ms(mdbg_ctx* c, double* ms) {
+    if (!c || !ms) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    *ms = c->ms_read_paths;
+    return MDBG_OK;
+}

@@ -1,0 +1,194 @@
+// read_paths.hip — the resident reads threaded through the current unitig list, on the GPU (gfx950): everything of the stage except the table lookup.
+// Definition: include/mdbg_hip.h (mdbg_graph_read_paths).  Input: the device arrays of a unitig list (unitigs.hip), the node table's `index` column, the
+// store's read offsets and minimizer -> read map, and the per-index codes that place_windows_kernel (place_windows.hip, main translation unit) writes.
+//
+//   (memset)            entry_of_row <- NONE, the support sums and the counters <- 0
+//   entry_kernel        one thread per list entry e: the row of node[e] by binary search (rows are in index order) gets e; unitig_of_entry[e] by binary
+//                       search in offsets.  A node index that is no row sets RP_DEFECT_ENTRY
+//   place_windows_kernel  (place_windows.hip) code[t] = entry | strand << 31 of the window that starts at index i0 + t, or NONE
+//   head_kernel         flag[t] = 1 iff code[t] is a window and does not continue code[t - 1] inside the same read (same unitig and strand, the entry
+//                       one further in the read's direction, modulo the size on a circular unitig)
+//   (rocPRIM)           pos = exclusive scan of flag: a window's step is pos + flag - 1, the range's steps are numbered in index order
+//   steps_kernel        a head writes its step's first_window, unitig, first_entry, strand; the LAST window of a run (the next code is NONE, a head, or
+//                       the range ends) writes its window number + 1 into step_windows — the p-th head and the p-th run end belong to one step, so
+//                       nobody walks a run
+//   finish_kernel       one thread per step: step_windows -= first_window; integer atomics add the step to its unitig's two sums
+//   reads_kernel        one thread per read: step_offsets[q] = pos at the read's first index, ordinal[q] from the batch table, read_windows[q] from its offsets
+//
+// All sums are integers and every position comes from the scan: two calls give identical arrays.  No loop but the two binary searches; the number of
+// launches is fixed.
+#include <cstring>
+
+#include "read_paths.h"
+#include "graph_common.h"
+
+struct ReadPathBuffers {
+    Buf entry_of_row, unitig_of_entry, code, flag, pos, tmp, counters;
+    Buf ordinal, read_windows, step_offsets, first_window, step_windows, unitig, first_entry, strand, sup_w, sup_s;      // the result
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~ReadPathBuffers() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+};
+
+namespace {
+
+struct RpArgs {
+    u64 U, N, n_rows; const u64* offsets; const u32* node; const u8* circ; const u32* index;
+    u32* entry_of_row; u32* unitig_of_entry;
+    const u64* roff; const u32* mread; u32 r0, nr, k; u64 i0, n_idx;
+    const u32* code; u8* flag; const u32* pos; u64* counters;
+    u64* ordinal; u32* read_windows; u64* step_offsets; u32* first_window; u32* step_windows; u32* unitig; u32* first_entry; u8* strand; u64* sup_w; u64* sup_s;
+    const u32* by_slot0; const u64* by_slot_first; u32 n_batches;
+};
+
+__device__ inline void set_defect(u64* counters, u32 what) { atomicOr((unsigned long long*)(counters + RP_C_DEFECT), (unsigned long long)what); }
+
+__global__ __launch_bounds__(256) void entry_kernel(RpArgs a) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.N) return;
+    {   // the unitig that holds entry e: the last u with offsets[u] <= e
+        u64 lo = 0, hi = a.U - 1;
+        while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (a.offsets[mid] <= e) lo = mid; else hi = mid - 1; }
+        a.unitig_of_entry[e] = (u32)lo;
+    }
+    const u32 idx = a.node[e];
+    u64 lo = 0, hi = a.n_rows;                 // as row_of (unitigs.hip)
+    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (a.index[mid] < idx) lo = mid + 1; else hi = mid; }
+    if (lo < a.n_rows && a.index[lo] == idx) a.entry_of_row[lo] = (u32)e;
+    else set_defect(a.counters, RP_DEFECT_ENTRY);
+}
+
+// does the placed window with code c continue the placed window with code pc (the index in front of it, same read)?
+__device__ inline bool continues(const RpArgs& a, u32 pc, u32 c) {
+    if ((pc ^ c) & RP_STRAND) return false;
+    const u32 e = c & ~RP_STRAND, pe = pc & ~RP_STRAND;
+    const u32 u = a.unitig_of_entry[e];
+    if (a.unitig_of_entry[pe] != u) return false;
+    const u64 first = a.offsets[u], last = a.offsets[u + 1] - 1;
+    const bool circ = a.circ[u] != 0;
+    if (!(c & RP_STRAND)) return e == pe + 1 || (circ && pe == last && e == first);
+    return pe == e + 1 || (circ && pe == first && e == last);
+}
+
+__global__ __launch_bounds__(256) void head_kernel(RpArgs a) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.n_idx) return;
+    const u32 c = a.code[t];
+    u8 f = 0;
+    if (c != RP_NONE) {
+        f = 1;
+        const u64 i = a.i0 + t;
+        if (t > 0 && i > a.roff[a.mread[i]]) {             // (the range starts at a read's first index)
+            const u32 pc = a.code[t - 1];
+            if (pc != RP_NONE && continues(a, pc, c)) f = 0;
+        }
+    }
+    a.flag[t] = f;
+}
+
+__global__ __launch_bounds__(256) void steps_kernel(RpArgs a) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.n_idx) return;
+    const u32 f = a.flag[t], before = a.pos[t];
+    if (t == a.n_idx - 1) a.counters[RP_C_STEPS] = (u64)before + f;
+    const u32 c = a.code[t];
+    if (c == RP_NONE) return;
+    const u32 p = before + f - 1;                          // (a window that is no head has a head in front of it: before >= 1)
+    const u64 i = a.i0 + t;
+    const u32 w = (u32)(i - a.roff[a.mread[i]]);
+    if (f) {
+        const u32 e = c & ~RP_STRAND, u = a.unitig_of_entry[e];
+        a.first_window[p] = w; a.unitig[p] = u; a.first_entry[p] = (u32)(e - a.offsets[u]); a.strand[p] = (u8)(c >> 31);
+    }
+    const bool last = t + 1 == a.n_idx || a.code[t + 1] == RP_NONE || a.flag[t + 1] != 0;      // (a read's first window is a head or no window)
+    if (last) a.step_windows[p] = w + 1;
+}
+
+__global__ __launch_bounds__(256) void finish_kernel(RpArgs a) {
+    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.counters[RP_C_STEPS]) return;               // (the grid is sized for one step per index)
+    const u32 n = a.step_windows[p] - a.first_window[p];
+    a.step_windows[p] = n;
+    const u32 u = a.unitig[p];
+    atomicAdd((unsigned long long*)(a.sup_s + u), 1ull);
+    atomicAdd((unsigned long long*)(a.sup_w + u), (unsigned long long)n);
+}
+
+__global__ __launch_bounds__(256) void reads_kernel(RpArgs a) {
+    const u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q > a.nr) return;
+    const u64 t = a.roff[a.r0 + q] - a.i0;
+    a.step_offsets[q] = t < a.n_idx ? (u64)a.pos[t] : a.n_idx ? (u64)a.pos[a.n_idx - 1] + a.flag[a.n_idx - 1] : 0;
+    if (q == a.nr) return;
+    const u64 n_min = a.roff[a.r0 + q + 1] - a.roff[a.r0 + q];
+    a.read_windows[q] = n_min > a.k ? (u32)(n_min - a.k + 1) : 0u;      // src/main.rs:756-759
+    const u32 slot = a.r0 + (u32)q;
+    u32 lo = 0, hi = a.n_batches - 1;                      // as rep_ordinal (finalize.hip): the last batch whose first slot is <= slot
+    while (lo < hi) { const u32 mid = lo + ((hi - lo + 1) >> 1); if (a.by_slot0[mid] <= slot) lo = mid; else hi = mid - 1; }
+    a.ordinal[q] = a.by_slot_first[lo] + (slot - a.by_slot0[lo]);
+}
+
+RpArgs args_of(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& rg) {
+    RpArgs a; memset(&a, 0, sizeof a);
+    a.U = ul.n_unitigs; a.N = ul.n_entries; a.offsets = ul.offsets; a.node = ul.node; a.circ = ul.circular;
+    a.entry_of_row = B->entry_of_row.as<u32>(); a.unitig_of_entry = B->unitig_of_entry.as<u32>();
+    a.roff = rg.roff; a.mread = rg.mread; a.r0 = rg.first_read; a.nr = rg.n_reads; a.k = rg.k; a.i0 = rg.i0; a.n_idx = rg.i1 - rg.i0;
+    a.code = B->code.as<u32>(); a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.counters = B->counters.as<u64>();
+    a.ordinal = B->ordinal.as<u64>(); a.read_windows = B->read_windows.as<u32>(); a.step_offsets = B->step_offsets.as<u64>(); a.first_window = B->first_window.as<u32>(); a.step_windows = B->step_windows.as<u32>();
+    a.unitig = B->unitig.as<u32>(); a.first_entry = B->first_entry.as<u32>(); a.strand = B->strand.as<u8>(); a.sup_w = B->sup_w.as<u64>(); a.sup_s = B->sup_s.as<u64>();
+    a.by_slot0 = rg.by_slot0; a.by_slot_first = rg.by_slot_first; a.n_batches = rg.n_batches;
+    return a;
+}
+
+}  // namespace
+
+ReadPathBuffers* read_path_buffers_create() { return new ReadPathBuffers(); }
+void read_path_buffers_destroy(ReadPathBuffers* b) { delete b; }
+
+hipError_t read_paths_begin(ReadPathBuffers* B, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan) {
+    memset(plan, 0, sizeof *plan);
+    const u64 U = ul.n_unitigs, N = ul.n_entries, n_idx = rg.i1 - rg.i0, nr = rg.n_reads;
+    if (U == 0 || N == 0 || n_rows == 0 || N >= (1ull << 30) || n_rows >= (1ull << 30) || n_idx >= 0xFFFFFFF0ull) return hipErrorInvalidValue;      // (read_paths_impl has answered MDBG_E_CAPACITY or returned before)
+    if (!B->ev0) { GHIP(hipEventCreate(&B->ev0)); GHIP(hipEventCreate(&B->ev1)); }
+    // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
+    GHIP(B->counters.ensure(RP_C_N * 8));
+    GHIP(B->entry_of_row.ensure(n_rows * 4)); GHIP(B->unitig_of_entry.ensure(N * 4));
+    GHIP(B->code.ensure(n_idx * 4 + 4)); GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
+    GHIP(B->ordinal.ensure(nr * 8 + 8)); GHIP(B->read_windows.ensure(nr * 4 + 4)); GHIP(B->step_offsets.ensure((nr + 1) * 8));
+    GHIP(B->first_window.ensure(n_idx * 4 + 4)); GHIP(B->step_windows.ensure(n_idx * 4 + 4)); GHIP(B->unitig.ensure(n_idx * 4 + 4)); GHIP(B->first_entry.ensure(n_idx * 4 + 4));
+    GHIP(B->strand.ensure(n_idx + 4)); GHIP(B->sup_w.ensure(U * 8)); GHIP(B->sup_s.ensure(U * 8));
+    if (n_idx) { size_t tb = 0; GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); GHIP(B->tmp.ensure(tb + 256)); }
+    GHIP(hipEventRecord(B->ev0, s));
+    GHIP(hipMemsetAsync(B->counters.p, 0, RP_C_N * 8, s));
+    GHIP(hipMemsetAsync(B->entry_of_row.p, 0xFF, n_rows * 4, s));
+    GHIP(hipMemsetAsync(B->sup_w.p, 0, U * 8, s)); GHIP(hipMemsetAsync(B->sup_s.p, 0, U * 8, s));
+    RpArgs a = args_of(B, ul, rg);
+    a.index = index; a.n_rows = n_rows;
+    hipLaunchKernelGGL(entry_kernel, dim3(grid_for(N)), dim3(256), 0, s, a);
+    plan->entry_of_row = a.entry_of_row; plan->n_rows = n_rows; plan->ori = ul.ori; plan->code = B->code.as<u32>(); plan->counters = a.counters;
+    return hipGetLastError();
+}
+
+hipError_t read_paths_end(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, hipStream_t s, ReadPathResult* out) {
+    memset(out, 0, sizeof *out);
+    const RpArgs a = args_of(B, ul, rg);
+    if (a.n_idx) {
+        const unsigned gi = grid_for(a.n_idx);
+        hipLaunchKernelGGL(head_kernel, dim3(gi), dim3(256), 0, s, a);
+        GHIP(excl_scan(B->tmp, B->flag.as<u8>(), B->pos.as<u32>(), (size_t)a.n_idx, s));
+        hipLaunchKernelGGL(steps_kernel, dim3(gi), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(finish_kernel, dim3(gi), dim3(256), 0, s, a);
+    }
+    hipLaunchKernelGGL(reads_kernel, dim3(grid_for((u64)a.nr + 1)), dim3(256), 0, s, a);
+    GHIP(hipGetLastError());
+    GHIP(hipEventRecord(B->ev1, s));
+    u64 h[RP_C_N];
+    GHIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
+    GHIP(hipStreamSynchronize(s));
+    if (hipEventElapsedTime(&out->ms, B->ev0, B->ev1) != hipSuccess) { (void)hipGetLastError(); out->ms = 0; }
+    out->defect = (u32)h[RP_C_DEFECT];
+    if (out->defect) return hipSuccess;
+    out->n_reads = a.nr; out->n_windows = h[RP_C_WINDOWS]; out->n_placed = h[RP_C_PLACED]; out->n_steps = h[RP_C_STEPS]; out->n_unitigs = a.U;
+    out->ordinal = a.ordinal; out->read_windows = a.read_windows; out->step_offsets = a.step_offsets; out->first_window = a.first_window; out->step_windows = a.step_windows; out->unitig = a.unitig;
+    out->first_entry = a.first_entry; out->strand = a.strand; out->support_windows = a.sup_w; out->support_steps = a.sup_s;
+    return hipSuccess;
+}

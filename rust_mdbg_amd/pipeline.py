@@ -7,8 +7,10 @@ import queue
 import threading
 import time
 
-from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, unitig_name
+from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, read_path_text, unitig_name
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
+
+READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths call of run_file
 
 
 def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max):
@@ -21,7 +23,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -31,6 +33,9 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     components (with contigs): also write <prefix>.unitigs.components.tsv, one line `utgNAME<TAB>component` per unitig: the connected component of the unitig
     graph each unitig lies in (Mdbg.graph_components; numbered by their smallest unitig), and with simplify <prefix>.msimpl.components.tsv for the simplified
     list.  Adds n_components (and n_components_simplified).  The other files are unchanged.
+    read_paths (with contigs): also write <prefix>.unitigs.read_paths.tsv, one line `ordinal<TAB>windows<TAB>placed<TAB>path` per read in the order of the store:
+    which unitigs the read walks (Mdbg.graph_read_paths; api.read_path_text gives the format), and with simplify <prefix>.msimpl.read_paths.tsv for the
+    simplified list.  Adds n_read_steps (and n_read_steps_simplified).  The other files are unchanged.
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -151,11 +156,24 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 with open(path_, "w") as f:
                     f.write("".join("%s\t%d\n" % (unitig_name(i, ul.circular[i]), c) for i, c in enumerate(cc["component"].tolist())))
                 comp[key] = cc["n_components"]
+            def write_read_paths(ul, path_, key):        # the reads in bounded ranges: the call's temporaries grow with the range's minimizers
+                comp[key] = 0
+                first = 0
+                with open(path_, "w") as f:
+                    while True:
+                        rp = m.graph_read_paths(first, READ_PATH_CHUNK)
+                        if not rp["n_reads"]:
+                            break
+                        f.write(read_path_text(rp, ul.circular))
+                        comp[key] += rp["n_steps"]
+                        first += rp["n_reads"]
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
                 if components:
                     write_components(sl, prefix + ".msimpl.components.tsv", "n_components_simplified")
+                if read_paths:
+                    write_read_paths(sl, prefix + ".msimpl.read_paths.tsv", "n_read_steps_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
@@ -165,6 +183,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 ctg = Contigs(ul, nodes["n_nodes"])
                 if components:
                     write_components(ul, prefix + ".unitigs.components.tsv", "n_components")
+                if read_paths:
+                    write_read_paths(ul, prefix + ".unitigs.read_paths.tsv", "n_read_steps")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
