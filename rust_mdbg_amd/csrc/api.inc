@@ -23,6 +23,7 @@
 #include "read_paths.h"
 
 #include "blocks.inc"
+#include "results.inc"      // the derived graph results and which of them are current
 #include "context.inc"
 #include "store.inc"
 #include "ingest_api.inc"

@@ -67,7 +67,6 @@ struct mdbg_ctx {
                                              // first sighting once more, and nothing clears the mark left on the old one: fin_setup then gives the claim map up (claims_ok)
     DevBuf bm_first, bm_solid, pre_first, pre_solid, popc_tmp, bt_dev, fin_out, solid_list, fin_order;
     DevBuf bm_local, pre_local, pre_local2;       // partitioned finalize: THIS rank's solid bitmap as it was before the merge over the ranks, and its prefix (the order of the partition's rows)
-    HostRaw<u64> h_keys, h_shift_full, h_src_read, h_src_start, h_src_end; HostRaw<u32> h_index, h_seqlen; HostRaw<u16> h_abund, h_shift; HostRaw<u8> h_rev;
     // sketch_only outputs
     std::vector<u64> so_hash, so_pos, so_off;
     // query_batch outputs
@@ -89,7 +88,6 @@ struct mdbg_ctx {
     FinArgs finF{}; u64 fin_words = 0, fin_bits = 0; bool fin_open = false;      // fin_bits: dense ordered indices in use (the batches' minimizers)
     u64 fin_rows_guess = 0;      // fin_rows_guess: rows the next local finalize writes before it knows the count (0: none yet)
     std::vector<u8> bt_host;                 // staging of the batch table (fin_setup)
-    EdgeBuffers* eb = nullptr;               // edge construction (edges.hip), created on first use
     DevBuf own_hist;                         // mdbg_owner_counts
     DevBuf own_lists; u64 own_lists_n = 0;   // window lists of the batches this context owns windows of (u32 each), see Batch::list_off
     DevBuf listed_multi; std::vector<ListedBatch> listed_multi_host;      // descriptors of the batches that share one listed-insertion launch
@@ -97,27 +95,8 @@ struct mdbg_ctx {
     DevBuf ol_cnt, ol_off, ol_tot, ol_list, ol_owner;  // mdbg_owner_lists scratch / result
     DevBuf lmer_set; u64 lmer_mask = 0; bool lmer_on = false; u32 lmer_all_ones = 0;      // --lmer-counts: mdbg_set_lmer_filter
     DevBuf w_jstar, w_count, w_ctr, w_start, w_fill, w_occ, w_sorted, w_ath;   // nodes whose u16 abundance wrapped (resolve_wrapped)
-    u64 nodes_n = 0; bool nodes_ok = false;  // device node table of the last local finalize is intact
-    HostRaw<u32> he_n1, he_n2, he_ov; HostRaw<u8> he_o1, he_o2;           // host copy of the last edge list
-    EdgeResult last_edges{}; bool edges_ok = false;                        // device edge list of the last edge call; edges_ok: it belongs to the node table as it stands (unitigs.hip reads both)
-    UnitigBuffers* ub = nullptr;             // unitig compaction (unitigs.hip), created on first use
-    HostRaw<u64> hu_off, hu_sread, hu_sbegin, hu_dst, hu_length, hu_kc; HostRaw<u32> hu_node, hu_len, hu_n1, hu_n2, hu_ov; HostRaw<u8> hu_ori, hu_rc, hu_circ, hu_o1, hu_o2;   // host copy of the last unitig list
-    std::vector<u64> hs_unitigs, hs_nodes;   // per-step removal counts of the last mdbg_graph_simplify
-    UnitigResult last_ul{}; bool ulist_ok = false;      // device unitig list of the last unitig / simplify call; ulist_ok: it is current (no edge, finalize, ingest or reset call since)
-    ComponentBuffers* compb = nullptr;       // connected components of the unitig list (components.hip), created on first use; its result buffers live until the next component call or simplify call with a component step
-    HostRaw<u32> hk_comp, hk_first, hk_unitigs; HostRaw<u64> hk_nodes, hk_bases, hk_kc; HostRaw<u8> hk_circ;      // host copy of the last mdbg_graph_components
-    ContigBuffers* cb = nullptr;             // contig stitching (contigs.hip), created on first use; its result buffers live until the next contig call
+    Results res;                             // what is derived from the table and kept for the caller, and which of it is current (results.inc)
     DevBuf kp_exc_pos, kp_exc_val, kp_cnt;   // keeping an ASCII batch: where the pack kernel appends the (unordered) exceptions, and their count
-    HostRaw<u8> hc_bases; HostRaw<u64> hc_off, hc_unitig;      // host copy of the last mdbg_graph_contigs
-    double ms_stitch = 0;                    // device time of the last stitch kernel
-    NodeSeqBuffers* nsb = nullptr;           // node sequences from the kept reads (node_seqs.hip), created on first use; its result buffers live until the next node-sequence call
-    bool nodes_none = false;                 // the last finalize found nothing resident: its table of no rows is current (ended where nodes_ok is)
-    bool nseq_prefix_ok = false;             // nsb holds the prefix of the rows' lengths of the node table as it stands (dropped wherever nodes_ok is cleared or set)
-    HostRaw<u8> hn_bases; HostRaw<u64> hn_off;      // host copy of the last mdbg_graph_node_seqs chunk
-    double ms_node_seqs = 0;                 // device time of the last node-sequence gather kernel
-    ReadPathBuffers* rpb = nullptr;          // read paths over the unitig list (read_paths.hip), created on first use; its result buffers live until the next read-path call
-    HostRaw<u64> hr_ord, hr_off, hr_supw, hr_sups; HostRaw<u32> hr_rw, hr_fw, hr_nw, hr_unitig, hr_fe; HostRaw<u8> hr_strand;      // host copy of the last mdbg_graph_read_paths
-    double ms_read_paths = 0;                // device time of the last read-path call
     std::vector<hipEvent_t> tile_ev; size_t tile_ev_used = 0; double ms_tile = 0; u64 n_tile_launches = 0, n_tile_bases = 0;
 };
 
@@ -130,15 +109,24 @@ int fail(mdbg_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
     if (c) { std::lock_guard<std::mutex> g_(c->err_mu); c->err = buf; if (code == MDBG_E_DEVICE || code == MDBG_E_ALPHABET || code == MDBG_E_NOMEM) c->poisoned = code; }
     return code;
 }
+int fail_hip(mdbg_ctx* c, const char* what, hipError_t e) { return fail(c, e == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, what, e); }
 #define MDBG_LOCK(c) std::lock_guard<std::recursive_mutex> lock_((c)->mu)
-#define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail((c), e_ == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, #call, e_); } while (0)
-// one column of a copy-out: *host <- the context's host copy `h` of the n elements at `dev` (device memory).  Blocking; `what` names the list in the error.
-template <class T> int copy_out(mdbg_ctx* c, HostRaw<T>& h, const T* dev, size_t n, const char* what, const T** host) {
-    if (!h.resize(n)) return fail(c, MDBG_E_NOMEM, what);
-    if (n) { const hipError_t e = hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost); if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? MDBG_E_NOMEM : MDBG_E_DEVICE, what, e); }
-    *host = h.data();
-    return MDBG_OK;
-}
+#define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail_hip((c), #call, e_); } while (0)
+// how an entry point opens: its pointers checked, the lock taken (for the rest of the function), the context's device current, a poisoned context refused
+#define MDBG_ENTER(c, args_ok) if (!(c) || !(args_ok)) return MDBG_E_PARAM; MDBG_LOCK(c); (void)hipSetDevice((c)->dev); if ((c)->poisoned) return fail((c), MDBG_E_STATE, "context is in an error state")
+// Hands a list's columns to the caller, one col() per column: the device pointer as it is, or (to_host) the context's host copy `h` of the n elements at `dev`, filled by a
+// blocking copy.  `what` names the list in an error; the first error stays in `err` and the columns behind it are left alone.
+struct HandOver {
+    mdbg_ctx* c; const char* what; bool to_host; int err = MDBG_OK;
+    template <class T> void col(const T* dev, size_t n, HostRaw<T>& h, const T** dst) {
+        if (err) return;
+        if (!to_host) { *dst = dev; return; }
+        if (!h.resize(n)) { err = fail(c, MDBG_E_NOMEM, what); return; }
+        if (n) { const hipError_t e = hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost); if (e != hipSuccess) { err = fail_hip(c, what, e); return; } }
+        *dst = h.data();
+    }
+};
+bool nothing_resident(const mdbg_ctx* c) { return c->cap == 0 || c->M == 0; }      // no table yet, or no minimizer in the store: an empty context
 
 u64* scal(mdbg_ctx* c) { return c->scalars.as<u64>(); }
 // with_fin: also the two finalize counters (shard arrays 2, 3 -> SC_FIN1, SC_FIN2)
@@ -187,10 +175,6 @@ int write_scalar(mdbg_ctx* c, int idx, u64 v) {
     return MDBG_OK;
 }
 
-// Which derived results (node table <- edge list <- unitig list) an operation ends, each with all that is built on it: whatever changes the table (insertion, clear,
-// finalize's setup) ends the node table; an edge call the edge list; an ingest the unitig list (mdbg_graph_contigs).  The flags are set where a result is made.
-enum ResultsFrom { FROM_NODES, FROM_EDGES, FROM_UNITIGS };
-void invalidate_results(mdbg_ctx* c, ResultsFrom from) { if (from <= FROM_NODES) { c->nodes_ok = false; c->nodes_none = false; c->nseq_prefix_ok = false; } if (from <= FROM_EDGES) c->edges_ok = false; c->ulist_ok = false; }
 static void fill_mread_of(mdbg_ctx* c, Batch& b);
 // largest hash a selected minimizer can have (0: unknown)
 double owner_hash_bound(const mdbg_ctx* c) {
@@ -296,7 +280,7 @@ int table_reserve(mdbg_ctx* c, u64 incoming) {
 }
 
 int clear_table(mdbg_ctx* c) {
-    invalidate_results(c, FROM_NODES);
+    c->res.invalidate(FROM_NODES);
     // the key counter's shards, SC_NDISTINCT + SC_NWINDOWS, SC_IMPORTERR, SC_PROBEERR: zeroed by the launch that clears the table (stream-ordered, no host sync) — or by
     // a launch of their own when there is no table yet
     ZeroList z{};
@@ -398,16 +382,10 @@ void mdbg_destroy(mdbg_ctx* c) {          // the caller guarantees that no other
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (auto e : c->tile_ev) (void)hipEventDestroy(e);
-    if (c->eb) edge_buffers_destroy(c->eb);
-    if (c->ub) unitig_buffers_destroy(c->ub);
-    if (c->compb) component_buffers_destroy(c->compb);
-    if (c->cb) contig_buffers_destroy(c->cb);
-    if (c->nsb) node_seq_buffers_destroy(c->nsb);
-    if (c->rpb) read_path_buffers_destroy(c->rpb);
     if (c->h_scal) (void)hipHostFree(c->h_scal);
     for (auto& g : c->stage) if (g.st) (void)hipStreamDestroy(g.st);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                              // (with it the stages' buffers, Results)
 }
 
 int mdbg_sync(mdbg_ctx* c) {

@@ -3,7 +3,7 @@
 // the ordinals), zeroed bitmaps over the resident minimizers, prefix buffers
 static int fin_setup(mdbg_ctx* c, FinArgs& F, u64& n_words_out, bool byte_maps = false) {
     hipStream_t s = c->stream;
-    invalidate_results(c, FROM_NODES);
+    c->res.invalidate(FROM_NODES);
     F.ath_override = nullptr;
     const u32 k = c->P.k;
         // batches sorted by first ordinal -> dense order of the ordinals
@@ -144,8 +144,7 @@ static int resolve_wrapped(mdbg_ctx* c, FinArgs& F, u64 n_bound, bool routed) {
                                      c->w_start.as<u32>(), c->w_fill.as<u32>(), c->w_occ.as<u64>(), s);
         }
     }
-    if (!c->eb) c->eb = edge_buffers_create();
-    HIPCHK(c, sort_segments_u64(c->eb, c->w_occ.as<u64>(), c->w_sorted.as<u64>(), total, (u32)n_w, c->w_start.as<u32>(), s));
+    HIPCHK(c, sort_segments_u64(c->res.edges.buf.get(), c->w_occ.as<u64>(), c->w_sorted.as<u64>(), total, (u32)n_w, c->w_start.as<u32>(), s));
     launch_wrap_pick((u32)n_w, c->w_start.as<u32>(), c->w_jstar.as<u64>(), c->w_sorted.as<u64>(), c->w_ath.as<u64>(), s);
     F.ath_override = c->w_ath.as<u64>();
     return MDBG_OK;
@@ -172,29 +171,44 @@ static int finalize_begin_impl(mdbg_ctx* c, bool fused) {
     c->fin_open = true;
     return MDBG_OK;
 }
-// the rows are on the device (c->finF.o_*): hand them over as device pointers, or copied into the context's host vectors
-static int finalize_hand_over(mdbg_ctx* c, mdbg_nodes* out, bool to_host, u64 n) {
-    FinArgs& F = c->finF;
-    const u32 k = c->P.k;
-    if (!to_host) {
-        out->keys = F.o_keys; out->index = F.o_index; out->abundance = F.o_abund; out->seqlen = F.o_seqlen; out->shift = F.o_shift;
-        out->shift_full = F.o_shift_full; out->src_read = F.o_src_read; out->src_start = F.o_src_start; out->src_end = F.o_src_end; out->reversed = F.o_rev;
-        return MDBG_OK;
-    }
-    const char* const what = "host copy of the node table";
-    int e;
-    if ((e = copy_out(c, c->h_keys, F.o_keys, n * k, what, &out->keys)) || (e = copy_out(c, c->h_index, F.o_index, n, what, &out->index)) ||
-        (e = copy_out(c, c->h_abund, F.o_abund, n, what, &out->abundance)) || (e = copy_out(c, c->h_seqlen, F.o_seqlen, n, what, &out->seqlen)) ||
-        (e = copy_out(c, c->h_shift, F.o_shift, 2 * n, what, &out->shift)) || (e = copy_out(c, c->h_shift_full, F.o_shift_full, 2 * n, what, &out->shift_full)) ||
-        (e = copy_out(c, c->h_src_read, F.o_src_read, n, what, &out->src_read)) || (e = copy_out(c, c->h_src_start, F.o_src_start, n, what, &out->src_start)) ||
-        (e = copy_out(c, c->h_src_end, F.o_src_end, n, what, &out->src_end)) || (e = copy_out(c, c->h_rev, F.o_rev, n, what, &out->reversed))) return e;
+// The node rows' block: fin_out sized for `rows` rows, every column rounded up to 256 bytes, and F.o_* set to the ten columns; row_column: room for a partition's
+// global rows (F.o_row) between src_end and index as well.
+static int carve_node_rows(mdbg_ctx* c, FinArgs& F, size_t rows, bool row_column) {
+    size_t off = 0; auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_keys = carve(rows * c->P.k * 8), o_sf = carve(rows * 16), o_sr = carve(rows * 8), o_ss = carve(rows * 8), o_se = carve(rows * 8), o_row = row_column ? carve(rows * 8) : 0,
+                 o_idx = carve(rows * 4), o_sl = carve(rows * 4), o_ab = carve(rows * 2), o_sh = carve(rows * 4), o_rv = carve(rows);
+    HIPCHK(c, c->fin_out.ensure(off + 256, 0, c->stream));
+    u8* fo_ = c->fin_out.as<u8>();
+    F.o_keys = (u64*)(fo_ + o_keys); F.o_shift_full = (u64*)(fo_ + o_sf); F.o_src_read = (u64*)(fo_ + o_sr); F.o_src_start = (u64*)(fo_ + o_ss);
+    F.o_src_end = (u64*)(fo_ + o_se); F.o_index = (u32*)(fo_ + o_idx); F.o_seqlen = (u32*)(fo_ + o_sl); F.o_abund = (u16*)(fo_ + o_ab);
+    F.o_shift = (u16*)(fo_ + o_sh); F.o_rev = fo_ + o_rv; F.o_row = row_column ? (u64*)(fo_ + o_row) : nullptr;
     return MDBG_OK;
+}
+// the rows are on the device (c->finF.o_*): hand them over as device pointers, copied into the context's host columns, or (mdbg_finalize_gfa) only the three columns
+// an S line prints copied and the others left null
+enum NodesTo { TO_DEVICE, TO_HOST, TO_HOST_GFA };
+static int finalize_hand_over(mdbg_ctx* c, mdbg_nodes* out, NodesTo to, u64 n) {
+    const FinArgs& F = c->finF;
+    auto& H = c->res.nodes;
+    const bool all = to != TO_HOST_GFA;
+    HandOver ho{c, "host copy of the node table", to != TO_DEVICE};
+    if (all) ho.col(F.o_keys, n * c->P.k, H.keys, &out->keys);
+    ho.col(F.o_index, n, H.index, &out->index);
+    ho.col(F.o_abund, n, H.abund, &out->abundance);
+    ho.col(F.o_seqlen, n, H.seqlen, &out->seqlen);
+    if (!all) return ho.err;
+    ho.col(F.o_shift, 2 * n, H.shift, &out->shift);
+    ho.col(F.o_shift_full, 2 * n, H.shift_full, &out->shift_full);
+    ho.col(F.o_src_read, n, H.src_read, &out->src_read);
+    ho.col(F.o_src_start, n, H.src_start, &out->src_start);
+    ho.col(F.o_src_end, n, H.src_end, &out->src_end);
+    ho.col(F.o_rev, n, H.rev, &out->reversed);
+    return ho.err;
 }
 // finalize, phase 2: ranks from the (possibly all-reduced) bitmaps, then the node rows of this context's solid keys.
 // partitioned: rows are written compactly in list order and their global row goes to *d_row.
-static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool partitioned, const uint64_t** d_row, uint64_t* n_solid_global, bool fused = false) {
+static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, NodesTo to, bool partitioned, const uint64_t** d_row, uint64_t* n_solid_global, bool fused = false) {
     hipStream_t s = c->stream;
-    const u32 k = c->P.k;
     FinArgs& F = c->finF;
     const u64 n_words = c->fin_words;
     c->fin_open = false;
@@ -211,14 +225,8 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
     const bool speculate = !partitioned && !c->before_emit && c->P.min_abundance <= MDBG_CASCADE_MAX && c->fin_rows_guess > 0;
     if (speculate) {
         const size_t cap_rows = c->fin_rows_guess;
-        size_t off = 0; auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t o_keys = carve(cap_rows * k * 8), o_sf = carve(cap_rows * 16), o_sr = carve(cap_rows * 8), o_ss = carve(cap_rows * 8), o_se = carve(cap_rows * 8),
-                     o_idx = carve(cap_rows * 4), o_sl = carve(cap_rows * 4), o_ab = carve(cap_rows * 2), o_sh = carve(cap_rows * 4), o_rv = carve(cap_rows);
-        HIPCHK(c, c->fin_out.ensure(off + 256, 0, s)); HIPCHK(c, c->fin_order.ensure(cap_rows * 8, 0, s));
-        u8* fo_ = c->fin_out.as<u8>();
-        F.o_keys = (u64*)(fo_ + o_keys); F.o_shift_full = (u64*)(fo_ + o_sf); F.o_src_read = (u64*)(fo_ + o_sr); F.o_src_start = (u64*)(fo_ + o_ss);
-        F.o_src_end = (u64*)(fo_ + o_se); F.o_index = (u32*)(fo_ + o_idx); F.o_seqlen = (u32*)(fo_ + o_sl); F.o_abund = (u16*)(fo_ + o_ab);
-        F.o_shift = (u16*)(fo_ + o_sh); F.o_rev = fo_ + o_rv; F.o_row = nullptr;
+        e = carve_node_rows(c, F, cap_rows, false); if (e) return e;      // (no room for global rows: this path is never partitioned)
+        HIPCHK(c, c->fin_order.ensure(cap_rows * 8, 0, s));
         F.ath_override = nullptr; F.n_solid_dev = F.solid_count; F.order = nullptr;
         launch_fin_order(F, cap_rows, c->fin_order.as<u64>(), s);
         F.order = c->fin_order.as<u64>();
@@ -233,8 +241,8 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
             c->fin_rows_guess = n_solid + n_solid / 4 + 1024;
             if (d_row) *d_row = nullptr;
             out->n = n_solid;
-            invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = true; c->nseq_prefix_ok = false;
-            return finalize_hand_over(c, out, to_host, n_solid);
+            c->res.node_table_is(NodeTable::ROWS, n_solid);
+            return finalize_hand_over(c, out, to, n_solid);
         }
         STAGE_EVENT(c, c->ev0, s);        // (the span of the plain path starts here; what was written above is overwritten)
     } else { e = read_scalars(c, sc, true); if (e) return e; }          // + wrapped, distinct; SC_FIN0 = solid count (list)
@@ -249,14 +257,8 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
     }
     // device outputs, one allocation
     const size_t n = n_solid;
-    size_t off = 0; auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_keys = carve(n * k * 8), o_sf = carve(n * 16), o_sr = carve(n * 8), o_ss = carve(n * 8), o_se = carve(n * 8), o_row = carve(n * 8),
-                 o_idx = carve(n * 4), o_sl = carve(n * 4), o_ab = carve(n * 2), o_sh = carve(n * 4), o_rv = carve(n);
-    HIPCHK(c, c->fin_out.ensure(off + 256, 0, s));
-    u8* fo_ = c->fin_out.as<u8>();
-    F.o_keys = (u64*)(fo_ + o_keys); F.o_shift_full = (u64*)(fo_ + o_sf); F.o_src_read = (u64*)(fo_ + o_sr); F.o_src_start = (u64*)(fo_ + o_ss);
-    F.o_src_end = (u64*)(fo_ + o_se); F.o_index = (u32*)(fo_ + o_idx); F.o_seqlen = (u32*)(fo_ + o_sl); F.o_abund = (u16*)(fo_ + o_ab);
-    F.o_shift = (u16*)(fo_ + o_sh); F.o_rev = fo_ + o_rv; F.o_row = partitioned ? (u64*)(fo_ + o_row) : nullptr;
+    e = carve_node_rows(c, F, n, true); if (e) return e;
+    if (!partitioned) F.o_row = nullptr;
     if (c->before_emit) { e = c->before_emit(c->before_emit_self, F, n_solid); if (e) return e; }
     F.order = nullptr;
     if (!partitioned && n) {           // rows in index order: list the slots by row first, so that every output array is written front to back
@@ -280,46 +282,22 @@ static int finalize_end_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host, bool pa
     c->ms_finalize += ev_ms(c);
     if (d_row) *d_row = F.o_row;
     out->n = n_solid;
-    invalidate_results(c, FROM_EDGES); c->nodes_n = n_solid; c->nodes_ok = !partitioned; c->nseq_prefix_ok = false;
-    return finalize_hand_over(c, out, to_host, n);
+    c->res.node_table_is(partitioned ? NodeTable::NONE : NodeTable::ROWS, n_solid);
+    return finalize_hand_over(c, out, to, n);
 }
 
-static int finalize_impl(mdbg_ctx* c, mdbg_nodes* out, bool to_host) {
-    if (!c || !out) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+static int finalize_impl(mdbg_ctx* c, mdbg_nodes* out, NodesTo to) {
+    MDBG_ENTER(c, out);
     if (c->routed) return fail(c, MDBG_E_STATE, "a routed table is finalized by the distributed driver (mdbg_routed_export / mdbg_resolve_* / mdbg_routed_keys)");
     memset(out, 0, sizeof *out);
     out->k = c->P.k;
-    if (!(c->cap && c->M)) {
-        c->h_keys.clear(); c->h_shift_full.clear(); c->h_src_read.clear(); c->h_src_start.clear(); c->h_src_end.clear();
-        c->h_index.clear(); c->h_seqlen.clear(); c->h_abund.clear(); c->h_shift.clear(); c->h_rev.clear();
-        c->nodes_none = true;
-        return MDBG_OK;
-    }
+    if (nothing_resident(c)) { c->res.node_table_is(NodeTable::EMPTY, 0); return MDBG_OK; }
     int e = finalize_begin_impl(c, true); if (e) return e;
-    return finalize_end_impl(c, out, to_host, false, nullptr, nullptr, true);
+    return finalize_end_impl(c, out, to, false, nullptr, nullptr, true);
 }
-int mdbg_finalize(mdbg_ctx* c, mdbg_nodes* out) { return finalize_impl(c, out, true); }
-int mdbg_finalize_device(mdbg_ctx* c, mdbg_nodes* out) { return finalize_impl(c, out, false); }
-int mdbg_finalize_gfa(mdbg_ctx* c, mdbg_nodes* out) {
-    int e = finalize_impl(c, out, false); if (e) return e;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    const u64 n = out->n;
-    const uint32_t* d_index = out->index; const uint32_t* d_seqlen = out->seqlen; const uint16_t* d_abund = out->abundance;
-    out->keys = nullptr; out->shift = nullptr; out->shift_full = nullptr; out->src_read = nullptr; out->src_start = nullptr; out->src_end = nullptr; out->reversed = nullptr;
-    out->index = nullptr; out->seqlen = nullptr; out->abundance = nullptr;
-    if (!(c->h_index.resize(n) && c->h_seqlen.resize(n) && c->h_abund.resize(n))) return fail(c, MDBG_E_NOMEM, "host copy of the node table");
-    if (n) {
-        HIPCHK(c, hipMemcpy(c->h_index.data(), d_index, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_seqlen.data(), d_seqlen, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->h_abund.data(), d_abund, n * 2, hipMemcpyDeviceToHost));
-    }
-    out->index = c->h_index.data(); out->seqlen = c->h_seqlen.data(); out->abundance = c->h_abund.data();
-    return MDBG_OK;
-}
+int mdbg_finalize(mdbg_ctx* c, mdbg_nodes* out) { return finalize_impl(c, out, TO_HOST); }
+int mdbg_finalize_device(mdbg_ctx* c, mdbg_nodes* out) { return finalize_impl(c, out, TO_DEVICE); }
+int mdbg_finalize_gfa(mdbg_ctx* c, mdbg_nodes* out) { return finalize_impl(c, out, TO_HOST_GFA); }
 
 int mdbg_nodes_digest(mdbg_ctx* c, const mdbg_nodes* nodes, uint64_t* sum, uint64_t* xr) {
     if (!c || !nodes || !sum || !xr) return MDBG_E_PARAM;
@@ -340,10 +318,7 @@ int mdbg_nodes_digest(mdbg_ctx* c, const mdbg_nodes* nodes, uint64_t* sum, uint6
 }
 
 int mdbg_finalize_begin(mdbg_ctx* c, uint64_t** d_bm_first, uint64_t** d_bm_solid, uint64_t* n_words) {
-    if (!c || !d_bm_first || !d_bm_solid || !n_words) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    MDBG_ENTER(c, d_bm_first && d_bm_solid && n_words);
     if (c->routed) return fail(c, MDBG_E_STATE, "not available for a routed table");
     if (!c->M) {                       // no minimizer anywhere (empty input, or every read shorter than l): an empty table, not an error
         c->fin_open = true; c->fin_words = 0;      // (nothing resident: no node table can be current, M == 0 since the last clear_table)
@@ -357,10 +332,7 @@ int mdbg_finalize_begin(mdbg_ctx* c, uint64_t** d_bm_first, uint64_t** d_bm_soli
 }
 
 int mdbg_finalize_end(mdbg_ctx* c, mdbg_nodes* out, const uint64_t** d_row, uint64_t* n_nodes_global) {
-    if (!c || !out) return MDBG_E_PARAM;
-    MDBG_LOCK(c);
-    (void)hipSetDevice(c->dev);
-    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    MDBG_ENTER(c, out);
     if (!c->fin_open) return fail(c, MDBG_E_STATE, "mdbg_finalize_begin was not called");
     memset(out, 0, sizeof *out);
     out->k = c->P.k;
@@ -370,5 +342,5 @@ int mdbg_finalize_end(mdbg_ctx* c, mdbg_nodes* out, const uint64_t** d_row, uint
         if (n_nodes_global) *n_nodes_global = 0;
         return MDBG_OK;
     }
-    return finalize_end_impl(c, out, false, true, d_row, n_nodes_global);
+    return finalize_end_impl(c, out, TO_DEVICE, true, d_row, n_nodes_global);
 }

@@ -197,7 +197,7 @@ int launch_fused_insert(mdbg_ctx* c, const SketchCall& k) {
 }
 // The table side of a round trip whose insertion rode behind the sketch (the tail of insert_resident_impl)
 int fused_tail(mdbg_ctx* c, const u64* sc, bool* inserted) {
-    invalidate_results(c, FROM_NODES);
+    c->res.invalidate(FROM_NODES);
     if (sc[SC_CAPERR] >> 32) return MDBG_OK;   // the sketch was fine, so the table was too small: nothing was inserted; the caller inserts the plain way (*inserted stays false)
     c->batches_inserted = c->batches.size();
     *inserted = true;
@@ -279,7 +279,7 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
         const u64 slow_total = sc[SC_SLOWTOTAL];      // (the scalar is scratch from here on)
         if (c->lmer_on && m_new > c->M) { e = lmer_filter_pass(c, k, m_new); if (e) return e; }
         Batch b; b.first_ordinal = first_ordinal; b.n_reads = (u32)n_reads; b.slot0 = slot0; b.m0 = c->M; b.m1 = m_new; b.n_bases = n_bases;
-        invalidate_results(c, FROM_UNITIGS);
+        c->res.invalidate(FROM_UNITIGS);
         if (c->P.flags & MDBG_FLAG_KEEP_READS) { int ke = keep_batch(c, in, d_offsets, n_reads, n_bases, b.kept); if (ke) return ke; }
         store_append(c, b);
         c->n_reads += n_reads; c->n_bases += n_bases; c->n_tiles += n_tiles_total; c->n_slow_tiles += slow_total;
@@ -417,7 +417,7 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
     if (c->pending_m && !allow_pending) return fail(c, MDBG_E_STATE, "reserved sketch regions have not been committed");
     hipStream_t s = c->stream;
     const size_t first = c->batches_inserted, last = c->batches.size();
-    invalidate_results(c, FROM_NODES);
+    c->res.invalidate(FROM_NODES);
     bool any = false;
     for (size_t i = first; i < last; ++i) any = any || c->batches[i].m1 > c->batches[i].m0;
     c->batches_inserted = last;

@@ -5,7 +5,7 @@
 // and which row follows from what that finalize left behind, without a second table over the node keys: the slot's first sighting (its claimer, or the smallest
 // ordinal the later sightings pushed) has a dense ordered index D, and the row is the rank of D among the solid bits, pre_solid[D >> 6] + popc(bm_solid[D >> 6] & below)
 // — the expression fin_emit_kernel numbered the rows with.  fin_setup is the only writer of the bitmaps, the prefixes and the batch table, and it ends the node table
-// (nodes_ok) before it touches them, so they are intact whenever the caller's state checks pass.
+// (Results::invalidate, results.inc) before it touches them, so they are intact whenever the caller's state checks pass.
 #include "mdbg_dev.h"
 #include "read_paths.h"
 

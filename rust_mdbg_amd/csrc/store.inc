@@ -90,8 +90,7 @@ int keep_batch(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets, u64 n_r
         k->n_exc = n;
         if (n) {
             HIPCHK(c, mdbg_block_alloc(&k->xblk, n * 9, &k->xcap));
-            if (!c->cb) c->cb = contig_buffers_create();
-            HIPCHK(c, sort_exceptions(c->cb, c->kp_exc_pos.as<u64>(), c->kp_exc_val.as<u8>(), k->exc_pos(), k->exc_val(), n, s));
+            HIPCHK(c, sort_exceptions(c->res.contigs.buf.get(), c->kp_exc_pos.as<u64>(), c->kp_exc_val.as<u8>(), k->exc_pos(), k->exc_val(), n, s));
         }
     } else HIPCHK(c, hipStreamSynchronize(s));
     out = std::move(k);
