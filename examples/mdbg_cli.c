@@ -5,6 +5,8 @@
  *   -c N,L: a small-component step in the schedule (every unitig of a non-circular connected component of at most N nodes and L bases is removed; 0 = no limit
  *   on that side); --components: the number of connected components of the unitig graph and the largest one (mdbg_graph_components)
  *   --read-paths (implies --contigs): the resident reads threaded through the unitig list (mdbg_graph_read_paths, in ranges of 2^20 reads): one summary line
+ *   --junctions (implies --contigs): the reads that cross each edge record of the unitig list (mdbg_graph_junctions, in ranges of 2^20 reads, the supports summed):
+ *   one summary line
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
  *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
@@ -86,7 +88,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L append steps of their own, in command-line order */
@@ -136,15 +138,16 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(argv[i], "--components")) components = 1;
         else if (!strcmp(argv[i], "--read-paths")) read_paths = 1;
+        else if (!strcmp(argv[i], "--junctions")) junctions = 1;
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [--components] [--read-paths] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [--components] [--read-paths] [--junctions] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
-    if (simplify || components || read_paths) contigs = 1;
+    if (simplify || components || read_paths || junctions) contigs = 1;
     if (!contigs) keep_reads = 0;
     if (!write_sequences) seq_kept = 0;
     if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
@@ -299,6 +302,27 @@ int main(int argc, char** argv) {
             }
             printf("read paths: %llu reads with a step, %llu / %llu windows placed, %llu reads with more than one step\n", (unsigned long long)with_steps,
                    (unsigned long long)placed, (unsigned long long)windows, (unsigned long long)several);
+        }
+        if (junctions) {                                            /* of the same list and in the same ranges; the supports of the ranges add up */
+            uint64_t jx_first = 0, records = 0, unsupported = 0, crossings = 0, missing = 0;
+            uint64_t* support = NULL;
+            for (;;) {
+                mdbg_junction_list jx;
+                rc = mdbg_graph_junctions(ctx, jx_first, (uint64_t)1 << 20, &jx);
+                if (rc) die(ctx, "mdbg_graph_junctions", rc);
+                if (!jx.n_reads) break;
+                if (!support && jx.n_records) {
+                    records = jx.n_records;
+                    support = (uint64_t*)calloc(records, sizeof *support);
+                    if (!support) die(NULL, "calloc", MDBG_E_NOMEM);
+                }
+                for (uint64_t r = 0; r < jx.n_records; ++r) support[r] += jx.support[r];
+                crossings += jx.n_crossings; missing += jx.n_missing_crossings; jx_first += jx.n_reads;
+            }
+            for (uint64_t r = 0; r < records; ++r) unsupported += support[r] == 0;
+            free(support);
+            printf("junctions: %llu records, %llu crossed by no read, %llu crossings, %llu of them on no record\n", (unsigned long long)records,
+                   (unsigned long long)unsupported, (unsigned long long)crossings, (unsigned long long)missing);
         }
         if (keep_reads) {
             mdbg_contig_seqs cs;

@@ -539,6 +539,58 @@ int mdbg_graph_read_paths(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads
 int mdbg_graph_read_paths_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out);
 int mdbg_read_paths_ms(mdbg_ctx* ctx, double* ms);
 
+/* ---- read support per junction: the reads that cross each unitig edge, and the crossings no edge explains ----------------------------
+ * An edge record of the graph does not come from a read: two nodes get an L line when they share a normalized (k-1)-mer, whether or not a read ever went from one to
+ * the other.  This call counts, per edge record of the CURRENT unitig list, the resident reads that cross it, and lists the places where reads cross without a
+ * record.  It works on what mdbg_graph_read_paths works on — the current unitig list, the node table that list was built from, the resident sketch store —, with the
+ * same state requirements and the same range of reads [first_read, first_read + max_reads) (max_reads = 0: to the end).  SINGLE GPU ONLY.
+ *
+ * Definition.  Windows, PLACED, unitig u, entry j and strand s are those of mdbg_graph_read_paths; m(u) = offsets[u + 1] - offsets[u] is the entry count of unitig u.
+ *   A VERTEX is (u, j, s); vertices are ordered by (u, j, s), which is the order of 2 * (offsets[u] + j) + s.
+ *   The MIRROR of the ordered pair (x, y) is ((y.u, y.j, 1 - y.s), (x.u, x.j, 1 - x.s)).  The KEY of a pair is the smaller of the pair and its mirror, compared
+ *   lexicographically on (x, y).
+ *   An ADJACENT PAIR is windows w and w + 1 of one read, both placed; n_adjacent counts them over the range.
+ *   A LINK is an adjacent pair x -> y with the same u, the same s, and y.j == x.j + 1 (s = 0) or y.j == x.j - 1 (s = 1), taken WITHOUT wrapping; n_links counts them.
+ *   A CROSSING is every other adjacent pair — the wrap m - 1 -> 0 (s = 0) or 0 -> m - 1 (s = 1), which mdbg_graph_read_paths treats as the continuation of a step on
+ *   a circular unitig, included.  n_crossings = n_adjacent - n_links.
+ *   The key of EDGE RECORD r = (n1, o1, n2, o2) of the list's `edges` is the key of the pair x = (n1, o1 == '+' ? m(n1) - 1 : 0, o1 == '-'),
+ *   y = (n2, o2 == '+' ? 0 : m(n2) - 1, o2 == '-').  A record and its mirror record have the same key, so do duplicate records; the closing record u + u + of a
+ *   circular unitig has the key of its wrap.
+ *   support[r], n_records entries parallel to the list's edge arrays, is the number of crossings in the range whose key is the key of record r: records with equal
+ *   keys carry equal counts.  n_explained is the number of crossings whose key is some record's key.
+ *   The other crossings are MISSING.  They are returned as their distinct keys in ascending key order, n_missing of them: missing_unitig1[], missing_entry1[],
+ *   missing_strand1[] (x) and missing_unitig2[], missing_entry2[], missing_strand2[] (y), with missing_count[] the crossings on that key; n_missing_crossings is the
+ *   sum of missing_count[].
+ *   Everything is an integer sum or a position of a sort or a scan: two calls give identical arrays, nothing depends on scheduling.
+ * Invariants: n_explained + n_missing_crossings == n_crossings; n_links + n_crossings == n_adjacent.  On a plain list (mdbg_graph_unitigs) built on edges of presimp 0,
+ * n_missing == 0: consecutive windows share a (k-1)-mer, so their arc exists, and it is an interior link or both of its ends are unitig ends.  Against the read-path
+ * result of the same range: n_links + wraps == n_placed - n_steps, with `wraps` the ring wraps inside steps (from first_entry, step_windows and strand of the steps
+ * on circular unitigs).
+ * Ranges: over the ranges of a partition of the reads the support arrays add up to the whole call's, the missing lists merge by key (counts added) into the whole
+ * call's, and n_reads, n_adjacent, n_links, n_crossings, n_explained and n_missing_crossings add up.  first_read >= the number of reads: MDBG_OK with zero counts,
+ * which ends a caller's loop `first_read += n_reads`.  The temporaries are 25 bytes per minimizer index of the range (the place codes 4, the keys of the missing
+ * crossings and their sorted copy 16, head flags 1, positions 4) beside the sort's own, and the missing columns are sized for their worst case, another 26 bytes per
+ * index, because their number is known only on the device: the range bounds both.  Per edge record the call takes 32 bytes of temporaries and 8 of result.
+ * mdbg_graph_junctions: HOST arrays; mdbg_graph_junctions_device: DEVICE arrays.  They belong to the context until its next junction call or mdbg_destroy and share
+ * memory with no other result — a read-path result the caller holds is untouched —, and the call leaves the node table, the edge list, the unitig list and the contig,
+ * component and read-path results as they are.  The number of kernel launches is fixed; the device variant waits for the device ONCE (all counts and the defect flag
+ * in one read-back) when the range starts and ends where batches do, otherwise once more, up front, for the range's two offsets.
+ * mdbg_junctions_ms: device time of the last junction call (HIP events; 0 if it launched nothing).
+ * MDBG_E_STATE: no current unitig list, the node table is not current, or a routed / partitioned context; MDBG_E_PARAM: a null pointer; MDBG_E_CAPACITY: the bounds of
+ * the read paths (2^30 entries, 2^32 minimizers in the range) or 2^32 edge records; MDBG_E_DEVICE: the defect flags of the read paths, or an edge record that names a
+ * unitig outside the list.  An empty context, an empty list or first_read >= the number of reads gives MDBG_OK with every count zero (n_records included) and no
+ * arrays.  A list with no edge records and a non-empty range is ordinary: n_records == 0 and every crossing is missing. */
+typedef struct mdbg_junction_list {
+    uint64_t first_read, n_reads, n_adjacent, n_links, n_crossings, n_explained, n_missing_crossings, n_records, n_missing;
+    const uint64_t* support;                                                                                  /* n_records */
+    const uint32_t* missing_unitig1; const uint32_t* missing_entry1; const uint8_t* missing_strand1;          /* n_missing */
+    const uint32_t* missing_unitig2; const uint32_t* missing_entry2; const uint8_t* missing_strand2;          /* n_missing */
+    const uint64_t* missing_count;                                                                            /* n_missing */
+} mdbg_junction_list;
+int mdbg_graph_junctions(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out);
+int mdbg_graph_junctions_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out);
+int mdbg_junctions_ms(mdbg_ctx* ctx, double* ms);
+
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),
  * so the ranks may exchange SKETCHES instead (one all-gather), each rank then windows the global sketch but inserts only

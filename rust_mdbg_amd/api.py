@@ -122,6 +122,54 @@ def read_path_text(rp, circular):
     return "".join(lines)
 
 
+class JunctionList(C.Structure):       # mdbg_junction_list
+    _fields_ = [("first_read", C.c_uint64), ("n_reads", C.c_uint64), ("n_adjacent", C.c_uint64), ("n_links", C.c_uint64), ("n_crossings", C.c_uint64),
+                ("n_explained", C.c_uint64), ("n_missing_crossings", C.c_uint64), ("n_records", C.c_uint64), ("n_missing", C.c_uint64),
+                ("support", C.POINTER(C.c_uint64)), ("missing_unitig1", C.POINTER(C.c_uint32)), ("missing_entry1", C.POINTER(C.c_uint32)),
+                ("missing_strand1", C.POINTER(C.c_uint8)), ("missing_unitig2", C.POINTER(C.c_uint32)), ("missing_entry2", C.POINTER(C.c_uint32)),
+                ("missing_strand2", C.POINTER(C.c_uint8)), ("missing_count", C.POINTER(C.c_uint64))]
+
+
+# (field, dtype, what it has one element of: "record" or "missing")
+JUNCTION_FIELDS = (("support", np.uint64, "record"), ("missing_unitig1", np.uint32, "missing"), ("missing_entry1", np.uint32, "missing"), ("missing_strand1", np.uint8, "missing"),
+                   ("missing_unitig2", np.uint32, "missing"), ("missing_entry2", np.uint32, "missing"), ("missing_strand2", np.uint8, "missing"), ("missing_count", np.uint64, "missing"))
+JUNCTION_COUNTS = ("n_reads", "n_adjacent", "n_links", "n_crossings", "n_explained", "n_missing_crossings")      # what adds up over the ranges of a partition of the reads
+MISSING_COLUMNS = tuple(f for f, _, per in JUNCTION_FIELDS if per == "missing")
+
+
+def junction_text(edges, support, missing, circular):
+    """the lines of a .junctions.tsv: first one per edge record of the unitig list in list order, the record's L line of the .gfa with the number of reads that cross it
+    appended, `L<TAB>utgA<TAB>o1<TAB>utgB<TAB>o2<TAB>overlapM<TAB>support`; then one per missing key in key order, a place where reads cross and no record exists,
+    `X<TAB>utgA<TAB>+|-<TAB>entry1<TAB>utgB<TAB>+|-<TAB>entry2<TAB>count` (`+` = strand 0).  edges: the list's `edges` dict; support: per record; missing: a dict with
+    the seven missing_* columns (a graph_junctions() result, or the merge of several); circular: the list's `circular` array."""
+    name = lambda u: unitig_name(u, circular[u])
+    sign = lambda s: "-" if s else "+"
+    n1, o1, n2, o2, ov = (np.asarray(edges[f]).tolist() for f, _ in EDGE_FIELDS)
+    lines = ["L\t%s\t%s\t%s\t%s\t%dM\t%d\n" % (name(a), chr(oa), name(b), chr(ob), v, s) for a, oa, b, ob, v, s in zip(n1, o1, n2, o2, ov, np.asarray(support).tolist())]
+    for u1, j1, s1, u2, j2, s2, n in zip(*(np.asarray(missing[f]).tolist() for f in MISSING_COLUMNS)):
+        lines.append("X\t%s\t%s\t%d\t%s\t%s\t%d\t%d\n" % (name(u1), sign(s1), j1, name(u2), sign(s2), j2, n))
+    return "".join(lines)
+
+
+def merge_junctions(parts):
+    """the graph_junctions() results of the ranges of a partition of the reads -> the whole call's: the counts and the supports add up, the missing lists merge by
+    key (counts added, ascending key order)"""
+    parts = list(parts)
+    out = {f: sum(p[f] for p in parts) for f in JUNCTION_COUNTS}
+    with_records = [p for p in parts if p["n_records"]]            # (a range behind the store, an empty list: no arrays)
+    out["n_records"] = with_records[0]["n_records"] if with_records else 0
+    out["support"] = sum((p["support"] for p in with_records), np.zeros(out["n_records"], np.uint64))
+    by_key = {}
+    for p in parts:
+        for row in zip(*(p[f].tolist() for f in MISSING_COLUMNS)):
+            by_key[row[:6]] = by_key.get(row[:6], 0) + row[6]
+    rows = [key + (by_key[key],) for key in sorted(by_key)]       # (tuples of the six columns compare as keys do)
+    for i, (f, t, _) in enumerate(JUNCTION_FIELDS[1:]):
+        out[f] = np.array([r[i] for r in rows], dtype=t)
+    out.update(first_read=parts[0]["first_read"] if parts else 0, n_missing=len(rows))
+    return out
+
+
 class ContigSeqs(C.Structure):         # mdbg_contig_seqs
     _fields_ = [("n_contigs", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64)),
                 ("unitig", C.POINTER(C.c_uint64))]
@@ -180,6 +228,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
            "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
+           "mdbg_graph_junctions", "mdbg_graph_junctions_device", "mdbg_junctions_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -282,6 +331,9 @@ def load_library():
     L.mdbg_graph_read_paths.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
     L.mdbg_graph_read_paths_device.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
     L.mdbg_read_paths_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mdbg_graph_junctions.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
+    L.mdbg_graph_junctions_device.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
+    L.mdbg_junctions_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -309,6 +361,11 @@ def _np(ptr, n, dtype):
     if n == 0:
         return np.zeros(0, dtype=dtype)
     return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True)
+
+
+def edge_columns(e):
+    """the five arrays of an EdgeList with HOST pointers (a unitig list's `edges`), copied -> dict by field name"""
+    return {f: _np(getattr(e, f), int(e.n), t) for f, t in EDGE_FIELDS}
 
 
 def concat_reads(reads):
@@ -545,9 +602,7 @@ class Mdbg:
         out = {f: _np(getattr(u, f), cnt[f], t) for f, t in UNITIG_FIELDS}
         if not len(out["offsets"]):
             out["offsets"] = np.zeros(1, np.uint64)
-        ne = int(u.edges.n)
-        out.update(n_unitigs=int(u.n_unitigs), n_entries=int(u.n_entries), n_rounds=int(u.n_rounds),
-                   edges={f: _np(getattr(u.edges, f), ne, t) for f, t in EDGE_FIELDS})
+        out.update(n_unitigs=int(u.n_unitigs), n_entries=int(u.n_entries), n_rounds=int(u.n_rounds), edges=edge_columns(u.edges))
         return out
 
     def graph_unitigs_device(self):
@@ -621,6 +676,30 @@ class Mdbg:
         """device time of the last graph_read_paths* call, in milliseconds"""
         ms = C.c_double()
         self._chk(self.L.mdbg_read_paths_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def graph_junctions(self, first_read=0, max_reads=0):
+        """read support per junction of the current unitig list, counted on the GPU over the resident reads [first_read, first_read + max_reads) (0: to the end): how
+        many reads cross each edge record, and where reads cross without a record (mdbg_graph_junctions, include/mdbg_hip.h).  Leaves the list and every other result
+        as they are.  -> dict(first_read, n_reads, n_adjacent, n_links, n_crossings, n_explained, n_missing_crossings, n_records, n_missing; per edge record support;
+        per missing key missing_unitig1, missing_entry1, missing_strand1, missing_unitig2, missing_entry2, missing_strand2, missing_count)"""
+        jl = JunctionList()
+        self._chk(self.L.mdbg_graph_junctions(self.h, first_read, max_reads, C.byref(jl)))
+        n = dict(record=int(jl.n_records), missing=int(jl.n_missing))
+        out = {f: _np(getattr(jl, f), n[per], t) for f, t, per in JUNCTION_FIELDS}
+        out.update({f: int(getattr(jl, f)) for f in JUNCTION_COUNTS}, first_read=int(jl.first_read), n_records=n["record"], n_missing=n["missing"])
+        return out
+
+    def graph_junctions_device(self, first_read=0, max_reads=0):
+        """-> JunctionList with DEVICE pointers (valid until the next junction call)"""
+        jl = JunctionList()
+        self._chk(self.L.mdbg_graph_junctions_device(self.h, first_read, max_reads, C.byref(jl)))
+        return jl
+
+    def junctions_ms(self):
+        """device time of the last graph_junctions* call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_junctions_ms(self.h, C.byref(ms)))
         return float(ms.value)
 
     def kept_reads(self):

@@ -1,5 +1,6 @@
 // graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip, bubble and small-component
-// removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip) and read paths (read_paths.hip).
+// removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip), read paths (read_paths.hip) and
+// read support per junction (junctions.hip).
 // Host code; included by api.inc, whose context, fail(), MDBG_ENTER and HandOver it uses; what is current is asked of c->res (results.inc).
 
 // ---- the refusals the stages share -------------------------------------------------------------------------
@@ -238,18 +239,16 @@ static bool known_read_offset(const mdbg_ctx* c, u64 r, u64* v) {
     }
     return false;
 }
-static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out, bool to_host) {
-    MDBG_ENTER(c, out);
-    memset(out, 0, sizeof *out);
-    out->first_read = first_read;
+// What the read paths and the junction support ask before they place a window: the state, the bounds, the range of reads with its minimizer indices, the store's
+// arrays.  what_is: "read paths are", ...  *empty <- the call answers MDBG_OK with zero counts (an empty context, an empty list, a range behind the store).
+static int placement_range(mdbg_ctx* c, const char* what_is, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty) {
+    *empty = true;
     Results& R = c->res;
-    auto& P = R.rpaths;
-    P.ms = 0;
     int e;
-    if ((e = refuse_multi_gpu(c, "read paths are")) || (e = refuse_without_unitig_list(c))) return e;
+    if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
     if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
     const UnitigResult& ul = R.unitigs.last;
-    if (ul.n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;      // an empty context, an empty list, a range behind the store
+    if (ul.n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;
     if (ul.n_entries >= (1ull << 30) || R.n_rows() >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
     hipStream_t s = c->stream;
     const u64 r0 = first_read, r1 = max_reads && max_reads < c->n_slots - r0 ? r0 + max_reads : c->n_slots;
@@ -265,6 +264,27 @@ static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads,
     F.mh = c->mh.as<u64>(); F.roff = c->roff.as<u64>(); F.mread = c->mread.as<u32>();
     rg.roff = F.roff; rg.mread = F.mread; rg.first_read = (u32)r0; rg.n_reads = (u32)(r1 - r0); rg.k = c->P.k;
     rg.by_slot0 = F.bt.by_slot0; rg.by_slot_first = F.bt.by_slot_first; rg.n_batches = F.bt.n;
+    *range = rg; *fin = F; *empty = false;
+    return MDBG_OK;
+}
+static int placement_defect(mdbg_ctx* c, uint32_t defect) {
+    if (defect & RP_DEFECT_ENTRY) return fail(c, MDBG_E_DEVICE, "an entry of the unitig list names a node index that is not a row of the node table");
+    if (defect & RP_DEFECT_PROBE) return fail(c, MDBG_E_DEVICE, "a probe sequence of the read paths visited every slot of the table");
+    if (defect & RP_DEFECT_ROW) return fail(c, MDBG_E_DEVICE, "a solid slot's first sighting is no row of the node table");
+    return MDBG_OK;
+}
+static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out, bool to_host) {
+    MDBG_ENTER(c, out);
+    memset(out, 0, sizeof *out);
+    out->first_read = first_read;
+    Results& R = c->res;
+    auto& P = R.rpaths;
+    P.ms = 0;
+    ReadPathRange rg; FinArgs F; bool empty;
+    const int e = placement_range(c, "read paths are", first_read, max_reads, &rg, &F, &empty);
+    if (e || empty) return e;
+    const UnitigResult& ul = R.unitigs.last;
+    hipStream_t s = c->stream;
     ReadPathPlan plan;
     hipError_t he = read_paths_begin(P.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
     if (he != hipSuccess) return fail_hip(c, "read_paths_begin", he);
@@ -273,9 +293,7 @@ static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads,
     he = read_paths_end(P.buf.get(), ul, rg, s, &r);
     if (he != hipSuccess) return fail_hip(c, "read_paths_end", he);
     P.ms = r.ms;
-    if (r.defect & RP_DEFECT_ENTRY) return fail(c, MDBG_E_DEVICE, "an entry of the unitig list names a node index that is not a row of the node table");
-    if (r.defect & RP_DEFECT_PROBE) return fail(c, MDBG_E_DEVICE, "a probe sequence of the read paths visited every slot of the table");
-    if (r.defect) return fail(c, MDBG_E_DEVICE, "a solid slot's first sighting is no row of the node table");
+    if (r.defect) return placement_defect(c, r.defect);
     const u64 nr = r.n_reads, ns = r.n_steps, U = r.n_unitigs;
     out->n_reads = nr; out->n_windows = r.n_windows; out->n_placed = r.n_placed; out->n_steps = ns; out->n_unitigs = U;
     HandOver ho{c, "host copy of the read paths", to_host};
@@ -294,3 +312,45 @@ static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads,
 int mdbg_graph_read_paths(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out) { return read_paths_impl(c, first_read, max_reads, out, true); }
 int mdbg_graph_read_paths_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out) { return read_paths_impl(c, first_read, max_reads, out, false); }
 int mdbg_read_paths_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.rpaths.ms : nullptr, ms); }
+
+// ---- read support per junction of the current unitig list (place_windows.hip, junctions.hip) -----------------
+static int junctions_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out, bool to_host) {
+    MDBG_ENTER(c, out);
+    memset(out, 0, sizeof *out);
+    out->first_read = first_read;
+    Results& R = c->res;
+    auto& J = R.junctions;
+    J.ms = 0;
+    ReadPathRange rg; FinArgs F; bool empty;
+    const int e = placement_range(c, "junctions are", first_read, max_reads, &rg, &F, &empty);
+    if (e || empty) return e;
+    const UnitigResult& ul = R.unitigs.last;
+    if (ul.edges.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
+    hipStream_t s = c->stream;
+    ReadPathPlan plan;
+    hipError_t he = junctions_begin(J.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
+    if (he != hipSuccess) return fail_hip(c, "junctions_begin", he);
+    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
+    JunctionResult r;
+    he = junctions_end(J.buf.get(), ul, rg, s, &r);
+    if (he != hipSuccess) return fail_hip(c, "junctions_end", he);
+    J.ms = r.ms;
+    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, "an edge record of the unitig list names a unitig outside the list");
+    if (r.defect) return placement_defect(c, r.defect);
+    const u64 nrec = r.n_records, nm = r.n_missing;
+    out->n_reads = r.n_reads; out->n_adjacent = r.n_adjacent; out->n_links = r.n_links; out->n_crossings = r.n_crossings; out->n_explained = r.n_explained;
+    out->n_missing_crossings = r.n_missing_crossings; out->n_records = nrec; out->n_missing = nm;
+    HandOver ho{c, "host copy of the junction support", to_host};
+    ho.col(r.support, nrec, J.support, &out->support);
+    ho.col(r.missing_unitig1, nm, J.u1, &out->missing_unitig1);
+    ho.col(r.missing_entry1, nm, J.e1, &out->missing_entry1);
+    ho.col(r.missing_strand1, nm, J.s1, &out->missing_strand1);
+    ho.col(r.missing_unitig2, nm, J.u2, &out->missing_unitig2);
+    ho.col(r.missing_entry2, nm, J.e2, &out->missing_entry2);
+    ho.col(r.missing_strand2, nm, J.s2, &out->missing_strand2);
+    ho.col(r.missing_count, nm, J.count, &out->missing_count);
+    return ho.err;
+}
+int mdbg_graph_junctions(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out) { return junctions_impl(c, first_read, max_reads, out, true); }
+int mdbg_graph_junctions_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out) { return junctions_impl(c, first_read, max_reads, out, false); }
+int mdbg_junctions_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.junctions.ms : nullptr, ms); }

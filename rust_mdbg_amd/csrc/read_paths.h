@@ -36,6 +36,16 @@ struct ReadPathResult {            // device pointers into ReadPathBuffers, vali
     const uint64_t* support_windows; const uint64_t* support_steps;
     uint32_t defect; float ms;     // defect: mask of RP_DEFECT_*; ms: device time from read_paths_begin to the end of read_paths_end
 };
+// The placement half, which the junction stage (junctions.hip) shares: the arrays belong to the caller's stage.  placement_begin queues the zeroing of the
+// first n_counters counters (>= RP_C_N: a stage may keep counts of its own behind them) and of the map, and entry_kernel, and fills *plan; place_windows_kernel,
+// launched by the caller on the same stream, then writes code[] and the counters RP_C_WINDOWS, RP_C_PLACED and RP_C_DEFECT.
+struct PlacementArrays {
+    uint32_t* entry_of_row;        // [n_rows]
+    uint32_t* unitig_of_entry;     // [n_entries]
+    uint32_t* code;                // [i1 - i0]
+    uint64_t* counters; uint32_t n_counters;
+};
+hipError_t placement_begin(const PlacementArrays& A, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, hipStream_t s, ReadPathPlan* plan);
 // read_paths_begin queues the zeroing and the row -> entry map and fills *plan; the caller then launches place_windows_kernel on the same stream;
 // read_paths_end queues the rest (head flags, one scan, the steps, the sums), reads the counters back and waits ONCE.  Every launch count is fixed.
 hipError_t read_paths_begin(ReadPathBuffers* B, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan);

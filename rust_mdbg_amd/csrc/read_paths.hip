@@ -144,6 +144,19 @@ RpArgs args_of(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& 
 ReadPathBuffers* read_path_buffers_create() { return new ReadPathBuffers(); }
 void read_path_buffers_destroy(ReadPathBuffers* b) { delete b; }
 
+hipError_t placement_begin(const PlacementArrays& A, const UnitigResult& ul, const u32* index, u64 n_rows, hipStream_t s, ReadPathPlan* plan) {
+    memset(plan, 0, sizeof *plan);
+    if (ul.n_unitigs == 0 || ul.n_entries == 0 || n_rows == 0 || A.n_counters < RP_C_N) return hipErrorInvalidValue;
+    GHIP(hipMemsetAsync(A.counters, 0, (size_t)A.n_counters * 8, s));
+    GHIP(hipMemsetAsync(A.entry_of_row, 0xFF, n_rows * 4, s));
+    RpArgs a; memset(&a, 0, sizeof a);      // (what entry_kernel reads)
+    a.U = ul.n_unitigs; a.N = ul.n_entries; a.offsets = ul.offsets; a.node = ul.node; a.index = index; a.n_rows = n_rows;
+    a.entry_of_row = A.entry_of_row; a.unitig_of_entry = A.unitig_of_entry; a.counters = A.counters;
+    hipLaunchKernelGGL(entry_kernel, dim3(grid_for(a.N)), dim3(256), 0, s, a);
+    plan->entry_of_row = A.entry_of_row; plan->n_rows = n_rows; plan->ori = ul.ori; plan->code = A.code; plan->counters = A.counters;
+    return hipGetLastError();
+}
+
 hipError_t read_paths_begin(ReadPathBuffers* B, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan) {
     memset(plan, 0, sizeof *plan);
     const u64 U = ul.n_unitigs, N = ul.n_entries, n_idx = rg.i1 - rg.i0, nr = rg.n_reads;
@@ -158,14 +171,9 @@ hipError_t read_paths_begin(ReadPathBuffers* B, const UnitigResult& ul, const u3
     GHIP(B->strand.ensure(n_idx + 4)); GHIP(B->sup_w.ensure(U * 8)); GHIP(B->sup_s.ensure(U * 8));
     if (n_idx) { size_t tb = 0; GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); GHIP(B->tmp.ensure(tb + 256)); }
     GHIP(hipEventRecord(B->ev0, s));
-    GHIP(hipMemsetAsync(B->counters.p, 0, RP_C_N * 8, s));
-    GHIP(hipMemsetAsync(B->entry_of_row.p, 0xFF, n_rows * 4, s));
     GHIP(hipMemsetAsync(B->sup_w.p, 0, U * 8, s)); GHIP(hipMemsetAsync(B->sup_s.p, 0, U * 8, s));
-    RpArgs a = args_of(B, ul, rg);
-    a.index = index; a.n_rows = n_rows;
-    hipLaunchKernelGGL(entry_kernel, dim3(grid_for(N)), dim3(256), 0, s, a);
-    plan->entry_of_row = a.entry_of_row; plan->n_rows = n_rows; plan->ori = ul.ori; plan->code = B->code.as<u32>(); plan->counters = a.counters;
-    return hipGetLastError();
+    const PlacementArrays pa{B->entry_of_row.as<u32>(), B->unitig_of_entry.as<u32>(), B->code.as<u32>(), B->counters.as<u64>(), RP_C_N};
+    return placement_begin(pa, ul, index, n_rows, s, plan);
 }
 
 hipError_t read_paths_end(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, hipStream_t s, ReadPathResult* out) {

@@ -1,5 +1,5 @@
 // results.inc — what a context derives from its table and keeps for the caller (the host copy of the node table, the edge list, the unitig list, components, contigs,
-// node sequences, read paths) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
+// node sequences, read paths, junction support) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
 namespace {
 // the buffers of one graph stage: created on first use, destroyed with the context
 template <class B, B* (*Create)(), void (*Destroy)(B*)> struct StageBuffers {
@@ -19,7 +19,7 @@ struct Results {
     // ---- per result: the stage's buffers, the last device result, the host copy, the device time of the last call
     struct { HostRaw<u64> keys, shift_full, src_read, src_start, src_end; HostRaw<u32> index, seqlen; HostRaw<u16> abund, shift; HostRaw<u8> rev; } nodes;
     struct { StageBuffers<EdgeBuffers, edge_buffers_create, edge_buffers_destroy> buf; EdgeResult last{}; EdgeColumns h; } edges;      // (buf also sorts for resolve_wrapped)
-    struct { StageBuffers<UnitigBuffers, unitig_buffers_create, unitig_buffers_destroy> buf; UnitigResult last{};      // last: of the last unitig / simplify call; contigs, components and read paths read it
+    struct { StageBuffers<UnitigBuffers, unitig_buffers_create, unitig_buffers_destroy> buf; UnitigResult last{};      // last: of the last unitig / simplify call; contigs, components, read paths and junctions read it
              HostRaw<u64> off, sread, sbegin, dst, length, kc; HostRaw<u32> node, len; HostRaw<u8> ori, rc, circ; EdgeColumns he;
              std::vector<u64> removed_unitigs, removed_nodes; } unitigs;                                                 // per-step removal counts of the last mdbg_graph_simplify
     struct { StageBuffers<ComponentBuffers, component_buffers_create, component_buffers_destroy> buf;                    // its result lives until the next component call or simplify call with a component step
@@ -30,6 +30,8 @@ struct Results {
              HostRaw<u8> bases; HostRaw<u64> off; double ms = 0; } nseq;
     struct { StageBuffers<ReadPathBuffers, read_path_buffers_create, read_path_buffers_destroy> buf;                     // its result lives until the next read-path call
              HostRaw<u64> ord, off, supw, sups; HostRaw<u32> rw, fw, nw, unitig, fe; HostRaw<u8> strand; double ms = 0; } rpaths;
+    struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call
+             HostRaw<u64> support, count; HostRaw<u32> u1, e1, u2, e2; HostRaw<u8> s1, s2; double ms = 0; } junctions;
 
     // ---- what is current.  ONLY the functions from here to prefix_is_summed write these members; everybody else asks the predicates below.
     struct { NodeTable table = NodeTable::NONE; u64 rows = 0;

@@ -7,10 +7,10 @@ import queue
 import threading
 import time
 
-from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, read_path_text, unitig_name
+from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, edge_columns, junction_text, merge_junctions, read_path_text, unitig_name
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
-READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths call of run_file
+READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions call of run_file
 
 
 def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max):
@@ -23,7 +23,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -36,6 +36,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     read_paths (with contigs): also write <prefix>.unitigs.read_paths.tsv, one line `ordinal<TAB>windows<TAB>placed<TAB>path` per read in the order of the store:
     which unitigs the read walks (Mdbg.graph_read_paths; api.read_path_text gives the format), and with simplify <prefix>.msimpl.read_paths.tsv for the
     simplified list.  Adds n_read_steps (and n_read_steps_simplified).  The other files are unchanged.
+    junctions (with contigs): also write <prefix>.unitigs.junctions.tsv: per edge record of the unitig list its L line with the number of reads that cross it
+    appended, then one X line per place where reads cross and no record exists (Mdbg.graph_junctions; api.junction_text gives the format), and with simplify
+    <prefix>.msimpl.junctions.tsv for the simplified list.  Adds n_junction_records, n_junction_records_unsupported, n_crossings and n_missing_crossings (and
+    their _simplified twins).  The other files are unchanged.
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -167,6 +171,19 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                         f.write(read_path_text(rp, ul.circular))
                         comp[key] += rp["n_steps"]
                         first += rp["n_reads"]
+            def write_junctions(ul, path_, suffix):      # the same ranges; supports summed and missing keys merged on the host
+                parts, first = [], 0
+                while True:
+                    jx = m.graph_junctions(first, READ_PATH_CHUNK)
+                    if not jx["n_reads"]:
+                        break
+                    parts.append(jx)
+                    first += jx["n_reads"]
+                jx = merge_junctions(parts)
+                with open(path_, "w") as f:
+                    f.write(junction_text(edge_columns(ul.edges), jx["support"], jx, ul.circular))
+                comp.update({"n_junction_records" + suffix: jx["n_records"], "n_junction_records_unsupported" + suffix: int((jx["support"] == 0).sum()),
+                             "n_crossings" + suffix: jx["n_crossings"], "n_missing_crossings" + suffix: jx["n_missing_crossings"]})
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
@@ -174,6 +191,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_components(sl, prefix + ".msimpl.components.tsv", "n_components_simplified")
                 if read_paths:
                     write_read_paths(sl, prefix + ".msimpl.read_paths.tsv", "n_read_steps_simplified")
+                if junctions:
+                    write_junctions(sl, prefix + ".msimpl.junctions.tsv", "_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
@@ -185,6 +204,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_components(ul, prefix + ".unitigs.components.tsv", "n_components")
                 if read_paths:
                     write_read_paths(ul, prefix + ".unitigs.read_paths.tsv", "n_read_steps")
+                if junctions:
+                    write_junctions(ul, prefix + ".unitigs.junctions.tsv", "")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
