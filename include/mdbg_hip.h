@@ -358,7 +358,8 @@ typedef struct mdbg_unitig_list {
 int mdbg_graph_unitigs(mdbg_ctx* ctx, mdbg_unitig_list* out);
 int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
 
-/* ---- graph simplification: tip clipping, simple-bubble popping (the -t / -b rounds of utils/magic_simplify) and small-component removal ----
+/* ---- graph simplification: tip clipping, simple-bubble popping (the -t / -b rounds of utils/magic_simplify), small-component removal and
+ * ---- the pruning of edges no read crosses ----
  * Runs a caller-given schedule of steps on the GPU and returns the unitig list (same layout, same ownership rule, same state
  * requirements as mdbg_graph_unitigs: a current edge list, SINGLE GPU ONLY) of the graph that is left.  With n_steps = 0 the result
  * equals mdbg_graph_unitigs array for array.  The first `gfatools asm` line of utils/magic_simplify is the schedule
@@ -368,10 +369,11 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  * depends on vertex order; the rules below are order-free (a parallel implementation and a dictionary-and-set checker must agree:
  * tests/simplify_restatement.py).  The two outputs have never been compared.
  *
- *   State: a set S of surviving nodes, at first all nodes of the table.  The current graph is the arc set of mdbg_graph_unitigs
- *   restricted to arcs whose two nodes are in S; the current unitigs are its unitigs by the definition above (order, orientation,
- *   names, length, kc_sum unchanged).  A step chooses unitigs to remove — every decision against the graph as it is when the step
- *   starts — and removes all their nodes from S.
+ *   State: a set S of surviving nodes, at first all nodes of the table, and a set D of removed arcs, closed under mirroring and at first
+ *   empty.  The current graph is the arc set of mdbg_graph_unitigs restricted to arcs whose two nodes are in S, minus D; the current
+ *   unitigs are its unitigs by the definition above (order, orientation, names, length, kc_sum unchanged).  Every step kind decides on
+ *   that graph, as it is when the step starts, and every compaction compacts it.  A TIPS, BUBBLES or COMPONENTS step chooses unitigs
+ *   to remove and removes all their nodes from S; an EDGES step chooses edge records and puts their arcs into D.
  *   A unitig is SMALL for a step iff it is not circular, has at most max_nodes entries and length <= max_bases (0 = no limit).
  *   a BEATS b: higher mean abundance kc_sum / entries (compared exactly by cross-multiplication), then larger length, then the
  *   smaller unitig number.
@@ -392,13 +394,35 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   is removed; unitigs_removed[k] / nodes_removed[k] count as for the other kinds.  max_nodes == 0 && max_bases == 0 is MDBG_E_PARAM for this kind
  *   (it would delete the graph).  A step may remove everything that is left: the call then returns MDBG_OK with the empty list (n_unitigs ==
  *   n_entries == 0, edges.n == 0).  The schedule of utils/magic_simplify has no such step.
- *   Result: n_entries = |S|; edges = every edge record whose two nodes survive and whose arc is not an interior link, in source order.
- * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
+ *   EDGES, {MDBG_SIMPLIFY_EDGES, min_support, 0}: for this kind the field max_nodes carries min_support (>= 1) and max_bases is reserved (0).  An edge of
+ *   the graph does not come from a read (mdbg_graph_junctions below): a repeat of exactly k-1 minimizers that two contexts share puts a full 2 x 2 cross of
+ *   edges into the graph, two of which no read ever took.  The step decides against the edge records of the current unitig list as they are when the
+ *   step starts.  support[r] is what mdbg_graph_junctions gives for record r of that list over the WHOLE resident store (first_read = 0, max_reads = 0).
+ *   Let x -> y be the node-level arc of r: x the last vertex of n1 in orientation o1, y the first vertex of n2 in orientation o2.  r is STRONG iff
+ *   support[r] >= min_support, else WEAK.  A vertex v HAS A STRONG EXIT iff some strong record has an arc, or the mirror of its arc, with source v.  A weak
+ *   record is REMOVED iff x has a strong exit and comp(y) has a strong exit — reads leave x another way, and reads enter y another way; its arc and the
+ *   mirror arc join D.  Records with equal junction keys carry equal supports, so a record, its mirror record and their duplicates fall together.
+ *   Consequences: an interior link is never removed (it is the only exit of its source, and it has no record); a weak edge that is the only way, supported
+ *   or not, out of a dead-end side stays, so a coverage gap does not cut a contig; the step removes no node (unitigs_removed[k] == nodes_removed[k] == 0
+ *   for it); a compaction follows iff it removed a record; if no read is resident nothing is strong and the step removes nothing.  The removed records are
+ *   counted by mdbg_simplify_edges_removed.
+ *   Result: n_entries = |S|; edges = every edge record whose two nodes survive, whose arc is not in D and is not an interior link, in source order.
+ * An EDGES step needs what mdbg_graph_junctions needs on top of a current edge list — the node table current, the bounds of the read paths —, and the call
+ * refuses with the same code before anything is launched; the context stays usable.  The step uses the context's junction buffers: a junction result the
+ * caller holds ends with a simplify call that has an EDGES step, exactly as a component result ends with one that has a COMPONENTS step; a held read-path,
+ * component or contig result is untouched.  The defect flags of the junction stage surface as MDBG_E_DEVICE.
+ * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, an EDGES step with min_support == 0 or max_bases != 0, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
  * entries owned by the context (valid like the list); n_compactions: compactions run (a step that removes nothing is followed by none);
- * n_syncs: host synchronisations of the call (per step: those of one compaction + 1; a COMPONENTS step adds none of its own). */
+ * n_syncs: host synchronisations of the call (per step: those of one compaction + 1; a COMPONENTS step adds none of its own; an EDGES step that has
+ * records and resident reads to look at waits twice — the one wait of its junction stage, then its own counter, which the junction stage's wait cannot
+ * carry because the decision reads the supports — and is followed by a compaction only if it removed a record).
+ * mdbg_simplify_edges_removed: *per_step <- n_steps HOST entries of the last simplify call, owned by the context and valid like unitigs_removed;
+ * per_step[k] = the node-level edge records step k put into D (mirror records and duplicates counted as records; 0 for the other kinds); *total <- their
+ * sum.  Either pointer may be NULL.  mdbg_simplify_stats keeps its layout. */
 #define MDBG_SIMPLIFY_TIPS 1u
 #define MDBG_SIMPLIFY_BUBBLES 2u
 #define MDBG_SIMPLIFY_COMPONENTS 4u
+#define MDBG_SIMPLIFY_EDGES 8u     /* {EDGES, min_support, 0} */
 typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
 typedef struct mdbg_simplify_stats {
     uint32_t n_steps, n_compactions;
@@ -408,6 +432,7 @@ typedef struct mdbg_simplify_stats {
 } mdbg_simplify_stats;
 int mdbg_graph_simplify(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
 int mdbg_graph_simplify_device(mdbg_ctx* ctx, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats);
+int mdbg_simplify_edges_removed(mdbg_ctx* ctx, const uint64_t** per_step, uint64_t* total);
 
 /* ---- connected components of the unitig graph ---------------------------------------------------------------------------------
  * Which unitigs belong together: what the reference's users get from splitting a .gfa by weakly connected component.  The call works on the context's
@@ -571,11 +596,12 @@ int mdbg_read_paths_ms(mdbg_ctx* ctx, double* ms);
  * which ends a caller's loop `first_read += n_reads`.  The temporaries are 25 bytes per minimizer index of the range (the place codes 4, the keys of the missing
  * crossings and their sorted copy 16, head flags 1, positions 4) beside the sort's own, and the missing columns are sized for their worst case, another 26 bytes per
  * index, because their number is known only on the device: the range bounds both.  Per edge record the call takes 32 bytes of temporaries and 8 of result.
- * mdbg_graph_junctions: HOST arrays; mdbg_graph_junctions_device: DEVICE arrays.  They belong to the context until its next junction call or mdbg_destroy and share
- * memory with no other result — a read-path result the caller holds is untouched —, and the call leaves the node table, the edge list, the unitig list and the contig,
+ * mdbg_graph_junctions: HOST arrays; mdbg_graph_junctions_device: DEVICE arrays.  They belong to the context until its next junction call, its next simplify call with an EDGES
+ * step or mdbg_destroy and share memory with no other result — a read-path result the caller holds is untouched —, and the call leaves the node table, the edge list, the unitig list and the contig,
  * component and read-path results as they are.  The number of kernel launches is fixed; the device variant waits for the device ONCE (all counts and the defect flag
  * in one read-back) when the range starts and ends where batches do, otherwise once more, up front, for the range's two offsets.
- * mdbg_junctions_ms: device time of the last junction call (HIP events; 0 if it launched nothing).
+ * mdbg_junctions_ms: device time of the last junction call (HIP events; 0 if it launched nothing); after a simplify call with EDGES steps, the device time
+ * of their junction stages, summed.
  * MDBG_E_STATE: no current unitig list, the node table is not current, or a routed / partitioned context; MDBG_E_PARAM: a null pointer; MDBG_E_CAPACITY: the bounds of
  * the read paths (2^30 entries, 2^32 minimizers in the range) or 2^32 edge records; MDBG_E_DEVICE: the defect flags of the read paths, or an edge record that names a
  * unitig outside the list.  An empty context, an empty list or first_read >= the number of reads gives MDBG_OK with every count zero (n_records included) and no

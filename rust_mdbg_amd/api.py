@@ -190,6 +190,7 @@ class SimplifyStats(C.Structure):      # mdbg_simplify_stats
 
 MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
 MDBG_SIMPLIFY_COMPONENTS = 4      # (kind, max_nodes, max_bases): every unitig of a non-circular connected component of at most max_nodes nodes and max_bases bases goes
+MDBG_SIMPLIFY_EDGES = 8           # (kind, min_support, 0): every edge record crossed by fewer than min_support resident reads goes where reads leave its source and enter its target another way
 _T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
 # the schedule of the first `gfatools asm` line of utils/magic_simplify, as (kind, max_nodes, max_bases): -t N,L = tips of at most N nodes and L bases,
 # -b L = bubbles whose branches have at most L bases.  Same schedule, this project's own order-free rules (include/mdbg_hip.h): not gfatools parity.
@@ -227,7 +228,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_routed_export", "mdbg_resolve_first", "mdbg_resolve_meta", "mdbg_routed_keys", "mdbg_arena_reserve",
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
-           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
+           "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_simplify_edges_removed", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
            "mdbg_graph_junctions", "mdbg_graph_junctions_device", "mdbg_junctions_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
@@ -331,6 +332,7 @@ def load_library():
     L.mdbg_graph_read_paths.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
     L.mdbg_graph_read_paths_device.argtypes = [vp, u64, u64, C.POINTER(ReadPathList)]
     L.mdbg_read_paths_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mdbg_simplify_edges_removed.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
     L.mdbg_graph_junctions.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
     L.mdbg_graph_junctions_device.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
     L.mdbg_junctions_ms.argtypes = [vp, C.POINTER(C.c_double)]
@@ -611,17 +613,19 @@ class Mdbg:
         self._chk(self.L.mdbg_graph_unitigs_device(self.h, C.byref(u)))
         return u
 
-    @staticmethod
-    def _simplify_stats(st):
+    def _simplify_stats(self, st):
         n = int(st.n_steps)
+        per_step, total = C.POINTER(C.c_uint64)(), C.c_uint64()
+        self._chk(self.L.mdbg_simplify_edges_removed(self.h, C.byref(per_step), C.byref(total)))
         return dict(unitigs_removed=[int(st.unitigs_removed[i]) for i in range(n)], nodes_removed=[int(st.nodes_removed[i]) for i in range(n)],
-                    total_unitigs_removed=int(st.total_unitigs_removed), total_nodes_removed=int(st.total_nodes_removed), n_compactions=int(st.n_compactions),
+                    edges_removed=[int(per_step[i]) for i in range(n)], total_unitigs_removed=int(st.total_unitigs_removed),
+                    total_nodes_removed=int(st.total_nodes_removed), total_edges_removed=int(total.value), n_compactions=int(st.n_compactions),
                     n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs))
 
     def graph_simplify(self, steps, raw=False):
-        """the unitigs that are left after a schedule of tip, simple-bubble and small-component steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
+        """the unitigs that are left after a schedule of tip, simple-bubble, small-component and edge-pruning steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
         project's own order-free rules in the spirit of `gfatools asm -t N,L -b L`, NOT bit-parity with gfatools).  steps: [(kind, max_nodes, max_bases)], e.g.
-        MAGIC_SIMPLIFY_STEPS; an empty schedule gives graph_unitigs().  -> the dict of graph_unitigs() plus `stats` (per step: unitigs / nodes removed; totals);
+        MAGIC_SIMPLIFY_STEPS; an empty schedule gives graph_unitigs().  -> the dict of graph_unitigs() plus `stats` (per step: unitigs / nodes / edge records removed; totals);
         raw=True: (the C struct with HOST arrays, stats)"""
         arr, n = simplify_steps(steps)
         u, st = UnitigList(), SimplifyStats()

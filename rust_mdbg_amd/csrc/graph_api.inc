@@ -52,22 +52,36 @@ int mdbg_graph_edges_device(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { r
 
 // ---- unitigs + base-space copy plan of the last node table and edge list (unitigs.hip) -------------------
 // steps == nullptr: plain compaction (mdbg_graph_unitigs); otherwise the schedule runs first (mdbg_graph_simplify, simplify.hip) and stats is filled
+// (what an EDGES step shares with the read paths and the junction support, defined beside them below)
+static int store_range(mdbg_ctx* c, uint64_t n_unitigs, uint64_t n_entries, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty);
+static int placement_defect(mdbg_ctx* c, uint32_t defect);
+static const char* const JX_EDGE_DEFECT_TEXT = "an edge record of the unitig list names a unitig outside the list";
+// the window placer as simplify.hip calls it between the two halves of the junction stage (SimplifySupport::place)
+struct PlaceForSimplify { mdbg_ctx* c; FinArgs F; ReadPathRange rg; };
+static void place_for_simplify(void* ctx, const ReadPathPlan& plan, hipStream_t s) {
+    const PlaceForSimplify& p = *(const PlaceForSimplify*)ctx;
+    launch_place_windows(table_args(p.c), p.F, p.c->fin_words, plan, p.F.mh, p.F.mread, p.F.roff, p.rg.i0, p.rg.i1, s);
+}
 static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats, bool to_host) {
     MDBG_ENTER(c, out && !(stats && n_steps && !steps));
     memset(out, 0, sizeof *out);
     Results& R = c->res;
     auto& UL = R.unitigs;
-    bool with_components = false;
+    bool with_components = false, with_edges = false;
     if (stats) {
         memset(stats, 0, sizeof *stats);
         for (uint32_t i = 0; i < n_steps; ++i) {
             const uint32_t kind = steps[i].kind;
-            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS) return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES)
+                return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+            if (kind == MDBG_SIMPLIFY_EDGES && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
+                return fail(c, MDBG_E_PARAM, "an edge step takes {EDGES, min_support >= 1, 0}");
+            with_edges |= kind == MDBG_SIMPLIFY_EDGES;
             if (kind == MDBG_SIMPLIFY_COMPONENTS && steps[i].max_nodes == 0 && steps[i].max_bases == 0)
                 return fail(c, MDBG_E_PARAM, "a component step without a limit would remove the whole graph");
             with_components |= kind == MDBG_SIMPLIFY_COMPONENTS;
         }
-        UL.removed_unitigs.assign(n_steps, 0); UL.removed_nodes.assign(n_steps, 0);
+        UL.removed_unitigs.assign(n_steps, 0); UL.removed_nodes.assign(n_steps, 0); UL.removed_edges.assign(n_steps, 0);
         stats->n_steps = n_steps; stats->unitigs_removed = UL.removed_unitigs.data(); stats->nodes_removed = UL.removed_nodes.data();
     }
     R.invalidate(FROM_UNITIGS); UL.last = UnitigResult{};
@@ -76,14 +90,28 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (!R.edge_list_current()) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
     if (R.n_rows() == 0) { R.unitig_list_is(UnitigResult{}); return MDBG_OK; }
     if (with_components) R.comps.buf.get();
+    SimplifySupport sup{}; PlaceForSimplify pfs{};
+    if (with_edges) {                                // what the junction support asks, before anything of the schedule is launched
+        if (R.edges.last.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
+        bool empty;
+        const int e = store_range(c, 1, R.n_rows(), 0, 0, &pfs.rg, &pfs.F, &empty);
+        if (e) return e;
+        pfs.c = c;
+        sup.jb = R.junctions.buf.get(); sup.index = c->finF.o_index; sup.n_rows = R.n_rows(); sup.range = pfs.rg; sup.has_reads = !empty; sup.place = place_for_simplify; sup.ctx = &pfs;
+        R.junctions.ms = 0;
+    }
     const FinArgs& F = c->finF;
     UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
     nd.reversed = F.o_rev; nd.n = R.n_rows();
     UnitigResult r; int broken = 0;
     SimplifyInfo si{};
-    const hipError_t he = stats ? simplify_unitigs(UL.buf.get(), R.comps.buf.have(), nd, R.edges.last, steps, n_steps, c->stream, &r, UL.removed_unitigs.data(), UL.removed_nodes.data(), &si, &broken)
+    const hipError_t he = stats ? simplify_unitigs(UL.buf.get(), R.comps.buf.have(), with_edges ? &sup : nullptr, nd, R.edges.last, steps, n_steps, c->stream, &r, UL.removed_unitigs.data(),
+                                                   UL.removed_nodes.data(), UL.removed_edges.data(), &si, &broken)
                                 : build_unitigs(UL.buf.get(), nd, R.edges.last, c->stream, &r, &broken);
     if (he != hipSuccess) return fail_hip(c, "build_unitigs", he);
+    if (with_edges) R.junctions.ms = si.junction_ms;
+    if (broken && (si.junction_defect & JX_DEFECT_EDGE)) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
+    if (broken && si.junction_defect) return placement_defect(c, si.junction_defect);
     if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, or the walk broke an invariant");
     if (stats) {
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
@@ -115,6 +143,14 @@ int mdbg_graph_simplify(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
 }
 int mdbg_graph_simplify_device(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats) {
     return stats ? unitigs_impl(c, steps, n_steps, out, stats, false) : MDBG_E_PARAM;
+}
+int mdbg_simplify_edges_removed(mdbg_ctx* c, const uint64_t** per_step, uint64_t* total) {
+    if (!c) return MDBG_E_PARAM;
+    MDBG_LOCK(c);
+    const std::vector<u64>& v = c->res.unitigs.removed_edges;
+    if (per_step) *per_step = v.data();
+    if (total) { *total = 0; for (u64 x : v) *total += x; }
+    return MDBG_OK;
 }
 
 // ---- connected components of the current unitig list (components.hip) -------------------------------------
@@ -243,13 +279,19 @@ static bool known_read_offset(const mdbg_ctx* c, u64 r, u64* v) {
 // arrays.  what_is: "read paths are", ...  *empty <- the call answers MDBG_OK with zero counts (an empty context, an empty list, a range behind the store).
 static int placement_range(mdbg_ctx* c, const char* what_is, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty) {
     *empty = true;
-    Results& R = c->res;
     int e;
     if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
+    const UnitigResult& ul = c->res.unitigs.last;
+    return store_range(c, ul.n_unitigs, ul.n_entries, first_read, max_reads, range, fin, empty);
+}
+// placement_range behind its two refusals, for a list of n_unitigs unitigs and n_entries entries: an EDGES step of a simplify schedule (unitigs_impl) asks it for
+// the lists it is going to build, which have at most as many entries as the table has rows
+static int store_range(mdbg_ctx* c, uint64_t n_unitigs, uint64_t n_entries, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty) {
+    *empty = true;
+    Results& R = c->res;
     if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
-    const UnitigResult& ul = R.unitigs.last;
-    if (ul.n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;
-    if (ul.n_entries >= (1ull << 30) || R.n_rows() >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
+    if (n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;
+    if (n_entries >= (1ull << 30) || R.n_rows() >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
     hipStream_t s = c->stream;
     const u64 r0 = first_read, r1 = max_reads && max_reads < c->n_slots - r0 ? r0 + max_reads : c->n_slots;
     ReadPathRange rg{};
@@ -335,7 +377,7 @@ static int junctions_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, 
     he = junctions_end(J.buf.get(), ul, rg, s, &r);
     if (he != hipSuccess) return fail_hip(c, "junctions_end", he);
     J.ms = r.ms;
-    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, "an edge record of the unitig list names a unitig outside the list");
+    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
     if (r.defect) return placement_defect(c, r.defect);
     const u64 nrec = r.n_records, nm = r.n_missing;
     out->n_reads = r.n_reads; out->n_adjacent = r.n_adjacent; out->n_links = r.n_links; out->n_crossings = r.n_crossings; out->n_explained = r.n_explained;

@@ -21,7 +21,7 @@ struct Results {
     struct { StageBuffers<EdgeBuffers, edge_buffers_create, edge_buffers_destroy> buf; EdgeResult last{}; EdgeColumns h; } edges;      // (buf also sorts for resolve_wrapped)
     struct { StageBuffers<UnitigBuffers, unitig_buffers_create, unitig_buffers_destroy> buf; UnitigResult last{};      // last: of the last unitig / simplify call; contigs, components, read paths and junctions read it
              HostRaw<u64> off, sread, sbegin, dst, length, kc; HostRaw<u32> node, len; HostRaw<u8> ori, rc, circ; EdgeColumns he;
-             std::vector<u64> removed_unitigs, removed_nodes; } unitigs;                                                 // per-step removal counts of the last mdbg_graph_simplify
+             std::vector<u64> removed_unitigs, removed_nodes, removed_edges; } unitigs;                                  // per-step removal counts of the last mdbg_graph_simplify
     struct { StageBuffers<ComponentBuffers, component_buffers_create, component_buffers_destroy> buf;                    // its result lives until the next component call or simplify call with a component step
              HostRaw<u32> comp, first, unitigs; HostRaw<u64> nodes, bases, kc; HostRaw<u8> circ; } comps;
     struct { StageBuffers<ContigBuffers, contig_buffers_create, contig_buffers_destroy> buf;                             // its result lives until the next contig call (buf also sorts the exceptions of a kept batch)
@@ -30,7 +30,7 @@ struct Results {
              HostRaw<u8> bases; HostRaw<u64> off; double ms = 0; } nseq;
     struct { StageBuffers<ReadPathBuffers, read_path_buffers_create, read_path_buffers_destroy> buf;                     // its result lives until the next read-path call
              HostRaw<u64> ord, off, supw, sups; HostRaw<u32> rw, fw, nw, unitig, fe; HostRaw<u8> strand; double ms = 0; } rpaths;
-    struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call
+    struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call or simplify call with an EDGES step
              HostRaw<u64> support, count; HostRaw<u32> u1, e1, u2, e2; HostRaw<u8> s1, s2; double ms = 0; } junctions;
 
     // ---- what is current.  ONLY the functions from here to prefix_is_summed write these members; everybody else asks the predicates below.

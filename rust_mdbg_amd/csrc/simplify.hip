@@ -1,5 +1,6 @@
-// simplify.hip — tip clipping and simple-bubble popping on the unitig graph, on the GPU (gfx950).  It reads the arrays of the compaction stage (unitigs.hip; shown
-// by unitigs_priv.h: sorted arcs, settled ranking, unitig numbers, lengths, abundance sums) and calls that compaction again under a node mask.
+// simplify.hip — tip clipping, simple-bubble popping, small-component removal and the pruning of edges no read crosses, on the unitig graph, on the GPU (gfx950).
+// It reads the arrays of the compaction stage (unitigs.hip; shown by unitigs_priv.h: sorted arcs, settled ranking, unitig numbers, lengths, abundance sums, the
+// records' vertices and unitig edge positions) and calls that compaction again under a node mask and, once an EDGES step has removed a record, a record mask.
 //
 // The rules are the ones written out in include/mdbg_hip.h (mdbg_graph_simplify): this project's own order-free definition in the spirit of
 // `gfatools asm -t N,L -b L`, NOT gfatools' in-place passes.  A step decides against the graph as it is when the step starts, so every kernel below reads
@@ -16,8 +17,14 @@
 //   comp_decide_kernel   unitig of a small component (components.hip: nodes, bases and circular summed per component) -> removed
 //   scatter_kernel       vertices of removed unitigs -> alive[row] = 0; counts the nodes
 //
-// Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks.  A step that
-// removes nothing is followed by no compaction: the next step decides on the same arrays.
+// MDBG_SIMPLIFY_EDGES removes edge records, not nodes: the junction stage (junctions.hip) counts the reads that cross each unitig edge record of the current
+// list, and two kernels over the node-level records of the last compaction (eu / ev: their vertices, ekeep / epos: their unitig record) decide:
+//   edge_mark_kernel     kept record whose unitig record has support >= min_support -> strong[eu] = strong[comp(ev)] = 1 (plain stores of one value)
+//   edge_decide_kernel   kept weak record with strong[eu] and strong[comp(ev)] -> edge_alive[e] = 0; counts the records
+// The record mask is closed under mirroring and duplication because equal junction keys carry equal supports; the next compaction takes it beside the node mask.
+//
+// Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks; an EDGES step
+// waits once for its junction stage and once for its counter.  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
 #include <cstring>
 
 #include "simplify.h"
@@ -173,11 +180,39 @@ __global__ __launch_bounds__(256) void scatter_kernel(SimpArgs a) {
     count_to(a.ctr + 1, gone);
 }
 
+// MDBG_SIMPLIFY_EDGES.  Node-level record e of the last compaction: vertices eu[e] -> ev[e] (NONE: an end or the record was removed before), ekeep[e] = it is a
+// unitig edge record, the one at epos[e] of the current list (an interior link has none and is never touched)
+struct EdgeArgs {
+    u64 n_edges, n_records; u32 n2x, min_support;
+    const u32* eu; const u32* ev; const u32* ekeep; const u32* epos; const u64* support;
+    u8* strong; u8* edge_alive; u32* ctr;
+};
+__device__ inline bool edge_record(const EdgeArgs& a, u64 e, u32* x, u32* cy, bool* is_strong) {      // false: no unitig edge record (or one outside the arrays: never indexed)
+    if (e >= a.n_edges || !a.ekeep[e]) return false;
+    const u32 u = a.eu[e], v = a.ev[e], r = a.epos[e];
+    if (u >= a.n2x || v >= a.n2x || r >= a.n_records) return false;
+    *x = u; *cy = v ^ 1; *is_strong = a.support[r] >= a.min_support;
+    return true;
+}
+__global__ __launch_bounds__(256) void edge_mark_kernel(EdgeArgs a) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u32 x, cy; bool is_strong;
+    if (edge_record(a, e, &x, &cy, &is_strong) && is_strong) { a.strong[x] = 1; a.strong[cy] = 1; }      // reads leave x here, and comp(y) by the mirror
+}
+__global__ __launch_bounds__(256) void edge_decide_kernel(EdgeArgs a) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u32 x, cy; bool is_strong;
+    const bool gone = edge_record(a, e, &x, &cy, &is_strong) && !is_strong && a.strong[x] && a.strong[cy];
+    if (gone) a.edge_alive[e] = 0;
+    count_to(a.ctr, gone);
+}
+
 }  // namespace
 
-hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps, hipStream_t s, UnitigResult* out,
-                     uint64_t* unitigs_removed, uint64_t* nodes_removed, SimplifyInfo* info, int* broken) {
+hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const SimplifySupport* sup, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps,
+                     hipStream_t s, UnitigResult* out, uint64_t* unitigs_removed, uint64_t* nodes_removed, uint64_t* edges_removed, SimplifyInfo* info, int* broken) {
     memset(info, 0, sizeof *info);
+    for (uint32_t k = 0; k < n_steps; ++k) edges_removed[k] = 0;
     if (n_steps == 0 || nd.n == 0) {                          // the empty schedule IS the unitig call
         const hipError_t rc = build_unitigs(B, nd, ed, s, out, broken);
         if (rc == hipSuccess && !*broken && nd.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed.n ? 1 : 0); }
@@ -191,10 +226,11 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Unitig
     GHIP(hipMemsetAsync(B->alive.p, 1, n, s));
     u8* alive = B->alive.as<u8>();
     u64 n_alive = n;
+    const u8* edge_alive = nullptr;                           // null until an EDGES step removes a record: a schedule without one compacts as it always did
     bool stale = true;                                        // the arrays of the last compaction no longer describe the surviving graph
     auto compact = [&]() -> hipError_t {
         if (n_alive == 0) { memset(out, 0, sizeof *out); stale = false; return hipSuccess; }      // a step removed all that was left: the empty list, nothing to launch
-        GHIP(build_unitigs_masked(B, nd, ed, alive, n_alive, s, out, broken));
+        GHIP(build_unitigs_masked(B, nd, ed, alive, n_alive, edge_alive, s, out, broken));
         if (*broken) return hipSuccess;
         ++info->n_compactions; info->n_rounds_total += out->n_rounds; info->n_syncs += out->n_rounds + 3 + (ed.n ? 1 : 0);
         stale = false;
@@ -205,6 +241,37 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Unitig
         if (stale) { GHIP(compact()); if (*broken) return hipSuccess; }
         const u64 U = out->n_unitigs;
         if (U == 0) continue;
+        if (steps[k].kind == MDBG_SIMPLIFY_EDGES) {
+            if (!sup) return hipErrorInvalidValue;
+            const u64 E = ed.n, UE = out->edges.n;
+            if (!sup->has_reads || E == 0 || UE == 0) continue;      // nothing is strong, or there is no record: the step removes nothing
+            if (!edge_alive) { GHIP(B->edge_alive.ensure(E)); GHIP(hipMemsetAsync(B->edge_alive.p, 1, E, s)); }      // (not handed to a compaction before a record goes)
+            GHIP(B->strong.ensure(n2x));
+            ReadPathPlan plan; JunctionResult jr;
+            GHIP(junctions_begin(sup->jb, *out, sup->index, sup->n_rows, sup->range, s, &plan));
+            sup->place(sup->ctx, plan, s);
+            GHIP(junctions_end(sup->jb, *out, sup->range, s, &jr));
+            ++info->n_syncs; info->junction_ms += jr.ms;
+            if (jr.defect) { info->junction_defect = jr.defect; return defect(broken); }
+            if (jr.n_records != UE) return defect(broken);
+            u32* d_ctr = B->ctr.as<u32>();                    // (the compaction is over: its round counters are free)
+            GHIP(hipMemsetAsync(d_ctr, 0, 4, s));
+            GHIP(hipMemsetAsync(B->strong.p, 0, n2x, s));
+            EdgeArgs ea; memset(&ea, 0, sizeof ea);
+            ea.n_edges = E; ea.n_records = UE; ea.n2x = n2x; ea.min_support = steps[k].max_nodes;
+            ea.eu = B->eu.as<u32>(); ea.ev = B->ev.as<u32>(); ea.ekeep = B->ekeep.as<u32>(); ea.epos = B->epos.as<u32>(); ea.support = jr.support;
+            ea.strong = B->strong.as<u8>(); ea.edge_alive = B->edge_alive.as<u8>(); ea.ctr = d_ctr;
+            hipLaunchKernelGGL(edge_mark_kernel, dim3(grid_for(E)), dim3(256), 0, s, ea);
+            hipLaunchKernelGGL(edge_decide_kernel, dim3(grid_for(E)), dim3(256), 0, s, ea);
+            u32 gone = 0;
+            GHIP(hipMemcpyAsync(&gone, d_ctr, 4, hipMemcpyDeviceToHost, s));
+            GHIP(hipStreamSynchronize(s));
+            ++info->n_syncs;
+            if (gone > UE) return defect(broken);
+            edges_removed[k] = gone;
+            if (gone) { edge_alive = B->edge_alive.as<u8>(); stale = true; }
+            continue;
+        }
         GHIP(B->uhead.ensure(n * 4)); GHIP(B->utail.ensure(n * 4)); GHIP(B->att.ensure(n * 4)); GHIP(B->rem.ensure(n)); GHIP(B->owner.ensure((size_t)n2x * 4));
         u32* d_ctr = B->ctr.as<u32>();                        // (the compaction is over: its round counters are free)
         GHIP(hipMemsetAsync(d_ctr, 0, 8, s));

@@ -9,7 +9,8 @@
 // comp(v)->comp(u), hence closed under mirroring: the in-degree of v is the out-degree of comp(v), and ONE sort of the 2E arcs by
 // (source, target) gives every degree the link test needs — no second sort, no degree atomics.
 //
-//   arc_kernel       edge record -> its two vertices (binary search of index -> row) and its two arcs as u64 keys; rocPRIM sorts them
+//   arc_kernel       edge record -> its two vertices (binary search of index -> row) and its two arcs as u64 keys; rocPRIM sorts them.  Under simplify.hip's
+//                    masks a record with a removed end, or a removed record, gets no vertices and two arcs at source 2n, behind every vertex
 //   succ_kernel      first arc of every source group: the unique successor if the group holds one distinct target
 //   link_kernel      u->v is a link iff u has one distinct out-arc, v one distinct in-arc, node(u) != node(v); next / prev per vertex and the
 //                    start state of the ranking
@@ -38,12 +39,13 @@ __device__ inline u32 row_of(const u32* __restrict__ index, u32 n, u32 idx) {
 }
 
 __global__ __launch_bounds__(256) void arc_kernel(u64 n_edges, const u32* __restrict__ n1, const u8* __restrict__ o1, const u32* __restrict__ n2, const u8* __restrict__ o2,
-                                                  const u32* __restrict__ index, u32 n, const u8* __restrict__ alive, u32* __restrict__ eu, u32* __restrict__ ev, u64* __restrict__ keys,
+                                                  const u32* __restrict__ index, u32 n, const u8* __restrict__ alive, const u8* __restrict__ edge_alive, u32* __restrict__ eu, u32* __restrict__ ev, u64* __restrict__ keys,
                                                   u32* __restrict__ ctr) {
     const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_edges) return;
     const u32 ra = row_of(index, n, n1[e]), rb = row_of(index, n, n2[e]);
-    if (alive && ra != NONE && rb != NONE && !(alive[ra] && alive[rb])) {      // an end was removed (simplify.hip): no vertices, and both arcs sort behind every vertex (source 2n)
+    // an end was removed, or the record itself (simplify.hip): no vertices, and both arcs sort behind every vertex (source 2n)
+    if (ra != NONE && rb != NONE && ((alive && !(alive[ra] && alive[rb])) || (edge_alive && !edge_alive[e]))) {
         eu[e] = NONE; ev[e] = NONE; keys[2 * e] = (u64)(2 * n) << 32; keys[2 * e + 1] = (u64)(2 * n) << 32; return;
     }
     if (ra == NONE || rb == NONE) { ctr[C_ERR] = 1; eu[e] = 0; ev[e] = 0; keys[2 * e] = 0; keys[2 * e + 1] = 0; return; }      // an edge of another table: reported by the host
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256) void uedge_kernel(UedgeArgs a) {
     const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.n_edges) return;
     const u32 u = a.eu[e], v = a.ev[e];
-    if (u == NONE) { if (!WRITE) a.keep[e] = 0; return; }      // a record of a removed node
+    if (u == NONE) { if (!WRITE) a.keep[e] = 0; return; }      // a record of a removed node, or a removed record
     // interior link: a link that is not the closing link of a circular unitig (its target is the kept head) nor that link's mirror (its source is the head's complement);
     // a path has no link into its head, and the mirror cycle's own cut lies elsewhere, so only kept heads count
     if (!WRITE) { a.keep[e] = (a.nxt[u] == v && !a.flag[v] && !a.flag[u ^ 1]) ? 0u : 1u; return; }
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void uedge_kernel(UedgeArgs a) {
 UnitigBuffers* unitig_buffers_create() { return new UnitigBuffers(); }
 void unitig_buffers_destroy(UnitigBuffers* b) { delete b; }
 
-hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, int* broken) {
+hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, const u8* edge_alive, hipStream_t s, UnitigResult* out, int* broken) {
     memset(out, 0, sizeof *out);
     *broken = 0;
     const u64 n = nd.n, E = ed.n;
@@ -221,8 +223,8 @@ hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const E
     GHIP(B->eu.ensure(E * 4 + 4)); GHIP(B->ev.ensure(E * 4 + 4));
     if (E) {
         GHIP(B->keys.ensure(2 * E * 8)); GHIP(B->skeys.ensure(2 * E * 8));
-        hipLaunchKernelGGL(arc_kernel, dim3(grid_for(E)), dim3(256), 0, s, E, ed.n1, ed.o1, ed.n2, ed.o2, nd.index, (u32)n, alive, B->eu.as<u32>(), B->ev.as<u32>(), B->keys.as<u64>(), d_ctr);
-        unsigned end_bit = 33; while (end_bit < 64 && (1ull << (end_bit - 32)) < (u64)n2x + (alive ? 1 : 0)) ++end_bit;      // (masked: the source 2n occurs)
+        hipLaunchKernelGGL(arc_kernel, dim3(grid_for(E)), dim3(256), 0, s, E, ed.n1, ed.o1, ed.n2, ed.o2, nd.index, (u32)n, alive, edge_alive, B->eu.as<u32>(), B->ev.as<u32>(), B->keys.as<u64>(), d_ctr);
+        unsigned end_bit = 33; while (end_bit < 64 && (1ull << (end_bit - 32)) < (u64)n2x + (alive || edge_alive ? 1 : 0)) ++end_bit;      // (either mask: the source 2n occurs)
         GHIP(sort_keys(B->tmp, B->keys.as<u64>(), B->skeys.as<u64>(), (size_t)(2 * E), 0, end_bit, s));
         hipLaunchKernelGGL(succ_kernel, dim3(grid_for(2 * E)), dim3(256), 0, s, 2 * E, n2x, B->skeys.as<u64>(), B->succ.as<u32>());
     }
@@ -319,5 +321,5 @@ hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const E
 }
 
 hipError_t build_unitigs(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, hipStream_t s, UnitigResult* out, int* broken) {
-    return build_unitigs_masked(B, nd, ed, nullptr, 0, s, out, broken);
+    return build_unitigs_masked(B, nd, ed, nullptr, 0, nullptr, s, out, broken);
 }

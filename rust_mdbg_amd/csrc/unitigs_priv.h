@@ -22,8 +22,11 @@ struct UnitigBuffers {
     // what the last build_unitigs left for simplify.hip: the settled ranking (one of P[] / D[]), the cycle marks (or null) and the number of sorted arcs in skeys
     const u32* Pfin = nullptr; const u32* Dfin = nullptr; const u8* cycfin = nullptr; u64 n_arcs = 0;
     Buf alive, uhead, utail, att, owner, rem, bkey, bkey2, bval, bval2;      // simplify.hip
+    Buf edge_alive, strong;                                                  // simplify.hip, EDGES steps: the record mask, the vertices with a strong exit
 };
 
-// build_unitigs restricted by `alive` (device, one byte per row of the node table; null = every node) to the surviving nodes and the arcs between them; n_alive = how many
+// build_unitigs restricted by `alive` (device, one byte per row of the node table; null = every node) to the surviving nodes and the arcs between them; n_alive = how many;
+// and by `edge_alive` (device, one byte per record of `ed`; null = every record) to the arcs of the surviving records: a record with edge_alive[e] == 0 is treated
+// exactly as a record with a removed end.  The mask must be closed under mirroring and duplication (a record, its mirror record and their copies fall together).
 // (not part of the library's surface: hidden, as it was while it was static)
-__attribute__((visibility("hidden"))) hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, hipStream_t s, UnitigResult* out, int* broken);
+__attribute__((visibility("hidden"))) hipError_t build_unitigs_masked(UnitigBuffers* B, const UnitigNodes& nd, const EdgeResult& ed, const u8* alive, u64 n_alive, const u8* edge_alive, hipStream_t s, UnitigResult* out, int* broken);

@@ -28,7 +28,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
     to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
-    simplify (with contigs): a schedule of tip / bubble steps, e.g. api.MAGIC_SIMPLIFY_STEPS — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
+    simplify (with contigs): a schedule of tip / bubble / component / edge-pruning steps, e.g. api.MAGIC_SIMPLIFY_STEPS or [(api.MDBG_SIMPLIFY_EDGES, 1, 0)] + those (the
+    sketch store is still resident when the schedule runs, which is all an edge step needs; its count is simplify["total_edges_removed"]) — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
     Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
     components (with contigs): also write <prefix>.unitigs.components.tsv, one line `utgNAME<TAB>component` per unitig: the connected component of the unitig
     graph each unitig lies in (Mdbg.graph_components; numbered by their smallest unitig), and with simplify <prefix>.msimpl.components.tsv for the simplified
