@@ -4,16 +4,24 @@
 // obviously equal to the reference rather than fast.  Only tests/, __graft_entry__.smoke() and
 // bench.py's cpu_baseline leg may load this library; the product path (rust_mdbg_amd/) never does.
 //
-// PARITY STATUS: **parity unpinned** by the reference itself — the reference (Rust) has no tests,
-// no golden outputs, cannot be compiled here (no cargo/rustc), and its ntHash arithmetic lives in
-// the un-vendored third-party crate `nthash` (Cargo.toml:26 `nthash = "*"`, no lockfile; newest
-// release at reference time: 0.5.1).  The oracle is anchored instead on
-//   (1) the nthash crate's published known-answer vectors (tests/test_oracle_kat.py), and
-//   (2) the reference's own call sites, restated line by line below (file:line cited per function), and
-//   (3) for ONE function something the reference itself produced: encode_rle against the outputs of the reference's Python helper
-//       utils/remove_homopoly.py (the same rule and the same literal "ACTGactgNn" as src/read.rs:157-174), run in the build container on 80
-//       committed inputs (tests/golden/make_reference_py_vectors.py -> reference_py_vectors.json; tests/test_oracle_golden.py).  The Rust
-//       path as a whole stays unpinned.
+// PARITY STATUS: pinned in part on the reference's own output.  The reference (Rust) cannot be compiled
+// where this is built (no cargo/rustc) and its ntHash arithmetic lives in the un-vendored third-party
+// crate `nthash` (Cargo.toml:26 `nthash = "*"`, no lockfile; newest release at reference time: 0.5.1),
+// but its tree holds two real `.sequences` lines, quoted as comments (experiments/661k_genomes/
+// scan_genomes_minmers.py and src/to_basespace.rs).  The oracle is anchored on
+//   (1) those two lines (tests/golden/reference_held_vectors.json; tests/test_reference_held_cpu.py): with homopolymer compression off, l = 12 / l = 10
+//       and density 0.01 the oracle selects exactly the 10 / 7 listed hashes, at positions that give the printed shift pair and sequence length, and a read
+//       holding the sequence yields the listed k-min-mer with that span, that shift pair and that orientation, the reverse-complement read included.
+//       PINNED by them: hash_bound (the first line brackets the bound of density 0.01 within 4 %), ntHash seeds / rotations / canonical minimum, the
+//       inclusive density filter and the positions, the window loop's shift pair and `+ l` span, normalize, the `.sequences` line format — for
+//       already-compressed input (oracle/PIN.md says why that setting);
+//   (2) encode_rle, on the outputs of the reference's Python helper utils/remove_homopoly.py (the same rule and the same literal "ACTGactgNn" as
+//       src/read.rs:157-174) for 80 committed inputs (tests/golden/make_reference_py_vectors.py -> reference_py_vectors.json; tests/test_oracle_golden.py);
+//   (3) the nthash crate's published known-answer vectors (tests/test_oracle_kat.py), and
+//   (4) the reference's own call sites, restated line by line below (file:line cited per function), and a second restatement written separately
+//       (tests/golden/independent_restatement.py).
+// NOT pinned on reference output: abundance counting across reads, NODE_INDEX order, the edges, and homopolymer compression TOGETHER with hashing
+// (the recipe of oracle/PIN.md §1-3 stays for those).
 //
 // What is restated (all paths relative to /root/reference):
 //   src/read.rs:157-174      Read::encode_rle          -> orc::encode_rle

@@ -2,9 +2,10 @@
 """A SECOND, independent restatement of rust-mdbg's hot path, written from the reference sources and from the published
 definition of ntHash — it imports nothing from oracle/ and shares no code with it.
 
-Why it exists: the reference cannot be built in this image (Rust, no cargo; the `nthash` crate is not vendored) and it has
-no tests or golden outputs, so nothing produced BY the reference can pin the C++ oracle ("parity unpinned").
-The strongest evidence available is two restatements written separately, in different languages and with different
+Why it exists: the reference cannot be built in this image (Rust, no cargo; the `nthash` crate is not vendored), and what
+it produced itself pins only part of the C++ oracle: two `.sequences` lines (tests/golden/reference_held_vectors.json, which
+this file reproduces too: tests/test_reference_held_cpu.py) and the homopolymer compression.  For the rest the
+strongest evidence available is two restatements written separately, in different languages and with different
 algorithms, that agree bit for bit:
   * oracle/mdbg_oracle.cpp  — C++, rolling ntHash (the crate's iterator recurrences), per-read loops, hash maps;
   * this file               — Python/numpy, the DIRECT (non-rolling) definition of ntHash evaluated position by position

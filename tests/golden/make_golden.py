@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.json|npz from the CPU oracle.
 
-Provenance: the reference (Rust) cannot be built or run in this image, and it has no tests or golden
-outputs of its own, so these fixtures are produced by oracle/mdbg_oracle.cpp (a line-by-line restatement,
-pinned on the nthash crate's known-answer vectors).  The config-1 counts and the node-set SHA-256 were
+Provenance: the reference (Rust) cannot be built or run in this image, so these fixtures are produced by
+oracle/mdbg_oracle.cpp (a line-by-line restatement, pinned on the nthash crate's known-answer vectors and, for
+the sketch and the window loop, on the two .sequences lines the reference tree holds: reference_held_vectors.json,
+which is NOT made by this script).  The config-1 counts and the node-set SHA-256 were
 additionally reproduced by an independent numpy restatement during the survey.
 Run:  python tests/golden/make_golden.py
 """
