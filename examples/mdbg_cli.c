@@ -8,6 +8,8 @@
  *   --read-paths (implies --contigs): the resident reads threaded through the unitig list (mdbg_graph_read_paths, in ranges of 2^20 reads): one summary line
  *   --junctions (implies --contigs): the reads that cross each edge record of the unitig list (mdbg_graph_junctions, in ranges of 2^20 reads, the supports summed):
  *   one summary line
+ *   --transits N (implies --contigs): the reads that span a unitig end to end (mdbg_graph_transits, in ranges of 2^20 reads, the counts merged by key) and whether
+ *   the pairs seen N times or more match a repeat's entrances to its exits: <prefix>.unitigs.transits.tsv (and <prefix>.msimpl.transits.tsv) and one summary line each
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
  *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
@@ -85,11 +87,77 @@ static void die(mdbg_ctx* ctx, const char* what, int rc) {
     exit(1);
 }
 
+/* ---- --transits: the rows of the ranges merged by key, the verdict rule of mdbg_graph_transits on the merged counts, the .transits.tsv ---- */
+typedef struct trow_t { uint32_t u, pu, pj, ps, qu, qj, qs; uint64_t count; } trow_t;
+static int trow_cmp(const void* a, const void* b) {
+    const trow_t* x = (const trow_t*)a; const trow_t* y = (const trow_t*)b;
+    const uint32_t kx[7] = {x->u, x->pu, x->pj, x->ps, x->qu, x->qj, x->qs}, ky[7] = {y->u, y->pu, y->pj, y->ps, y->qu, y->qj, y->qs};
+    for (int i = 0; i < 7; ++i) if (kx[i] != ky[i]) return kx[i] < ky[i] ? -1 : 1;
+    return 0;
+}
+static int u64_cmp(const void* a, const void* b) { const uint64_t x = *(const uint64_t*)a, y = *(const uint64_t*)b; return x < y ? -1 : x > y; }
+static void* must(void* p) { if (!p) { fprintf(stderr, "out of memory\n"); exit(1); } return p; }
+static void write_transits(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* path, uint64_t min_support, const char* label) {
+    static const char* const verdict_name[4] = {"plain", "resolved", "unresolved", "self"};
+    trow_t* rows = NULL; uint64_t n = 0, cap = 0, first = 0, U = 0, n_passes = 0, n_repeats = 0, n_resolved = 0;
+    uint32_t* n_in = NULL; uint32_t* n_out = NULL; uint64_t* passes = NULL;
+    for (;;) {
+        mdbg_transit_list t;
+        const int rc = mdbg_graph_transits(ctx, first, (uint64_t)1 << 20, min_support, &t);
+        if (rc) die(ctx, "mdbg_graph_transits", rc);
+        if (!t.n_reads) break;
+        if (!passes) {                                              /* n_in and n_out depend on the records alone: any range's */
+            U = t.n_unitigs;
+            n_in = (uint32_t*)must(malloc(U * sizeof *n_in)); n_out = (uint32_t*)must(malloc(U * sizeof *n_out)); passes = (uint64_t*)must(calloc(U, sizeof *passes));
+            memcpy(n_in, t.n_in, U * sizeof *n_in); memcpy(n_out, t.n_out, U * sizeof *n_out);
+        }
+        for (uint64_t u = 0; u < U; ++u) passes[u] += t.passes[u];
+        if (n + t.n_transits > cap) { cap = 2 * (n + t.n_transits); rows = (trow_t*)must(realloc(rows, cap * sizeof *rows)); }
+        for (uint64_t i = 0; i < t.n_transits; ++i) {
+            trow_t r; r.u = t.unitig[i]; r.pu = t.in_unitig[i]; r.pj = t.in_entry[i]; r.ps = t.in_strand[i]; r.qu = t.out_unitig[i]; r.qj = t.out_entry[i]; r.qs = t.out_strand[i];
+            r.count = t.count[i];
+            rows[n++] = r;
+        }
+        n_passes += t.n_passes; first += t.n_reads;
+    }
+    if (n) qsort(rows, n, sizeof *rows, trow_cmp);
+    uint64_t m = 0;                                                 /* equal keys of different ranges fall together */
+    for (uint64_t i = 0; i < n; ++i) if (m && !trow_cmp(&rows[m - 1], &rows[i])) rows[m - 1].count += rows[i].count; else rows[m++] = rows[i];
+    uint8_t* self = (uint8_t*)must(calloc(U + 1, 1));
+    for (uint64_t r = 0; r < ul->edges.n && U; ++r) if (ul->edges.n1[r] == ul->edges.n2[r]) self[ul->edges.n1[r]] = 1;
+    uint64_t* qs = (uint64_t*)must(malloc((m + 1) * sizeof *qs));
+    FILE* f = fopen(path, "w");
+    if (!f) { perror(path); exit(1); }
+    for (uint64_t i = 0; i < m; ++i)
+        fprintf(f, "T\tutg%07u%c\t%c\tutg%07u%c\t+\tutg%07u%c\t%c\t%llu\n", rows[i].pu + 1, ul->circular[rows[i].pu] ? 'c' : 'l', rows[i].ps ? '-' : '+', rows[i].u + 1,
+                ul->circular[rows[i].u] ? 'c' : 'l', rows[i].qu + 1, ul->circular[rows[i].qu] ? 'c' : 'l', rows[i].qs ? '-' : '+', (unsigned long long)rows[i].count);
+    uint64_t at = 0;
+    for (uint64_t u = 0; u < U; ++u) {
+        uint64_t strong = 0; int matched = 1; const trow_t* last = NULL;
+        for (; at < m && rows[at].u == u; ++at) {
+            if (rows[at].count < min_support) continue;
+            if (last && last->pu == rows[at].pu && last->pj == rows[at].pj && last->ps == rows[at].ps) matched = 0;      /* (equal p are neighbours in key order) */
+            last = &rows[at];
+            qs[strong++] = (uint64_t)rows[at].qu << 33 | (uint64_t)rows[at].qj << 1 | rows[at].qs;
+        }
+        if (n_in[u] < 2 || n_out[u] < 2) continue;
+        qsort(qs, strong, sizeof *qs, u64_cmp);
+        for (uint64_t i = 1; i < strong; ++i) if (qs[i] == qs[i - 1]) matched = 0;
+        const int v = self[u] ? MDBG_TRANSIT_SELF : n_in[u] == n_out[u] && strong == n_in[u] && matched ? MDBG_TRANSIT_RESOLVED : MDBG_TRANSIT_UNRESOLVED;
+        ++n_repeats; n_resolved += v == MDBG_TRANSIT_RESOLVED;
+        fprintf(f, "U\tutg%07llu%c\t%u\t%u\t%llu\t%s\n", (unsigned long long)u + 1, ul->circular[u] ? 'c' : 'l', n_in[u], n_out[u], (unsigned long long)passes[u], verdict_name[v]);
+    }
+    if (fclose(f)) { perror(path); exit(1); }
+    printf("transits%s: %llu keys, %llu passes, %llu repeats, %llu of them resolved at min_support %llu\n", label, (unsigned long long)m, (unsigned long long)n_passes,
+           (unsigned long long)n_repeats, (unsigned long long)n_resolved, (unsigned long long)min_support);
+    free(rows); free(n_in); free(n_out); free(passes); free(self); free(qs);
+}
+
 int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0; uint64_t transits = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L / -e N append steps of their own, in command-line order */
@@ -147,15 +215,16 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--components")) components = 1;
         else if (!strcmp(argv[i], "--read-paths")) read_paths = 1;
         else if (!strcmp(argv[i], "--junctions")) junctions = 1;
+        else if (!strcmp(argv[i], "--transits") && i + 1 < argc) { transits = strtoull(argv[++i], NULL, 10); if (!transits) { fprintf(stderr, "--transits takes a min_support >= 1\n"); return 2; } }
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [--components] [--read-paths] [--junctions] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
-    if (simplify || components || read_paths || junctions) contigs = 1;
+    if (simplify || components || read_paths || junctions || transits) contigs = 1;
     if (!contigs) keep_reads = 0;
     if (!write_sequences) seq_kept = 0;
     if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
@@ -275,6 +344,7 @@ int main(int argc, char** argv) {
         printf("simplify: %llu unitigs, %llu nodes removed; %llu contigs left\n", (unsigned long long)ss.total_unitigs_removed, (unsigned long long)ss.total_nodes_removed,
                (unsigned long long)sl.n_unitigs);
         if (edge_steps) printf("simplify: %llu edge records removed\n", (unsigned long long)total_edges_removed);
+        if (transits) { snprintf(path, sizeof path, "%s.msimpl.transits.tsv", prefix); write_transits(ctx, &sl, path, transits, " (simplified)"); }
         sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
         if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
         if (keep_reads) {                                           /* the sequences from the device store instead of the second pass */
@@ -337,6 +407,7 @@ int main(int argc, char** argv) {
             printf("junctions: %llu records, %llu crossed by no read, %llu crossings, %llu of them on no record\n", (unsigned long long)records,
                    (unsigned long long)unsupported, (unsigned long long)crossings, (unsigned long long)missing);
         }
+        if (transits) { snprintf(path, sizeof path, "%s.unitigs.transits.tsv", prefix); write_transits(ctx, &ul, path, transits, ""); }
         if (keep_reads) {
             mdbg_contig_seqs cs;
             rc = mdbg_graph_contigs(ctx, 0, &cs);

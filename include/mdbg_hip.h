@@ -617,6 +617,66 @@ int mdbg_graph_junctions(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads,
 int mdbg_graph_junctions_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out);
 int mdbg_junctions_ms(mdbg_ctx* ctx, double* ms);
 
+/* ---- transits: the reads that span a unitig end to end, and the repeats they resolve ------------------------------------------------
+ * A repeat longer than k - 1 minimizers is a unitig of its own with several ways in and several ways out, and every one of its edge records may be well supported:
+ * the junction support cannot say which entrance goes with which exit.  A read that enters the unitig over one record, walks all of it and leaves over another
+ * can.  This call lists, per unitig of the CURRENT list, every (entrance, exit) pair the resident reads take through it, with counts, and says per unitig whether
+ * those pairs match its entrances to its exits one to one.  It works on what mdbg_graph_junctions works on, with the same state requirements, the same range of reads
+ * [first_read, first_read + max_reads) (max_reads = 0: to the end), the same capacity bounds and the same defect flags.  It changes nothing: duplicating a resolved
+ * unitig is a later step's business.  SINGLE GPU ONLY.
+ *
+ * Definition.  Windows, PLACED, vertex (u, j, s), pair, MIRROR, KEY, LINK, CROSSING, the key of an edge record and m(u) are those of mdbg_graph_junctions.  A crossing
+ * is EXPLAINED iff its key is some record's key.
+ *   A TRANSIT is two explained crossings of one read, c = x -> y at windows (w, w + 1) and c' = x' -> y' at windows (w', w' + 1) with w < w', such that every window
+ *   w + 1 .. w' is placed and every adjacent pair strictly between the two crossings is a link (w' = w + 1: y and x' are the same window).  An unplaced window, a
+ *   crossing whose key is no record's key, or the end of the read ends the chain.  Consecutive explained crossings overlap: a read with crossings c1, c2, c3 in an
+ *   unbroken chain gives the transits (c1, c2) and (c2, c3).
+ *   Consequence: y and x' lie on one unitig u with one strand s, y on the end the read enters by and x' on the end it leaves by, and w' - w == m(u): the read walks
+ *   all of u.  (A record's pair ends on an end of its unitig and links never wrap.  The device checks it on every transit; a chain that breaks it is a defect.)
+ *   CANONICAL FORM: if s == 1, (c, c') is replaced by (mirror(c'), mirror(c)), the same walk read from the other strand.  The in-pair is then p -> (u, 0, 0) and
+ *   the out-pair (u, m(u) - 1, 0) -> q.  The TRANSIT KEY is (u, p, q), ordered by u, then p, then q in the junctions' vertex order; reads of both strands fall together.
+ *   Per distinct key, in key order, n_transits rows: unitig[] = u; in_unitig[], in_entry[], in_strand[] = p; out_unitig[], out_entry[], out_strand[] = q;
+ *   in_record[] / out_record[] = the smallest record number whose key is the key of the in-pair / of the out-pair; count[] = the transits of the range with that key.
+ *   Per unitig u of the list, n_unitigs entries: n_in[u] = the distinct keys among the records' pairs and their mirrors whose pair has target (u, 0, 0);
+ *   n_out[u] likewise for source (u, m(u) - 1, 0); passes[u] = the sum of count[] over u's keys; verdict[u] for the call's min_support >= 1, the first test that applies:
+ *     MDBG_TRANSIT_PLAIN       n_in < 2 or n_out < 2;
+ *     MDBG_TRANSIT_SELF        some record has n1 == n2 == u;
+ *     MDBG_TRANSIT_RESOLVED    n_in == n_out, n_in equals the number of u's keys with count >= min_support (the STRONG ones), and the strong keys have pairwise different
+ *                              p and pairwise different q: a perfect matching of entrances and exits.  Weak keys do not block, as weak records do not in an EDGES step;
+ *     MDBG_TRANSIT_UNRESOLVED  otherwise.
+ *   n_crossings and n_explained are the junctions'; n_passes is the sum of count[]; n_transits the number of distinct keys; n_repeats the unitigs with n_in >= 2 and
+ *   n_out >= 2; n_resolved the RESOLVED ones.  n_in, n_out and the SELF test depend on the records alone, not on the range.
+ *   Everything is an integer sum or a position of a sort or a scan: two calls give identical arrays, nothing depends on scheduling.
+ * Invariants: the sum of passes[] is n_passes; passes[u] <= support_steps[u] of the read paths of the same range for every LINEAR unitig (a transit's walk is a
+ * step of its own; on a circular unitig one step that wraps r times holds r - 1 transits, so the bound does not hold there);
+ * count[i] <= min(support[in_record[i]], support[out_record[i]]) of the junctions of the same range, with the support of a pair that is its OWN MIRROR taken
+ * twice (one such crossing closes a transit of strand 0 and opens one of strand 1 that fall on one key; no other crossing serves a key twice).
+ * Ranges: over the ranges of a partition of the reads the rows merge by key (counts added) into the whole call's, passes[] add up, and n_reads, n_crossings,
+ * n_explained and n_passes add up.  Verdicts, n_repeats and n_resolved belong to the range they were computed on; apply the rule to the merged counts for the whole.
+ * The temporaries are 35 bytes per minimizer index of the range (the place codes 4, the kind of each pair 1, the transit keys 12 and their second copy 12, head
+ * flags 1, positions 4, direction bits 1) beside the sorts' own, and the row columns are sized for their worst case, another 38 bytes per index, because their number
+ * is known only on the device: the range bounds both.  Per edge record the call takes 40 bytes of temporaries, per unitig 6 bytes of temporaries and 17 of result.
+ * mdbg_graph_transits: HOST arrays; mdbg_graph_transits_device: DEVICE arrays.  They belong to the context until its next transit call or mdbg_destroy and share memory
+ * with no other result: a read-path, junction, component or contig result the caller holds is untouched by the call, and a transit result survives a junction call
+ * and a simplify call.  The number of kernel launches is fixed; the device variant waits for the device ONCE (all counts and the defect flag in one read-back) when
+ * the range starts and ends where batches do, otherwise once more, up front, for the range's two offsets.
+ * mdbg_transits_ms: device time of the last transit call (HIP events; 0 if it launched nothing).
+ * MDBG_E_PARAM: min_support == 0 or a null pointer; MDBG_E_STATE, MDBG_E_CAPACITY: as mdbg_graph_junctions; MDBG_E_DEVICE: its defect flags, or a chain of two
+ * explained crossings that does not walk all of one unitig.  An empty context, an empty list or first_read >= the number of reads gives MDBG_OK with every count zero
+ * (n_unitigs included) and no arrays. */
+enum { MDBG_TRANSIT_PLAIN = 0, MDBG_TRANSIT_RESOLVED = 1, MDBG_TRANSIT_UNRESOLVED = 2, MDBG_TRANSIT_SELF = 3 };
+typedef struct mdbg_transit_list {
+    uint64_t first_read, n_reads, n_crossings, n_explained, n_passes, n_transits, n_unitigs, n_repeats, n_resolved;
+    const uint32_t* unitig;                                                                          /* n_transits */
+    const uint32_t* in_unitig; const uint32_t* in_entry; const uint8_t* in_strand;                   /* n_transits */
+    const uint32_t* out_unitig; const uint32_t* out_entry; const uint8_t* out_strand;                /* n_transits */
+    const uint32_t* in_record; const uint32_t* out_record; const uint64_t* count;                    /* n_transits */
+    const uint32_t* n_in; const uint32_t* n_out; const uint64_t* passes; const uint8_t* verdict;     /* n_unitigs */
+} mdbg_transit_list;
+int mdbg_graph_transits(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out);
+int mdbg_graph_transits_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out);
+int mdbg_transits_ms(mdbg_ctx* ctx, double* ms);
+
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),
  * so the ranks may exchange SKETCHES instead (one all-gather), each rank then windows the global sketch but inserts only

@@ -170,6 +170,95 @@ def merge_junctions(parts):
     return out
 
 
+class TransitList(C.Structure):        # mdbg_transit_list
+    _fields_ = [("first_read", C.c_uint64), ("n_reads", C.c_uint64), ("n_crossings", C.c_uint64), ("n_explained", C.c_uint64), ("n_passes", C.c_uint64),
+                ("n_transits", C.c_uint64), ("n_unitigs", C.c_uint64), ("n_repeats", C.c_uint64), ("n_resolved", C.c_uint64),
+                ("unitig", C.POINTER(C.c_uint32)), ("in_unitig", C.POINTER(C.c_uint32)), ("in_entry", C.POINTER(C.c_uint32)), ("in_strand", C.POINTER(C.c_uint8)),
+                ("out_unitig", C.POINTER(C.c_uint32)), ("out_entry", C.POINTER(C.c_uint32)), ("out_strand", C.POINTER(C.c_uint8)),
+                ("in_record", C.POINTER(C.c_uint32)), ("out_record", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint64)),
+                ("n_in", C.POINTER(C.c_uint32)), ("n_out", C.POINTER(C.c_uint32)), ("passes", C.POINTER(C.c_uint64)), ("verdict", C.POINTER(C.c_uint8))]
+
+
+# (field, dtype, what it has one element of: "transit" or "unitig")
+TRANSIT_FIELDS = (("unitig", np.uint32, "transit"), ("in_unitig", np.uint32, "transit"), ("in_entry", np.uint32, "transit"), ("in_strand", np.uint8, "transit"),
+                  ("out_unitig", np.uint32, "transit"), ("out_entry", np.uint32, "transit"), ("out_strand", np.uint8, "transit"), ("in_record", np.uint32, "transit"),
+                  ("out_record", np.uint32, "transit"), ("count", np.uint64, "transit"),
+                  ("n_in", np.uint32, "unitig"), ("n_out", np.uint32, "unitig"), ("passes", np.uint64, "unitig"), ("verdict", np.uint8, "unitig"))
+TRANSIT_COUNTS = ("n_reads", "n_crossings", "n_explained", "n_passes")      # what adds up over the ranges of a partition of the reads
+TRANSIT_COLUMNS = tuple(f for f, _, per in TRANSIT_FIELDS if per == "transit")
+TRANSIT_PLAIN, TRANSIT_RESOLVED, TRANSIT_UNRESOLVED, TRANSIT_SELF = 0, 1, 2, 3      # MDBG_TRANSIT_*
+TRANSIT_VERDICT_NAMES = ("plain", "resolved", "unresolved", "self")
+
+
+def transit_verdicts(n_in, n_out, self_flags, merged, min_support):
+    """the verdict rule of mdbg_graph_transits on the host, for counts merged over ranges: n_in, n_out per unitig (any range's: they depend on the records alone),
+    self_flags per unitig (some record has n1 == n2 == u), merged: a dict with the row columns (a graph_transits() result or merge_transits' of several)
+    -> verdict u8[n_unitigs]"""
+    assert min_support >= 1
+    strong = {}
+    for u, pu, pj, ps, qu, qj, qs, n in zip(*(np.asarray(merged[f]).tolist() for f in TRANSIT_COLUMNS[:7] + ("count",))):
+        if n >= min_support:
+            strong.setdefault(u, []).append(((pu, pj, ps), (qu, qj, qs)))
+    out = np.zeros(len(n_in), np.uint8)
+    for u, (ni, no, own) in enumerate(zip(np.asarray(n_in).tolist(), np.asarray(n_out).tolist(), np.asarray(self_flags).tolist())):
+        if ni < 2 or no < 2:
+            continue
+        s = strong.get(u, [])
+        matched = ni == no == len(s) and len({p for p, _ in s}) == len(s) and len({q for _, q in s}) == len(s)
+        out[u] = TRANSIT_SELF if own else TRANSIT_RESOLVED if matched else TRANSIT_UNRESOLVED
+    return out
+
+
+def transit_self_flags(edges, n_unitigs):
+    """per unitig: 1 iff some record of the list's `edges` has n1 == n2 == u"""
+    n1, n2 = np.asarray(edges["n1"]), np.asarray(edges["n2"])
+    out = np.zeros(n_unitigs, np.uint8)
+    out[n1[n1 == n2]] = 1
+    return out
+
+
+def merge_transits(parts, self_flags=None, min_support=1):
+    """the graph_transits() results of the ranges of a partition of the reads -> the whole call's: the rows merge by key (counts added, key order kept), passes and
+    the counts that are sums add up.  Verdicts belong to their range: with self_flags (transit_self_flags of the list's edges) they are computed again on the merged
+    counts by transit_verdicts, and n_repeats / n_resolved with them; without, the result carries no verdict."""
+    parts = list(parts)
+    out = {f: sum(p[f] for p in parts) for f in TRANSIT_COUNTS}
+    with_unitigs = [p for p in parts if p["n_unitigs"]]           # (a range behind the store, an empty list: no arrays)
+    U = with_unitigs[0]["n_unitigs"] if with_unitigs else 0
+    by_key = {}
+    for p in parts:
+        for row in zip(*(p[f].tolist() for f in TRANSIT_COLUMNS)):
+            at = by_key.setdefault(row[:7], [row[7], row[8], 0])   # (the two records follow from the key)
+            at[2] += row[9]
+    rows = [key + tuple(by_key[key]) for key in sorted(by_key)]   # (tuples of the seven columns compare as keys do)
+    for i, (f, t, _) in enumerate(TRANSIT_FIELDS[:10]):
+        out[f] = np.array([r[i] for r in rows], dtype=t)
+    out["n_in"] = with_unitigs[0]["n_in"].copy() if with_unitigs else np.zeros(0, np.uint32)
+    out["n_out"] = with_unitigs[0]["n_out"].copy() if with_unitigs else np.zeros(0, np.uint32)
+    out["passes"] = sum((p["passes"] for p in with_unitigs), np.zeros(U, np.uint64))
+    out.update(first_read=parts[0]["first_read"] if parts else 0, n_transits=len(rows), n_unitigs=U)
+    if self_flags is not None:
+        out["verdict"] = transit_verdicts(out["n_in"], out["n_out"], self_flags, out, min_support)
+        repeat = (out["n_in"] >= 2) & (out["n_out"] >= 2)
+        out.update(n_repeats=int(repeat.sum()), n_resolved=int((out["verdict"] == TRANSIT_RESOLVED).sum()))
+    return out
+
+
+def transit_text(t, circular):
+    """the lines of a .transits.tsv: first one per transit key in key order, `T<TAB>utgA<TAB>+|-<TAB>utgU<TAB>+<TAB>utgB<TAB>+|-<TAB>count` — reads enter unitig U from
+    A and leave it for B count times; the signs of A and B are the strands of p and q (`+` = strand 0), so the line reads as the two L lines `A oA U +` and
+    `U + B oB` —, then one per unitig with n_in >= 2 and n_out >= 2 in unitig order, `U<TAB>utgU<TAB>n_in<TAB>n_out<TAB>passes<TAB>plain|resolved|unresolved|self`.
+    t: a graph_transits() result or merge_transits' with verdicts; circular: the list's `circular` array."""
+    name = lambda u: unitig_name(u, circular[u])
+    sign = lambda s: "-" if s else "+"
+    cols = [np.asarray(t[f]).tolist() for f in ("unitig", "in_unitig", "in_strand", "out_unitig", "out_strand", "count")]
+    lines = ["T\t%s\t%s\t%s\t+\t%s\t%s\t%d\n" % (name(a), sign(sa), name(u), name(b), sign(sb), n) for u, a, sa, b, sb, n in zip(*cols)]
+    for u, (ni, no, n, v) in enumerate(zip(*(np.asarray(t[f]).tolist() for f in ("n_in", "n_out", "passes", "verdict")))):
+        if ni >= 2 and no >= 2:
+            lines.append("U\t%s\t%d\t%d\t%d\t%s\n" % (name(u), ni, no, n, TRANSIT_VERDICT_NAMES[v]))
+    return "".join(lines)
+
+
 class ContigSeqs(C.Structure):         # mdbg_contig_seqs
     _fields_ = [("n_contigs", C.c_uint64), ("n_bases", C.c_uint64), ("bases", C.POINTER(C.c_uint8)), ("offsets", C.POINTER(C.c_uint64)),
                 ("unitig", C.POINTER(C.c_uint64))]
@@ -229,7 +318,7 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_set_partition", "mdbg_sketch_view", "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end",
            "mdbg_store_reserve", "mdbg_sketch_reserve", "mdbg_sketch_commit", "mdbg_last_batch", "mdbg_owner_counts", "mdbg_graph_edges", "mdbg_graph_edges_device", "mdbg_graph_unitigs", "mdbg_graph_unitigs_device",
            "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_simplify_edges_removed", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
-           "mdbg_graph_junctions", "mdbg_graph_junctions_device", "mdbg_junctions_ms",
+           "mdbg_graph_junctions", "mdbg_graph_junctions_device", "mdbg_junctions_ms", "mdbg_graph_transits", "mdbg_graph_transits_device", "mdbg_transits_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
            "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
 
@@ -336,6 +425,9 @@ def load_library():
     L.mdbg_graph_junctions.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
     L.mdbg_graph_junctions_device.argtypes = [vp, u64, u64, C.POINTER(JunctionList)]
     L.mdbg_junctions_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mdbg_graph_transits.argtypes = [vp, u64, u64, u64, C.POINTER(TransitList)]
+    L.mdbg_graph_transits_device.argtypes = [vp, u64, u64, u64, C.POINTER(TransitList)]
+    L.mdbg_transits_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.mdbg_finalize_begin.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_finalize_end.argtypes = [vp, C.POINTER(Nodes), C.POINTER(vp), C.POINTER(u64)]
     L.mdbg_insert_records.argtypes = [vp, vp, u64]
@@ -704,6 +796,31 @@ class Mdbg:
         """device time of the last graph_junctions* call, in milliseconds"""
         ms = C.c_double()
         self._chk(self.L.mdbg_junctions_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def graph_transits(self, first_read=0, max_reads=0, min_support=1):
+        """the reads that span a unitig of the current list end to end, found on the GPU over the resident reads [first_read, first_read + max_reads) (0: to the end):
+        per (entrance, exit) pair the reads take through a unitig its count, and per unitig whether the pairs seen min_support times or more match its entrances to
+        its exits one to one (mdbg_graph_transits, include/mdbg_hip.h).  Leaves the list and every other result as they are.
+        -> dict(first_read, n_reads, n_crossings, n_explained, n_passes, n_transits, n_unitigs, n_repeats, n_resolved; per transit key unitig, in_unitig, in_entry,
+        in_strand, out_unitig, out_entry, out_strand, in_record, out_record, count; per unitig n_in, n_out, passes, verdict)"""
+        tl = TransitList()
+        self._chk(self.L.mdbg_graph_transits(self.h, first_read, max_reads, min_support, C.byref(tl)))
+        n = dict(transit=int(tl.n_transits), unitig=int(tl.n_unitigs))
+        out = {f: _np(getattr(tl, f), n[per], t) for f, t, per in TRANSIT_FIELDS}
+        out.update({f: int(getattr(tl, f)) for f in TRANSIT_COUNTS + ("n_repeats", "n_resolved")}, first_read=int(tl.first_read), n_transits=n["transit"], n_unitigs=n["unitig"])
+        return out
+
+    def graph_transits_device(self, first_read=0, max_reads=0, min_support=1):
+        """-> TransitList with DEVICE pointers (valid until the next transit call)"""
+        tl = TransitList()
+        self._chk(self.L.mdbg_graph_transits_device(self.h, first_read, max_reads, min_support, C.byref(tl)))
+        return tl
+
+    def transits_ms(self):
+        """device time of the last graph_transits* call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_transits_ms(self.h, C.byref(ms)))
         return float(ms.value)
 
     def kept_reads(self):

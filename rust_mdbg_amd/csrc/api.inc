@@ -22,6 +22,7 @@
 #include "node_seqs.h"
 #include "read_paths.h"
 #include "junctions.h"
+#include "transits.h"
 
 #include "blocks.inc"
 #include "results.inc"      // the derived graph results and which of them are current
@@ -30,7 +31,7 @@
 #include "ingest_api.inc"
 extern "C" {                   // entry points and their static helpers only from here on
 #include "finalize_api.inc"
-#include "graph_api.inc"      // edges, unitigs, simplification, contigs, node sequences, read paths, junction support
+#include "graph_api.inc"      // edges, unitigs, simplification, contigs, node sequences, read paths, junction support, transits
 #include "import_api.inc"
 }
 #include "route_api.inc"      // multi-GPU routing

@@ -396,3 +396,53 @@ static int junctions_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, 
 int mdbg_graph_junctions(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out) { return junctions_impl(c, first_read, max_reads, out, true); }
 int mdbg_graph_junctions_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out) { return junctions_impl(c, first_read, max_reads, out, false); }
 int mdbg_junctions_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.junctions.ms : nullptr, ms); }
+
+// ---- reads that span a unitig end to end, and the repeats they resolve (place_windows.hip, transits.hip) ------
+static int transits_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out, bool to_host) {
+    MDBG_ENTER(c, out);
+    if (min_support == 0) return fail(c, MDBG_E_PARAM, "min_support must be >= 1");
+    memset(out, 0, sizeof *out);
+    out->first_read = first_read;
+    Results& R = c->res;
+    auto& T = R.transits;
+    T.ms = 0;
+    ReadPathRange rg; FinArgs F; bool empty;
+    const int e = placement_range(c, "transits are", first_read, max_reads, &rg, &F, &empty);
+    if (e || empty) return e;
+    const UnitigResult& ul = R.unitigs.last;
+    if (ul.edges.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
+    hipStream_t s = c->stream;
+    ReadPathPlan plan;
+    hipError_t he = transits_begin(T.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
+    if (he != hipSuccess) return fail_hip(c, "transits_begin", he);
+    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
+    TransitResult r;
+    he = transits_end(T.buf.get(), ul, rg, min_support, s, &r);
+    if (he != hipSuccess) return fail_hip(c, "transits_end", he);
+    T.ms = r.ms;
+    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
+    if (r.defect & TX_DEFECT_SHAPE) return fail(c, MDBG_E_DEVICE, "two explained crossings in a row do not walk all of one unitig: the edge records are not those of the unitig list");
+    if (r.defect) return placement_defect(c, r.defect);
+    const u64 nt = r.n_transits, U = r.n_unitigs;
+    out->n_reads = r.n_reads; out->n_crossings = r.n_crossings; out->n_explained = r.n_explained; out->n_passes = r.n_passes; out->n_transits = nt;
+    out->n_unitigs = U; out->n_repeats = r.n_repeats; out->n_resolved = r.n_resolved;
+    HandOver ho{c, "host copy of the transits", to_host};
+    ho.col(r.unitig, nt, T.unitig, &out->unitig);
+    ho.col(r.in_unitig, nt, T.iu, &out->in_unitig);
+    ho.col(r.in_entry, nt, T.ie, &out->in_entry);
+    ho.col(r.in_strand, nt, T.is, &out->in_strand);
+    ho.col(r.out_unitig, nt, T.ou, &out->out_unitig);
+    ho.col(r.out_entry, nt, T.oe, &out->out_entry);
+    ho.col(r.out_strand, nt, T.os, &out->out_strand);
+    ho.col(r.in_record, nt, T.irec, &out->in_record);
+    ho.col(r.out_record, nt, T.orec, &out->out_record);
+    ho.col(r.count, nt, T.count, &out->count);
+    ho.col(r.n_in, U, T.n_in, &out->n_in);
+    ho.col(r.n_out, U, T.n_out, &out->n_out);
+    ho.col(r.passes, U, T.passes, &out->passes);
+    ho.col(r.verdict, U, T.verdict, &out->verdict);
+    return ho.err;
+}
+int mdbg_graph_transits(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out) { return transits_impl(c, first_read, max_reads, min_support, out, true); }
+int mdbg_graph_transits_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out) { return transits_impl(c, first_read, max_reads, min_support, out, false); }
+int mdbg_transits_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.transits.ms : nullptr, ms); }

@@ -3,12 +3,12 @@
 // records, the store's read offsets and minimizer -> read map, and the per-index place codes of the read paths (read_paths.h: placement_begin builds the row ->
 // entry map, place_windows_kernel writes code[t] = global entry | strand << 31 or NONE), kept in buffers of this stage.
 //
-// A vertex (u, j, s) is the number v = 2 * (offsets[u] + j) + s < 2^31; a pair x -> y is the u64 vx << 32 | vy, its mirror (vy ^ 1) << 32 | (vx ^ 1), its KEY the
-// smaller of the two: the order of the packed keys is the definition's order of keys.
+// Vertices, pairs and keys are packed as record_keys.h says, which also holds record_key_kernel (shared with transits.hip): the order of the packed keys is the
+// definition's order of keys.
 //
 //   (memset)            the counters, the map, the counter slots <- 0
 //   entry_kernel        (read_paths.hip) the row -> entry map, unitig_of_entry
-//   record_key_kernel   one thread per edge record r: rkey[r] = the record's key, rec[r] = r.  A record that names a unitig outside the list sets JX_DEFECT_EDGE
+//   record_key_kernel   (record_keys.h) one thread per edge record r: rkey[r] = the record's key, rec[r] = r.  A record that names a unitig outside the list sets JX_DEFECT_EDGE
 //   (rocPRIM)           sort_pairs(rkey, rec): equal keys are one run, the run's first position is the key's counter slot
 //   place_windows_kernel  (place_windows.hip) code[]
 //   cross_kernel        one thread per minimizer index t of the range: code[t - 1] -> code[t], both placed and in one read, is a link or a crossing; a crossing's
@@ -26,6 +26,7 @@
 
 #include "junctions.h"
 #include "graph_common.h"
+#include "record_keys.h"
 
 struct JunctionBuffers {
     Buf entry_of_row, unitig_of_entry, code, counters, tmp;
@@ -38,8 +39,6 @@ struct JunctionBuffers {
 
 namespace {
 
-constexpr u64 JX_NO_KEY = ~0ull;       // (a key is below 2^63)
-
 struct JxArgs {
     u64 U, N, R; const u64* offsets; const u32* unitig_of_entry;
     const u32* n1; const u8* o1; const u32* n2; const u8* o2;
@@ -48,34 +47,6 @@ struct JxArgs {
     const u32* code; u64* mkey; const u64* mkey_sorted; u8* flag; const u32* pos; u64* counters;
     u64* support; u32* mu1; u32* me1; u8* ms1; u32* mu2; u32* me2; u8* ms2; u64* mcount;
 };
-
-__device__ inline u64 key_of_pair(u32 vx, u32 vy) {
-    const u64 a = (u64)vx << 32 | vy, b = (u64)(vy ^ 1u) << 32 | (vx ^ 1u);
-    return a < b ? a : b;
-}
-__device__ inline u32 vertex_of_code(u32 c) { return (c & ~RP_STRAND) << 1 | c >> 31; }
-// the first position in sorted[0, n) whose key is >= key
-__device__ inline u64 lower_bound(const u64* sorted, u64 n, u64 key) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (sorted[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void record_key_kernel(JxArgs a) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.R) return;
-    const u32 n1 = a.n1[r], n2 = a.n2[r];
-    a.rec[r] = (u32)r;
-    if (n1 >= a.U || n2 >= a.U) {
-        atomicOr((unsigned long long*)(a.counters + RP_C_DEFECT), (unsigned long long)JX_DEFECT_EDGE);
-        a.rkey[r] = JX_NO_KEY;
-        return;
-    }
-    const bool m1 = a.o1[r] == '-', m2 = a.o2[r] == '-';
-    const u64 e1 = m1 ? a.offsets[n1] : a.offsets[n1 + 1] - 1;      // the record leaves n1 at its last entry ('+') or, walked backwards, at its first
-    const u64 e2 = m2 ? a.offsets[n2 + 1] - 1 : a.offsets[n2];      // and enters n2 at its first entry ('+') or its last
-    a.rkey[r] = key_of_pair((u32)(e1 << 1) | (u32)m1, (u32)(e2 << 1) | (u32)m2);
-}
 
 __global__ __launch_bounds__(256) void cross_kernel(JxArgs a) {
     __shared__ u32 wsum[4][4];
@@ -186,7 +157,8 @@ hipError_t junctions_begin(JunctionBuffers* B, const UnitigResult& ul, const u32
     if (R) {
         const JxArgs a = args_of(B, ul, rg);
         GHIP(hipMemsetAsync(B->slot.p, 0, R * 8, s));
-        hipLaunchKernelGGL(record_key_kernel, dim3(grid_for(R)), dim3(256), 0, s, a);
+        const RecordKeyArgs rk{a.U, a.R, a.offsets, a.n1, a.o1, a.n2, a.o2, a.rkey, a.rec, a.counters + RP_C_DEFECT, JX_DEFECT_EDGE};
+        hipLaunchKernelGGL(record_key_kernel, dim3(grid_for(R)), dim3(256), 0, s, rk);
         GHIP(hipGetLastError());
         GHIP(sort_pairs(B->tmp, (const u64*)a.rkey, B->rkey_sorted.as<u64>(), (const u32*)a.rec, B->rec_sorted.as<u32>(), (size_t)R, 0u, 64u, s));
     }

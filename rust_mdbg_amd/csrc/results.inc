@@ -1,5 +1,5 @@
 // results.inc — what a context derives from its table and keeps for the caller (the host copy of the node table, the edge list, the unitig list, components, contigs,
-// node sequences, read paths, junction support) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
+// node sequences, read paths, junction support, transits) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
 namespace {
 // the buffers of one graph stage: created on first use, destroyed with the context
 template <class B, B* (*Create)(), void (*Destroy)(B*)> struct StageBuffers {
@@ -32,6 +32,8 @@ struct Results {
              HostRaw<u64> ord, off, supw, sups; HostRaw<u32> rw, fw, nw, unitig, fe; HostRaw<u8> strand; double ms = 0; } rpaths;
     struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call or simplify call with an EDGES step
              HostRaw<u64> support, count; HostRaw<u32> u1, e1, u2, e2; HostRaw<u8> s1, s2; double ms = 0; } junctions;
+    struct { StageBuffers<TransitBuffers, transit_buffers_create, transit_buffers_destroy> buf;                          // its result lives until the next transit call
+             HostRaw<u64> count, passes; HostRaw<u32> unitig, iu, ie, ou, oe, irec, orec, n_in, n_out; HostRaw<u8> is, os, verdict; double ms = 0; } transits;
 
     // ---- what is current.  ONLY the functions from here to prefix_is_summed write these members; everybody else asks the predicates below.
     struct { NodeTable table = NodeTable::NONE; u64 rows = 0;

@@ -7,10 +7,10 @@ import queue
 import threading
 import time
 
-from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, edge_columns, junction_text, merge_junctions, read_path_text, unitig_name
+from .api import MAGIC_SIMPLIFY_STEPS, Mdbg, edge_columns, junction_text, merge_junctions, merge_transits, read_path_text, transit_self_flags, transit_text, unitig_name
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
-READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions call of run_file
+READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions / graph_transits call of run_file
 
 
 def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max):
@@ -23,7 +23,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False, transits=0):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -41,6 +41,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     appended, then one X line per place where reads cross and no record exists (Mdbg.graph_junctions; api.junction_text gives the format), and with simplify
     <prefix>.msimpl.junctions.tsv for the simplified list.  Adds n_junction_records, n_junction_records_unsupported, n_crossings and n_missing_crossings (and
     their _simplified twins).  The other files are unchanged.
+    transits=N >= 1 (with contigs): also write <prefix>.unitigs.transits.tsv: one T line per (entrance, exit) pair the reads take through a unitig from end to
+    end, with its count, then one U line per unitig with two or more entrances and exits saying whether the pairs seen N times or more match them one to one
+    (Mdbg.graph_transits; api.transit_text gives the format), and with simplify <prefix>.msimpl.transits.tsv for the simplified list.  Adds n_transits, n_passes,
+    n_repeats and n_resolved (and their _simplified twins).  The other files are unchanged.
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -185,6 +189,18 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     f.write(junction_text(edge_columns(ul.edges), jx["support"], jx, ul.circular))
                 comp.update({"n_junction_records" + suffix: jx["n_records"], "n_junction_records_unsupported" + suffix: int((jx["support"] == 0).sum()),
                              "n_crossings" + suffix: jx["n_crossings"], "n_missing_crossings" + suffix: jx["n_missing_crossings"]})
+            def write_transits(ul, path_, suffix):       # the same ranges; counts merged by key, the verdicts from the merged counts
+                parts, first = [], 0
+                while True:
+                    tr = m.graph_transits(first, READ_PATH_CHUNK, transits)
+                    if not tr["n_reads"]:
+                        break
+                    parts.append(tr)
+                    first += tr["n_reads"]
+                tr = merge_transits(parts, transit_self_flags(edge_columns(ul.edges), int(ul.n_unitigs)) if parts else [], transits)
+                with open(path_, "w") as f:
+                    f.write(transit_text(tr, ul.circular))
+                comp.update({f + suffix: tr[f] for f in ("n_transits", "n_passes", "n_repeats", "n_resolved")})
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
@@ -194,6 +210,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_read_paths(sl, prefix + ".msimpl.read_paths.tsv", "n_read_steps_simplified")
                 if junctions:
                     write_junctions(sl, prefix + ".msimpl.junctions.tsv", "_simplified")
+                if transits:
+                    write_transits(sl, prefix + ".msimpl.transits.tsv", "_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
@@ -207,6 +225,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_read_paths(ul, prefix + ".unitigs.read_paths.tsv", "n_read_steps")
                 if junctions:
                     write_junctions(ul, prefix + ".unitigs.junctions.tsv", "")
+                if transits:
+                    write_transits(ul, prefix + ".unitigs.transits.tsv", "")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
