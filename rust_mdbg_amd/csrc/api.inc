@@ -20,6 +20,7 @@
 #include "components.h"
 #include "contigs.h"
 #include "node_seqs.h"
+#include "placement.h"
 #include "read_paths.h"
 #include "junctions.h"
 #include "transits.h"

@@ -1,6 +1,7 @@
 // graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip, bubble and small-component
-// removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip), read paths (read_paths.hip) and
-// read support per junction (junctions.hip).
+// removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip), and the stages that
+// decide with the resident reads: read paths (read_paths.hip), read support per junction (junctions.hip) and transits (transits.hip), each ONE call over the
+// context's one placement scratch (placement.hip, c->res.placement) and the one window placer below.
 // Host code; included by api.inc, whose context, fail(), MDBG_ENTER and HandOver it uses; what is current is asked of c->res (results.inc).
 
 // ---- the refusals the stages share -------------------------------------------------------------------------
@@ -25,6 +26,71 @@ static int last_ms(mdbg_ctx* c, const double* of_stage, double* ms) {
 // the five arrays of an edge list: the edge stage's own, and the unitig list's
 static void hand_over_edges(HandOver& ho, const EdgeResult& r, EdgeColumns& h, mdbg_edge_list* out) {
     ho.col(r.n1, r.n, h.n1, &out->n1); ho.col(r.o1, r.n, h.o1, &out->o1); ho.col(r.n2, r.n, h.n2, &out->n2); ho.col(r.o2, r.n, h.o2, &out->o2); ho.col(r.overlap, r.n, h.ov, &out->overlap);
+}
+
+// ---- what the stages that decide with the resident reads share (read paths, junction support, transits, an EDGES step) ----
+// roff[r] where the host knows it without asking the device: r is the first slot of a batch, or one past its last
+static bool known_read_offset(const mdbg_ctx* c, u64 r, u64* v) {
+    for (const Batch& b : c->batches) {
+        if (b.slot0 == r) { *v = b.m0; return true; }
+        if ((u64)b.slot0 + b.n_reads == r) { *v = b.m1; return true; }
+    }
+    return false;
+}
+// The window placer, the ONE way a stage reaches place_windows_kernel (main translation unit, beside the table): the range of reads with its minimizer indices and
+// the store's arrays, as store_range fills them, and the launch placement_queue asks for.
+struct PlaceWindows { mdbg_ctx* c; FinArgs F; ReadPathRange rg; };
+static void place_windows(void* ctx, const ReadPathPlan& plan, hipStream_t s) {
+    const PlaceWindows& p = *(const PlaceWindows*)ctx;
+    launch_place_windows(table_args(p.c), p.F, p.c->fin_words, plan, p.F.mh, p.F.mread, p.F.roff, p.rg.i0, p.rg.i1, s);
+}
+// What a stage asks of the store before it places a window, for a list of n_unitigs unitigs and n_entries entries: the bounds, the range of reads with its minimizer
+// indices, the store's arrays.  *empty <- the call answers MDBG_OK with zero counts (an empty context, an empty list, a range behind the store).  An EDGES step of a
+// simplify schedule (unitigs_impl) asks it for the lists it is going to build, which have at most as many entries as the table has rows.
+static int store_range(mdbg_ctx* c, uint64_t n_unitigs, uint64_t n_entries, uint64_t first_read, uint64_t max_reads, PlaceWindows* pw, bool* empty) {
+    *empty = true;
+    Results& R = c->res;
+    if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
+    if (n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;
+    if (n_entries >= (1ull << 30) || R.n_rows() >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
+    hipStream_t s = c->stream;
+    const u64 r0 = first_read, r1 = max_reads && max_reads < c->n_slots - r0 ? r0 + max_reads : c->n_slots;
+    ReadPathRange rg{};
+    const bool known0 = known_read_offset(c, r0, &rg.i0), known1 = known_read_offset(c, r1, &rg.i1);
+    if (!known0) HIPCHK(c, hipMemcpyAsync(&rg.i0, c->roff.as<u64>() + r0, 8, hipMemcpyDeviceToHost, s));
+    if (!known1) HIPCHK(c, hipMemcpyAsync(&rg.i1, c->roff.as<u64>() + r1, 8, hipMemcpyDeviceToHost, s));
+    if (!(known0 && known1)) HIPCHK(c, hipStreamSynchronize(s));      // (a range that starts or ends inside a batch: one more wait, for its two offsets)
+    if (rg.i1 < rg.i0 || rg.i1 > c->M) return fail(c, MDBG_E_DEVICE, "the read offsets of the store are not ascending");
+    if (rg.i1 - rg.i0 >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 minimizers in the range of reads");
+    for (Batch& b : c->batches) fill_mread_of(c, b);
+    FinArgs F = c->finF;
+    F.mh = c->mh.as<u64>(); F.roff = c->roff.as<u64>(); F.mread = c->mread.as<u32>();
+    rg.roff = F.roff; rg.mread = F.mread; rg.first_read = (u32)r0; rg.n_reads = (u32)(r1 - r0); rg.k = c->P.k;
+    rg.by_slot0 = F.bt.by_slot0; rg.by_slot_first = F.bt.by_slot_first; rg.n_batches = F.bt.n;
+    pw->c = c; pw->F = F; pw->rg = rg; *empty = false;
+    return MDBG_OK;
+}
+static int refuse_too_many_records(mdbg_ctx* c, uint64_t n_records) {
+    return n_records < 0xFFFFFFF0ull ? MDBG_OK : fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
+}
+// The prologue of a read-path, junction or transit call (what_is: "read paths are", ...): the device time of the stage's last call <- 0, the two refusals, the
+// store's range for the current list and, for a stage with records, the bound on the list's edge records.
+static int stage_prologue(mdbg_ctx* c, const char* what_is, uint64_t first_read, uint64_t max_reads, bool with_records, double* ms, PlaceWindows* pw, bool* empty) {
+    *ms = 0; *empty = true;
+    int e;
+    if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
+    const UnitigResult& ul = c->res.unitigs.last;
+    if ((e = store_range(c, ul.n_unitigs, ul.n_entries, first_read, max_reads, pw, empty)) || *empty) return e;
+    return with_records ? refuse_too_many_records(c, ul.edges.n) : MDBG_OK;
+}
+// the defect mask of a stage (RP_DEFECT_* | JX_DEFECT_EDGE | TX_DEFECT_SHAPE) as the call's answer
+static int stage_defect(mdbg_ctx* c, uint32_t defect) {
+    if (defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, "an edge record of the unitig list names a unitig outside the list");
+    if (defect & TX_DEFECT_SHAPE) return fail(c, MDBG_E_DEVICE, "two explained crossings in a row do not walk all of one unitig: the edge records are not those of the unitig list");
+    if (defect & RP_DEFECT_ENTRY) return fail(c, MDBG_E_DEVICE, "an entry of the unitig list names a node index that is not a row of the node table");
+    if (defect & RP_DEFECT_PROBE) return fail(c, MDBG_E_DEVICE, "a probe sequence of the read paths visited every slot of the table");
+    if (defect & RP_DEFECT_ROW) return fail(c, MDBG_E_DEVICE, "a solid slot's first sighting is no row of the node table");
+    return MDBG_OK;
 }
 
 // ---- graph edges of the last finalized node table (edges.hip) -------------------------------------------
@@ -52,16 +118,6 @@ int mdbg_graph_edges_device(mdbg_ctx* c, float presimp, mdbg_edge_list* out) { r
 
 // ---- unitigs + base-space copy plan of the last node table and edge list (unitigs.hip) -------------------
 // steps == nullptr: plain compaction (mdbg_graph_unitigs); otherwise the schedule runs first (mdbg_graph_simplify, simplify.hip) and stats is filled
-// (what an EDGES step shares with the read paths and the junction support, defined beside them below)
-static int store_range(mdbg_ctx* c, uint64_t n_unitigs, uint64_t n_entries, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty);
-static int placement_defect(mdbg_ctx* c, uint32_t defect);
-static const char* const JX_EDGE_DEFECT_TEXT = "an edge record of the unitig list names a unitig outside the list";
-// the window placer as simplify.hip calls it between the two halves of the junction stage (SimplifySupport::place)
-struct PlaceForSimplify { mdbg_ctx* c; FinArgs F; ReadPathRange rg; };
-static void place_for_simplify(void* ctx, const ReadPathPlan& plan, hipStream_t s) {
-    const PlaceForSimplify& p = *(const PlaceForSimplify*)ctx;
-    launch_place_windows(table_args(p.c), p.F, p.c->fin_words, plan, p.F.mh, p.F.mread, p.F.roff, p.rg.i0, p.rg.i1, s);
-}
 static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n_steps, mdbg_unitig_list* out, mdbg_simplify_stats* stats, bool to_host) {
     MDBG_ENTER(c, out && !(stats && n_steps && !steps));
     memset(out, 0, sizeof *out);
@@ -90,14 +146,12 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (!R.edge_list_current()) return fail(c, MDBG_E_STATE, "no current edge list on this context (call mdbg_finalize* and mdbg_graph_edges* first)");
     if (R.n_rows() == 0) { R.unitig_list_is(UnitigResult{}); return MDBG_OK; }
     if (with_components) R.comps.buf.get();
-    SimplifySupport sup{}; PlaceForSimplify pfs{};
+    SimplifySupport sup{}; PlaceWindows pw{};
     if (with_edges) {                                // what the junction support asks, before anything of the schedule is launched
-        if (R.edges.last.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
-        bool empty;
-        const int e = store_range(c, 1, R.n_rows(), 0, 0, &pfs.rg, &pfs.F, &empty);
-        if (e) return e;
-        pfs.c = c;
-        sup.jb = R.junctions.buf.get(); sup.index = c->finF.o_index; sup.n_rows = R.n_rows(); sup.range = pfs.rg; sup.has_reads = !empty; sup.place = place_for_simplify; sup.ctx = &pfs;
+        int e; bool empty;
+        if ((e = refuse_too_many_records(c, R.edges.last.n)) || (e = store_range(c, 1, R.n_rows(), 0, 0, &pw, &empty))) return e;
+        sup.jb = R.junctions.buf.get(); sup.pb = R.placement.buf.get(); sup.index = c->finF.o_index; sup.n_rows = R.n_rows(); sup.range = pw.rg; sup.has_reads = !empty;
+        sup.placer = WindowPlacer{place_windows, &pw};
         R.junctions.ms = 0;
     }
     const FinArgs& F = c->finF;
@@ -110,8 +164,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
                                 : build_unitigs(UL.buf.get(), nd, R.edges.last, c->stream, &r, &broken);
     if (he != hipSuccess) return fail_hip(c, "build_unitigs", he);
     if (with_edges) R.junctions.ms = si.junction_ms;
-    if (broken && (si.junction_defect & JX_DEFECT_EDGE)) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
-    if (broken && si.junction_defect) return placement_defect(c, si.junction_defect);
+    if (broken && si.junction_defect) return stage_defect(c, si.junction_defect);
     if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, or the walk broke an invariant");
     if (stats) {
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
@@ -266,76 +319,21 @@ int mdbg_graph_node_seqs(mdbg_ctx* c, uint64_t first_row, uint64_t max_rows, uin
 int mdbg_graph_node_seqs_device(mdbg_ctx* c, uint64_t first_row, uint64_t max_rows, uint64_t max_bases, mdbg_node_seqs* out) { return node_seqs_impl(c, first_row, max_rows, max_bases, out, false); }
 int mdbg_node_seqs_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.nseq.ms : nullptr, ms); }
 
-// ---- the resident reads threaded through the current unitig list (place_windows.hip, read_paths.hip) ---------
-// roff[r] where the host knows it without asking the device: r is the first slot of a batch, or one past its last
-static bool known_read_offset(const mdbg_ctx* c, u64 r, u64* v) {
-    for (const Batch& b : c->batches) {
-        if (b.slot0 == r) { *v = b.m0; return true; }
-        if ((u64)b.slot0 + b.n_reads == r) { *v = b.m1; return true; }
-    }
-    return false;
-}
-// What the read paths and the junction support ask before they place a window: the state, the bounds, the range of reads with its minimizer indices, the store's
-// arrays.  what_is: "read paths are", ...  *empty <- the call answers MDBG_OK with zero counts (an empty context, an empty list, a range behind the store).
-static int placement_range(mdbg_ctx* c, const char* what_is, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty) {
-    *empty = true;
-    int e;
-    if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
-    const UnitigResult& ul = c->res.unitigs.last;
-    return store_range(c, ul.n_unitigs, ul.n_entries, first_read, max_reads, range, fin, empty);
-}
-// placement_range behind its two refusals, for a list of n_unitigs unitigs and n_entries entries: an EDGES step of a simplify schedule (unitigs_impl) asks it for
-// the lists it is going to build, which have at most as many entries as the table has rows
-static int store_range(mdbg_ctx* c, uint64_t n_unitigs, uint64_t n_entries, uint64_t first_read, uint64_t max_reads, ReadPathRange* range, FinArgs* fin, bool* empty) {
-    *empty = true;
-    Results& R = c->res;
-    if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
-    if (n_unitigs == 0 || first_read >= c->n_slots) return MDBG_OK;
-    if (n_entries >= (1ull << 30) || R.n_rows() >= (1ull << 30)) return fail(c, MDBG_E_CAPACITY, "more than 2^30 nodes");
-    hipStream_t s = c->stream;
-    const u64 r0 = first_read, r1 = max_reads && max_reads < c->n_slots - r0 ? r0 + max_reads : c->n_slots;
-    ReadPathRange rg{};
-    const bool known0 = known_read_offset(c, r0, &rg.i0), known1 = known_read_offset(c, r1, &rg.i1);
-    if (!known0) HIPCHK(c, hipMemcpyAsync(&rg.i0, c->roff.as<u64>() + r0, 8, hipMemcpyDeviceToHost, s));
-    if (!known1) HIPCHK(c, hipMemcpyAsync(&rg.i1, c->roff.as<u64>() + r1, 8, hipMemcpyDeviceToHost, s));
-    if (!(known0 && known1)) HIPCHK(c, hipStreamSynchronize(s));      // (a range that starts or ends inside a batch: one more wait, for its two offsets)
-    if (rg.i1 < rg.i0 || rg.i1 > c->M) return fail(c, MDBG_E_DEVICE, "the read offsets of the store are not ascending");
-    if (rg.i1 - rg.i0 >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 minimizers in the range of reads");
-    for (Batch& b : c->batches) fill_mread_of(c, b);
-    FinArgs F = c->finF;
-    F.mh = c->mh.as<u64>(); F.roff = c->roff.as<u64>(); F.mread = c->mread.as<u32>();
-    rg.roff = F.roff; rg.mread = F.mread; rg.first_read = (u32)r0; rg.n_reads = (u32)(r1 - r0); rg.k = c->P.k;
-    rg.by_slot0 = F.bt.by_slot0; rg.by_slot_first = F.bt.by_slot_first; rg.n_batches = F.bt.n;
-    *range = rg; *fin = F; *empty = false;
-    return MDBG_OK;
-}
-static int placement_defect(mdbg_ctx* c, uint32_t defect) {
-    if (defect & RP_DEFECT_ENTRY) return fail(c, MDBG_E_DEVICE, "an entry of the unitig list names a node index that is not a row of the node table");
-    if (defect & RP_DEFECT_PROBE) return fail(c, MDBG_E_DEVICE, "a probe sequence of the read paths visited every slot of the table");
-    if (defect & RP_DEFECT_ROW) return fail(c, MDBG_E_DEVICE, "a solid slot's first sighting is no row of the node table");
-    return MDBG_OK;
-}
+// ---- the resident reads threaded through the current unitig list (read_paths.hip) ---------
 static int read_paths_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out, bool to_host) {
     MDBG_ENTER(c, out);
     memset(out, 0, sizeof *out);
     out->first_read = first_read;
     Results& R = c->res;
     auto& P = R.rpaths;
-    P.ms = 0;
-    ReadPathRange rg; FinArgs F; bool empty;
-    const int e = placement_range(c, "read paths are", first_read, max_reads, &rg, &F, &empty);
+    PlaceWindows pw; bool empty;
+    const int e = stage_prologue(c, "read paths are", first_read, max_reads, false, &P.ms, &pw, &empty);
     if (e || empty) return e;
-    const UnitigResult& ul = R.unitigs.last;
-    hipStream_t s = c->stream;
-    ReadPathPlan plan;
-    hipError_t he = read_paths_begin(P.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
-    if (he != hipSuccess) return fail_hip(c, "read_paths_begin", he);
-    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
     ReadPathResult r;
-    he = read_paths_end(P.buf.get(), ul, rg, s, &r);
-    if (he != hipSuccess) return fail_hip(c, "read_paths_end", he);
+    const hipError_t he = read_paths_run(P.buf.get(), R.placement.buf.get(), R.unitigs.last, pw.F.o_index, R.n_rows(), pw.rg, WindowPlacer{place_windows, &pw}, c->stream, &r);
+    if (he != hipSuccess) return fail_hip(c, "read_paths_run", he);
     P.ms = r.ms;
-    if (r.defect) return placement_defect(c, r.defect);
+    if (r.defect) return stage_defect(c, r.defect);
     const u64 nr = r.n_reads, ns = r.n_steps, U = r.n_unitigs;
     out->n_reads = nr; out->n_windows = r.n_windows; out->n_placed = r.n_placed; out->n_steps = ns; out->n_unitigs = U;
     HandOver ho{c, "host copy of the read paths", to_host};
@@ -355,30 +353,21 @@ int mdbg_graph_read_paths(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, 
 int mdbg_graph_read_paths_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_read_path_list* out) { return read_paths_impl(c, first_read, max_reads, out, false); }
 int mdbg_read_paths_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.rpaths.ms : nullptr, ms); }
 
-// ---- read support per junction of the current unitig list (place_windows.hip, junctions.hip) -----------------
+// ---- read support per junction of the current unitig list (junctions.hip) -----------------
 static int junctions_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out, bool to_host) {
     MDBG_ENTER(c, out);
     memset(out, 0, sizeof *out);
     out->first_read = first_read;
     Results& R = c->res;
     auto& J = R.junctions;
-    J.ms = 0;
-    ReadPathRange rg; FinArgs F; bool empty;
-    const int e = placement_range(c, "junctions are", first_read, max_reads, &rg, &F, &empty);
+    PlaceWindows pw; bool empty;
+    const int e = stage_prologue(c, "junctions are", first_read, max_reads, true, &J.ms, &pw, &empty);
     if (e || empty) return e;
-    const UnitigResult& ul = R.unitigs.last;
-    if (ul.edges.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
-    hipStream_t s = c->stream;
-    ReadPathPlan plan;
-    hipError_t he = junctions_begin(J.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
-    if (he != hipSuccess) return fail_hip(c, "junctions_begin", he);
-    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
     JunctionResult r;
-    he = junctions_end(J.buf.get(), ul, rg, s, &r);
-    if (he != hipSuccess) return fail_hip(c, "junctions_end", he);
+    const hipError_t he = junctions_run(J.buf.get(), R.placement.buf.get(), R.unitigs.last, pw.F.o_index, R.n_rows(), pw.rg, WindowPlacer{place_windows, &pw}, c->stream, &r);
+    if (he != hipSuccess) return fail_hip(c, "junctions_run", he);
     J.ms = r.ms;
-    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
-    if (r.defect) return placement_defect(c, r.defect);
+    if (r.defect) return stage_defect(c, r.defect);
     const u64 nrec = r.n_records, nm = r.n_missing;
     out->n_reads = r.n_reads; out->n_adjacent = r.n_adjacent; out->n_links = r.n_links; out->n_crossings = r.n_crossings; out->n_explained = r.n_explained;
     out->n_missing_crossings = r.n_missing_crossings; out->n_records = nrec; out->n_missing = nm;
@@ -397,7 +386,7 @@ int mdbg_graph_junctions(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, m
 int mdbg_graph_junctions_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_junction_list* out) { return junctions_impl(c, first_read, max_reads, out, false); }
 int mdbg_junctions_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.junctions.ms : nullptr, ms); }
 
-// ---- reads that span a unitig end to end, and the repeats they resolve (place_windows.hip, transits.hip) ------
+// ---- reads that span a unitig end to end, and the repeats they resolve (transits.hip) ------
 static int transits_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out, bool to_host) {
     MDBG_ENTER(c, out);
     if (min_support == 0) return fail(c, MDBG_E_PARAM, "min_support must be >= 1");
@@ -405,24 +394,14 @@ static int transits_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, u
     out->first_read = first_read;
     Results& R = c->res;
     auto& T = R.transits;
-    T.ms = 0;
-    ReadPathRange rg; FinArgs F; bool empty;
-    const int e = placement_range(c, "transits are", first_read, max_reads, &rg, &F, &empty);
+    PlaceWindows pw; bool empty;
+    const int e = stage_prologue(c, "transits are", first_read, max_reads, true, &T.ms, &pw, &empty);
     if (e || empty) return e;
-    const UnitigResult& ul = R.unitigs.last;
-    if (ul.edges.n >= 0xFFFFFFF0ull) return fail(c, MDBG_E_CAPACITY, "more than 2^32 edge records");
-    hipStream_t s = c->stream;
-    ReadPathPlan plan;
-    hipError_t he = transits_begin(T.buf.get(), ul, F.o_index, R.n_rows(), rg, s, &plan);
-    if (he != hipSuccess) return fail_hip(c, "transits_begin", he);
-    launch_place_windows(table_args(c), F, c->fin_words, plan, F.mh, F.mread, F.roff, rg.i0, rg.i1, s);
     TransitResult r;
-    he = transits_end(T.buf.get(), ul, rg, min_support, s, &r);
-    if (he != hipSuccess) return fail_hip(c, "transits_end", he);
+    const hipError_t he = transits_run(T.buf.get(), R.placement.buf.get(), R.unitigs.last, pw.F.o_index, R.n_rows(), pw.rg, min_support, WindowPlacer{place_windows, &pw}, c->stream, &r);
+    if (he != hipSuccess) return fail_hip(c, "transits_run", he);
     T.ms = r.ms;
-    if (r.defect & JX_DEFECT_EDGE) return fail(c, MDBG_E_DEVICE, JX_EDGE_DEFECT_TEXT);
-    if (r.defect & TX_DEFECT_SHAPE) return fail(c, MDBG_E_DEVICE, "two explained crossings in a row do not walk all of one unitig: the edge records are not those of the unitig list");
-    if (r.defect) return placement_defect(c, r.defect);
+    if (r.defect) return stage_defect(c, r.defect);
     const u64 nt = r.n_transits, U = r.n_unitigs;
     out->n_reads = r.n_reads; out->n_crossings = r.n_crossings; out->n_explained = r.n_explained; out->n_passes = r.n_passes; out->n_transits = nt;
     out->n_unitigs = U; out->n_repeats = r.n_repeats; out->n_resolved = r.n_resolved;

@@ -1,5 +1,5 @@
-// graph_common.h — what the graph stages (edges.hip, unitigs.hip, simplify.hip, contigs.hip) share on the host side: the grow-only device block, the
-// two-phase rocPRIM calls and the read-back of a scan's total.  Header-only; it pulls in rocPRIM, so only those translation units include it (never libmdbg.hip).
+// graph_common.h — what the graph stages (edges.hip, unitigs.hip, simplify.hip, contigs.hip, placement.hip, ...) share on the host side: the grow-only device block, the
+// two-phase rocPRIM calls, the read-back of a scan's total and the timer of a read-evidence stage.  Header-only; it pulls in rocPRIM, so only those translation units include it (never libmdbg.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -32,6 +32,24 @@ struct Buf {
 };
 
 inline unsigned grid_for(u64 n) { return (unsigned)((n + 255) / 256); }
+
+// device time of one call of a read-evidence stage (read_paths.hip, junctions.hip, transits.hip), and how such a call ends
+struct StageTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~StageTimer() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    hipError_t start(hipStream_t s) {
+        if (!ev0) { GHIP(hipEventCreate(&ev0)); GHIP(hipEventCreate(&ev1)); }
+        return hipEventRecord(ev0, s);
+    }
+    // the closing event, ONE read-back (the stage's counters) and the call's ONE wait; *ms <- device time since start()
+    hipError_t stop_and_read(void* host, const void* dev, size_t bytes, hipStream_t s, float* ms) {
+        GHIP(hipEventRecord(ev1, s));
+        GHIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+        GHIP(hipStreamSynchronize(s));
+        if (hipEventElapsedTime(ms, ev0, ev1) != hipSuccess) { (void)hipGetLastError(); *ms = 0; }
+        return hipSuccess;
+    }
+};
 
 // ---- rocPRIM, two-phase: ask for the temporary size, grow `tmp`, run.  One `tmp` serves every call of a stage although the calls are only stream-ordered:
 // growing it frees the old block through mdbg_block_free, which synchronises the device for blocks of 1 MB and more, and hipFree does so for smaller ones,

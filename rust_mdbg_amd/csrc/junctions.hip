@@ -1,17 +1,14 @@
 // junctions.hip — read support per junction of the current unitig list, on the GPU (gfx950): how many resident reads cross each edge record, and which
 // crossings lie on no record.  Definition: include/mdbg_hip.h (mdbg_graph_junctions).  Input: the device arrays of a unitig list (unitigs.hip) with its edge
-// records, the store's read offsets and minimizer -> read map, and the per-index place codes of the read paths (read_paths.h: placement_begin builds the row ->
-// entry map, place_windows_kernel writes code[t] = global entry | strand << 31 or NONE), kept in buffers of this stage.
+// records, the store's read offsets and minimizer -> read map, and the placement with records (placement.h): unitig_of_entry, the per-index place codes
+// (code[t] = global entry | strand << 31 or NONE) and the edge records in key order, in the context's one placement scratch.
 //
-// Vertices, pairs and keys are packed as record_keys.h says, which also holds record_key_kernel (shared with transits.hip): the order of the packed keys is the
-// definition's order of keys.
+// Vertices, pairs and keys are packed as placement_dev.h says: the order of the packed keys is the definition's order of keys.
 //
-//   (memset)            the counters, the map, the counter slots <- 0
-//   entry_kernel        (read_paths.hip) the row -> entry map, unitig_of_entry
-//   record_key_kernel   (record_keys.h) one thread per edge record r: rkey[r] = the record's key, rec[r] = r.  A record that names a unitig outside the list sets JX_DEFECT_EDGE
-//   (rocPRIM)           sort_pairs(rkey, rec): equal keys are one run, the run's first position is the key's counter slot
-//   place_windows_kernel  (place_windows.hip) code[]
-//   cross_kernel        one thread per minimizer index t of the range: code[t - 1] -> code[t], both placed and in one read, is a link or a crossing; a crossing's
+//   (memset)            the counter slots <- 0
+//   (placement_queue)   the counters and the map zeroed, entry_kernel, record_key_kernel, sort_pairs(rkey, rec): equal keys are one run, the run's first
+//                       position is the key's counter slot; place_windows_kernel: code[]
+//   cross_kernel       one thread per minimizer index t of the range: code[t - 1] -> code[t], both placed and in one read, is a link or a crossing; a crossing's
 //                       key is searched in the sorted record keys: found, one integer atomic on the key's slot; not found, the key goes to mkey[t] (else ~0).
 //                       The four counts are reduced per workgroup: one atomic each
 //   (rocPRIM)           sort_keys(mkey): the missing crossings in key order, the ~0 of every other index behind them
@@ -20,68 +17,51 @@
 //   support_kernel      one thread per sorted record: support[rec] = the slot at the first position of its key
 //
 // All sums are integers and every position comes from a sort or a scan: two calls give identical arrays.  No loop but the binary searches; the number of
-// launches is fixed.  Per minimizer index of the range: 25 bytes of temporaries (code 4, mkey and its sorted copy 16, flag 1, pos 4) and 26 bytes of missing
-// columns, sized for the worst case (every pair a missing crossing of its own) because their number is known only on the device.
+// launches is fixed.  Per minimizer index of the range, beside the placement's 4: 21 bytes of temporaries (mkey and its sorted copy 16, flag 1, pos 4) and 26
+// bytes of missing columns, sized for the worst case (every pair a missing crossing of its own) because their number is known only on the device.  Per edge
+// record, beside the placement's 24: the counter slot 8 and the support 8.
 #include <cstring>
 
 #include "junctions.h"
-#include "graph_common.h"
-#include "record_keys.h"
+#include "placement_dev.h"
 
 struct JunctionBuffers {
-    Buf entry_of_row, unitig_of_entry, code, counters, tmp;
-    Buf rkey, rkey_sorted, rec, rec_sorted, slot;          // per edge record
-    Buf mkey, mkey_sorted, flag, pos;                      // per minimizer index
+    Buf slot;                                              // per edge record
+    Buf mkey, mkey_sorted, flag, pos, tmp;                 // per minimizer index
     Buf support, mu1, me1, ms1, mu2, me2, ms2, mcount;     // the result
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~JunctionBuffers() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    StageTimer timer;
 };
 
 namespace {
 
 struct JxArgs {
-    u64 U, N, R; const u64* offsets; const u32* unitig_of_entry;
-    const u32* n1; const u8* o1; const u32* n2; const u8* o2;
-    u64* rkey; u32* rec; const u64* rkey_sorted; const u32* rec_sorted; u64* slot;
+    u64 R; const u64* offsets; const u32* unitig_of_entry;
+    const u64* rkey_sorted; const u32* rec_sorted; u64* slot;
     const u64* roff; const u32* mread; u64 i0, n_idx;
     const u32* code; u64* mkey; const u64* mkey_sorted; u8* flag; const u32* pos; u64* counters;
     u64* support; u32* mu1; u32* me1; u8* ms1; u32* mu2; u32* me2; u8* ms2; u64* mcount;
 };
 
 __global__ __launch_bounds__(256) void cross_kernel(JxArgs a) {
-    __shared__ u32 wsum[4][4];
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     u32 cnt[4] = {0, 0, 0, 0};         // adjacent, links, explained, missing crossings
     if (t < a.n_idx) {
         u64 missing = JX_NO_KEY;
         const u32 c = a.code[t];
-        const u64 i = a.i0 + t;
-        if (c != RP_NONE && t > 0 && i > a.roff[a.mread[i]]) {          // (the range starts at a read's first index; the test of head_kernel, read_paths.hip)
-            const u32 pc = a.code[t - 1];
-            if (pc != RP_NONE) {
-                cnt[0] = 1;
-                const u32 e = c & ~RP_STRAND, pe = pc & ~RP_STRAND;
-                const bool link = !((pc ^ c) & RP_STRAND) && a.unitig_of_entry[e] == a.unitig_of_entry[pe] && (c & RP_STRAND ? pe == e + 1 : e == pe + 1);
-                if (link) cnt[1] = 1;
-                else {
-                    const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
-                    const u64 p = lower_bound(a.rkey_sorted, a.R, key);
-                    if (p < a.R && a.rkey_sorted[p] == key) { atomicAdd((unsigned long long*)(a.slot + p), 1ull); cnt[2] = 1; }
-                    else { missing = key; cnt[3] = 1; }
-                }
+        u32 pc;
+        if (adjacent_in_read(a.code, a.roff, a.mread, a.i0, t, c, &pc)) {
+            cnt[0] = 1;
+            if (is_link_of_codes(pc, c, a.unitig_of_entry)) cnt[1] = 1;
+            else {
+                const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
+                const u64 p = lower_bound(a.rkey_sorted, a.R, key);
+                if (p < a.R && a.rkey_sorted[p] == key) { atomicAdd((unsigned long long*)(a.slot + p), 1ull); cnt[2] = 1; }
+                else { missing = key; cnt[3] = 1; }
             }
         }
         a.mkey[t] = missing;
     }
-    // the workgroup's counts: one atomic each
-#pragma unroll
-    for (int q = 0; q < 4; ++q) for (int d = 32; d; d >>= 1) cnt[q] += __shfl_down(cnt[q], d, 64);
-    if ((threadIdx.x & 63) == 0) for (int q = 0; q < 4; ++q) wsum[q][threadIdx.x >> 6] = cnt[q];
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const u32 v = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
-        if (v) atomicAdd((unsigned long long*)(a.counters + JX_C_ADJACENT + threadIdx.x), (unsigned long long)v);
-    }
+    block_add<4>(cnt, a.counters, JX_C_ADJACENT);
 }
 
 __global__ __launch_bounds__(256) void head_kernel(JxArgs a) {
@@ -113,13 +93,12 @@ __global__ __launch_bounds__(256) void support_kernel(JxArgs a) {
     if (r < a.R) a.support[r] = a.slot[lower_bound(a.rkey_sorted, a.R, a.rkey_sorted[p])];
 }
 
-JxArgs args_of(JunctionBuffers* B, const UnitigResult& ul, const ReadPathRange& rg) {
+JxArgs args_of(JunctionBuffers* B, const PlacementView& V, const UnitigResult& ul, const ReadPathRange& rg) {
     JxArgs a; memset(&a, 0, sizeof a);
-    a.U = ul.n_unitigs; a.N = ul.n_entries; a.R = ul.edges.n; a.offsets = ul.offsets; a.unitig_of_entry = B->unitig_of_entry.as<u32>();
-    a.n1 = ul.edges.n1; a.o1 = ul.edges.o1; a.n2 = ul.edges.n2; a.o2 = ul.edges.o2;
-    a.rkey = B->rkey.as<u64>(); a.rec = B->rec.as<u32>(); a.rkey_sorted = B->rkey_sorted.as<u64>(); a.rec_sorted = B->rec_sorted.as<u32>(); a.slot = B->slot.as<u64>();
+    a.R = V.R; a.offsets = ul.offsets; a.unitig_of_entry = V.unitig_of_entry;
+    a.rkey_sorted = V.rkey_sorted; a.rec_sorted = V.rec_sorted; a.slot = B->slot.as<u64>();
     a.roff = rg.roff; a.mread = rg.mread; a.i0 = rg.i0; a.n_idx = rg.i1 - rg.i0;
-    a.code = B->code.as<u32>(); a.mkey = B->mkey.as<u64>(); a.mkey_sorted = B->mkey_sorted.as<u64>(); a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.counters = B->counters.as<u64>();
+    a.code = V.code; a.mkey = B->mkey.as<u64>(); a.mkey_sorted = B->mkey_sorted.as<u64>(); a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.counters = V.counters;
     a.support = B->support.as<u64>(); a.mu1 = B->mu1.as<u32>(); a.me1 = B->me1.as<u32>(); a.ms1 = B->ms1.as<u8>(); a.mu2 = B->mu2.as<u32>(); a.me2 = B->me2.as<u32>(); a.ms2 = B->ms2.as<u8>();
     a.mcount = B->mcount.as<u64>();
     return a;
@@ -130,44 +109,27 @@ JxArgs args_of(JunctionBuffers* B, const UnitigResult& ul, const ReadPathRange& 
 JunctionBuffers* junction_buffers_create() { return new JunctionBuffers(); }
 void junction_buffers_destroy(JunctionBuffers* b) { delete b; }
 
-hipError_t junctions_begin(JunctionBuffers* B, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan) {
-    memset(plan, 0, sizeof *plan);
-    const u64 U = ul.n_unitigs, N = ul.n_entries, R = ul.edges.n, n_idx = rg.i1 - rg.i0;
-    if (U == 0 || N == 0 || n_rows == 0 || N >= (1ull << 30) || n_rows >= (1ull << 30) || n_idx >= 0xFFFFFFF0ull || R >= 0xFFFFFFF0ull) return hipErrorInvalidValue;      // (junctions_impl has answered MDBG_E_CAPACITY or returned before)
-    if (!B->ev0) { GHIP(hipEventCreate(&B->ev0)); GHIP(hipEventCreate(&B->ev1)); }
+hipError_t junctions_run(JunctionBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
+                         hipStream_t s, JunctionResult* out) {
+    memset(out, 0, sizeof *out);
+    const u64 R = ul.edges.n, n_idx = rg.i1 - rg.i0;
     // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
-    GHIP(B->counters.ensure(JX_C_N * 8));
-    GHIP(B->entry_of_row.ensure(n_rows * 4)); GHIP(B->unitig_of_entry.ensure(N * 4)); GHIP(B->code.ensure(n_idx * 4 + 4));
-    GHIP(B->rkey.ensure(R * 8 + 8)); GHIP(B->rkey_sorted.ensure(R * 8 + 8)); GHIP(B->rec.ensure(R * 4 + 4)); GHIP(B->rec_sorted.ensure(R * 4 + 4)); GHIP(B->slot.ensure(R * 8 + 8)); GHIP(B->support.ensure(R * 8 + 8));
+    GHIP(placement_reserve(P, ul, n_rows, rg, true));
+    GHIP(B->slot.ensure(R * 8 + 8)); GHIP(B->support.ensure(R * 8 + 8));
     GHIP(B->mkey.ensure(n_idx * 8 + 8)); GHIP(B->mkey_sorted.ensure(n_idx * 8 + 8)); GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
     GHIP(B->mu1.ensure(n_idx * 4 + 4)); GHIP(B->me1.ensure(n_idx * 4 + 4)); GHIP(B->ms1.ensure(n_idx + 4)); GHIP(B->mu2.ensure(n_idx * 4 + 4)); GHIP(B->me2.ensure(n_idx * 4 + 4)); GHIP(B->ms2.ensure(n_idx + 4));
     GHIP(B->mcount.ensure(n_idx * 8 + 8));
-    {   // the largest temporary of the three rocPRIM calls, so that `tmp` does not grow between them
+    if (n_idx) {   // the larger temporary of the stage's two rocPRIM calls, so that `tmp` does not grow between them
         size_t tb = 0, most = 0;
-        if (R) { GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->rkey.as<u64>(), B->rkey_sorted.as<u64>(), B->rec.as<u32>(), B->rec_sorted.as<u32>(), (size_t)R, 0u, 64u, s)); most = tb; }
-        if (n_idx) {
-            GHIP(rocprim::radix_sort_keys(nullptr, tb, B->mkey.as<u64>(), B->mkey_sorted.as<u64>(), (size_t)n_idx, 0u, 64u, s)); if (tb > most) most = tb;
-            GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); if (tb > most) most = tb;
-        }
+        GHIP(rocprim::radix_sort_keys(nullptr, most, B->mkey.as<u64>(), B->mkey_sorted.as<u64>(), (size_t)n_idx, 0u, 64u, s));
+        GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); if (tb > most) most = tb;
         GHIP(B->tmp.ensure(most + 256));
     }
-    GHIP(hipEventRecord(B->ev0, s));
-    const PlacementArrays pa{B->entry_of_row.as<u32>(), B->unitig_of_entry.as<u32>(), B->code.as<u32>(), B->counters.as<u64>(), JX_C_N};
-    GHIP(placement_begin(pa, ul, index, n_rows, s, plan));
-    if (R) {
-        const JxArgs a = args_of(B, ul, rg);
-        GHIP(hipMemsetAsync(B->slot.p, 0, R * 8, s));
-        const RecordKeyArgs rk{a.U, a.R, a.offsets, a.n1, a.o1, a.n2, a.o2, a.rkey, a.rec, a.counters + RP_C_DEFECT, JX_DEFECT_EDGE};
-        hipLaunchKernelGGL(record_key_kernel, dim3(grid_for(R)), dim3(256), 0, s, rk);
-        GHIP(hipGetLastError());
-        GHIP(sort_pairs(B->tmp, (const u64*)a.rkey, B->rkey_sorted.as<u64>(), (const u32*)a.rec, B->rec_sorted.as<u32>(), (size_t)R, 0u, 64u, s));
-    }
-    return hipSuccess;
-}
-
-hipError_t junctions_end(JunctionBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, hipStream_t s, JunctionResult* out) {
-    memset(out, 0, sizeof *out);
-    const JxArgs a = args_of(B, ul, rg);
+    GHIP(B->timer.start(s));
+    if (R) GHIP(hipMemsetAsync(B->slot.p, 0, R * 8, s));
+    PlacementView V;
+    GHIP(placement_queue(P, ul, index, n_rows, rg, true, JX_C_N, placer, s, &V));
+    const JxArgs a = args_of(B, V, ul, rg);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);
         hipLaunchKernelGGL(cross_kernel, dim3(gi), dim3(256), 0, s, a);
@@ -179,11 +141,8 @@ hipError_t junctions_end(JunctionBuffers* B, const UnitigResult& ul, const ReadP
     }
     if (a.R) hipLaunchKernelGGL(support_kernel, dim3(grid_for(a.R)), dim3(256), 0, s, a);
     GHIP(hipGetLastError());
-    GHIP(hipEventRecord(B->ev1, s));
     u64 h[JX_C_N];
-    GHIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-    GHIP(hipStreamSynchronize(s));
-    if (hipEventElapsedTime(&out->ms, B->ev0, B->ev1) != hipSuccess) { (void)hipGetLastError(); out->ms = 0; }
+    GHIP(B->timer.stop_and_read(h, a.counters, sizeof h, s, &out->ms));
     out->defect = (u32)h[RP_C_DEFECT];
     if (out->defect) return hipSuccess;
     out->n_reads = rg.n_reads; out->n_adjacent = h[JX_C_ADJACENT]; out->n_links = h[JX_C_LINKS]; out->n_crossings = h[JX_C_ADJACENT] - h[JX_C_LINKS];

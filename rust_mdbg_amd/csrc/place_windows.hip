@@ -1,5 +1,5 @@
-// place_windows.hip — where on the current unitig list does every resident window lie (gfx950)?  The hot kernel of mdbg_graph_read_paths (include/mdbg_hip.h); the
-// rest of the stage is read_paths.hip.  Needs table.hip (the key hash and comparison, the slot layout) and finalize.hip (FinArgs, the batch table, the bitmaps).
+// place_windows.hip — where on the current unitig list does every resident window lie (gfx950)?  The hot kernel of the placement (placement.h) that every read-evidence
+// stage starts with; the rest of the placement is placement.hip.  Needs table.hip (the key hash and comparison, the slot layout) and finalize.hip (FinArgs, the batch table, the bitmaps).
 //
 // A window's key is looked up in the counting table as query_windows_kernel does; a hit that passes the abundance filter is a ROW of the last finalize's node table,
 // and which row follows from what that finalize left behind, without a second table over the node keys: the slot's first sighting (its claimer, or the smallest
@@ -7,7 +7,7 @@
 // — the expression fin_emit_kernel numbered the rows with.  fin_setup is the only writer of the bitmaps, the prefixes and the batch table, and it ends the node table
 // (Results::invalidate, results.inc) before it touches them, so they are intact whenever the caller's state checks pass.
 #include "mdbg_dev.h"
-#include "read_paths.h"
+#include "placement.h"
 
 // find_slot with the walk bounded by the table's capacity: ~0 when the key is absent; *full <- true when every slot was visited
 template <class EqFn>

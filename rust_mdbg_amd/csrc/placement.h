@@ -1,0 +1,51 @@
+// placement.h — where on the current unitig list every resident window lies, and the sorted keys of the list's edge records: the first half of every stage that
+// decides with the resident reads (read_paths.hip, junctions.hip, transits.hip, the EDGES step of simplify.hip).  The scratch is the context's, once
+// (PlacementBuffers, placement.hip); place_windows_kernel itself lives in the main translation unit beside the table (place_windows.hip) and is reached through
+// a WindowPlacer only.  Nothing here is a result: every call of a stage overwrites it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "unitigs.h"
+
+struct PlacementBuffers;           // scratch, owned by the context (opaque here)
+PlacementBuffers* placement_buffers_create();
+void placement_buffers_destroy(PlacementBuffers*);
+
+constexpr uint32_t RP_NONE = 0xFFFFFFFFu;         // entry_of_row: the row is in no entry; code: no window starts at the index, or the window is not placed
+constexpr uint32_t RP_STRAND = 0x80000000u;       // code = entry | strand << 31 (a list has fewer than 2^30 entries)
+// counters[] (u64 each), one read-back per call: the placement's own first, a stage's behind them (JX_C_*, TX_C_*).  RP_C_DEFECT is a mask of RP_DEFECT_*
+enum { RP_C_WINDOWS = 0, RP_C_PLACED, RP_C_STEPS, RP_C_DEFECT, RP_C_N };
+constexpr uint32_t PLACEMENT_COUNTERS = 16;       // the size of the block: it holds the largest stage's counters (each stage asserts that)
+enum { RP_DEFECT_ENTRY = 1,        // a list entry whose node index is not a row of the table
+       RP_DEFECT_PROBE = 2,        // a probe sequence visited every slot of the table
+       RP_DEFECT_ROW = 4 };        // a solid slot whose first sighting is no row of the table (the bitmaps are not this table's)
+constexpr uint32_t JX_DEFECT_EDGE = 8;            // beside RP_DEFECT_*: an edge record names a unitig outside the list (record_key_kernel)
+
+// the reads [first_read, first_read + n_reads) of the store and the minimizer indices [i0, i1) they cover
+struct ReadPathRange {
+    const uint64_t* roff; const uint32_t* mread; uint32_t first_read, n_reads, k; uint64_t i0, i1;
+    const uint32_t* by_slot0; const uint64_t* by_slot_first; uint32_t n_batches;      // the batches in slot order: first slot, first ordinal
+};
+// what place_windows_kernel reads and writes beside the table and the store
+struct ReadPathPlan {
+    const uint32_t* entry_of_row; uint64_t n_rows; const uint8_t* ori;
+    uint32_t* code;                // [i1 - i0]
+    uint64_t* counters;            // [PLACEMENT_COUNTERS]
+};
+// launches place_windows_kernel for the plan on the stream (graph_api.inc has the one there is)
+struct WindowPlacer { void (*place)(void* ctx, const ReadPathPlan& plan, hipStream_t s); void* ctx; };
+// what placement_queue leaves for the stage's kernels, valid until the next call of any stage
+struct PlacementView {
+    const uint32_t* entry_of_row;  // [n_rows]
+    const uint32_t* unitig_of_entry;      // [n_entries]
+    const uint32_t* code;          // [i1 - i0]: global entry | strand << 31, or RP_NONE
+    uint64_t* counters;            // [PLACEMENT_COUNTERS]
+    const uint64_t* rkey_sorted; const uint32_t* rec_sorted; uint64_t R;      // with records: the R edge records in key order (stable: a key's run starts at its smallest record)
+};
+// placement_reserve checks the bounds (hipErrorInvalidValue: the caller has answered MDBG_E_CAPACITY or returned before) and grows every buffer of the unit,
+// the sort's temporary included; a stage calls it beside its own `ensure`s, before it queues anything.  placement_queue then grows nothing: it queues the zeroing
+// of the first n_counters counters and of the map, entry_kernel, with records record_key_kernel and the stable pair sort, and the placer, and fills *view.
+hipError_t placement_reserve(PlacementBuffers* P, const UnitigResult& ul, uint64_t n_rows, const ReadPathRange& rg, bool with_records);
+hipError_t placement_queue(PlacementBuffers* P, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, const ReadPathRange& rg, bool with_records, uint32_t n_counters,
+                           const WindowPlacer& placer, hipStream_t s, PlacementView* view);

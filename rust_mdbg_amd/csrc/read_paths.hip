@@ -1,11 +1,10 @@
-// read_paths.hip — the resident reads threaded through the current unitig list, on the GPU (gfx950): everything of the stage except the table lookup.
-// Definition: include/mdbg_hip.h (mdbg_graph_read_paths).  Input: the device arrays of a unitig list (unitigs.hip), the node table's `index` column, the
-// store's read offsets and minimizer -> read map, and the per-index codes that place_windows_kernel (place_windows.hip, main translation unit) writes.
+// read_paths.hip — the resident reads threaded through the current unitig list, on the GPU (gfx950): everything of the stage behind the placement.
+// Definition: include/mdbg_hip.h (mdbg_graph_read_paths).  Input: the device arrays of a unitig list (unitigs.hip), the store's read offsets and minimizer ->
+// read map, and the placement (placement.h): unitig_of_entry and the per-index codes, in the context's one placement scratch.
 //
-//   (memset)            entry_of_row <- NONE, the support sums and the counters <- 0
-//   entry_kernel        one thread per list entry e: the row of node[e] by binary search (rows are in index order) gets e; unitig_of_entry[e] by binary
-//                       search in offsets.  A node index that is no row sets RP_DEFECT_ENTRY
-//   place_windows_kernel  (place_windows.hip) code[t] = entry | strand << 31 of the window that starts at index i0 + t, or NONE
+//   (memset)            the support sums <- 0
+//   (placement_queue)   the counters and the map zeroed, entry_kernel, place_windows_kernel: code[t] = entry | strand << 31 of the window that starts at index
+//                       i0 + t, or NONE
 //   head_kernel         flag[t] = 1 iff code[t] is a window and does not continue code[t - 1] inside the same read (same unitig and strand, the entry
 //                       one further in the read's direction, modulo the size on a circular unitig)
 //   (rocPRIM)           pos = exclusive scan of flag: a window's step is pos + flag - 1, the range's steps are numbered in index order
@@ -15,47 +14,29 @@
 //   finish_kernel       one thread per step: step_windows -= first_window; integer atomics add the step to its unitig's two sums
 //   reads_kernel        one thread per read: step_offsets[q] = pos at the read's first index, ordinal[q] from the batch table, read_windows[q] from its offsets
 //
-// All sums are integers and every position comes from the scan: two calls give identical arrays.  No loop but the two binary searches; the number of
-// launches is fixed.
+// All sums are integers and every position comes from the scan: two calls give identical arrays.  No loop but the binary search of reads_kernel; the number of
+// launches is fixed.  Per minimizer index of the range, beside the placement's 4: 5 bytes of temporaries (flag 1, pos 4) and 17 of step columns, sized for the
+// worst case (every window a step of its own).
 #include <cstring>
 
 #include "read_paths.h"
-#include "graph_common.h"
+#include "placement_dev.h"
 
 struct ReadPathBuffers {
-    Buf entry_of_row, unitig_of_entry, code, flag, pos, tmp, counters;
+    Buf flag, pos, tmp;
     Buf ordinal, read_windows, step_offsets, first_window, step_windows, unitig, first_entry, strand, sup_w, sup_s;      // the result
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~ReadPathBuffers() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    StageTimer timer;
 };
 
 namespace {
 
 struct RpArgs {
-    u64 U, N, n_rows; const u64* offsets; const u32* node; const u8* circ; const u32* index;
-    u32* entry_of_row; u32* unitig_of_entry;
+    u64 U; const u64* offsets; const u8* circ; const u32* unitig_of_entry;
     const u64* roff; const u32* mread; u32 r0, nr, k; u64 i0, n_idx;
     const u32* code; u8* flag; const u32* pos; u64* counters;
     u64* ordinal; u32* read_windows; u64* step_offsets; u32* first_window; u32* step_windows; u32* unitig; u32* first_entry; u8* strand; u64* sup_w; u64* sup_s;
     const u32* by_slot0; const u64* by_slot_first; u32 n_batches;
 };
-
-__device__ inline void set_defect(u64* counters, u32 what) { atomicOr((unsigned long long*)(counters + RP_C_DEFECT), (unsigned long long)what); }
-
-__global__ __launch_bounds__(256) void entry_kernel(RpArgs a) {
-    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.N) return;
-    {   // the unitig that holds entry e: the last u with offsets[u] <= e
-        u64 lo = 0, hi = a.U - 1;
-        while (lo < hi) { const u64 mid = lo + ((hi - lo + 1) >> 1); if (a.offsets[mid] <= e) lo = mid; else hi = mid - 1; }
-        a.unitig_of_entry[e] = (u32)lo;
-    }
-    const u32 idx = a.node[e];
-    u64 lo = 0, hi = a.n_rows;                 // as row_of (unitigs.hip)
-    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (a.index[mid] < idx) lo = mid + 1; else hi = mid; }
-    if (lo < a.n_rows && a.index[lo] == idx) a.entry_of_row[lo] = (u32)e;
-    else set_defect(a.counters, RP_DEFECT_ENTRY);
-}
 
 // does the placed window with code c continue the placed window with code pc (the index in front of it, same read)?
 __device__ inline bool continues(const RpArgs& a, u32 pc, u32 c) {
@@ -75,12 +56,8 @@ __global__ __launch_bounds__(256) void head_kernel(RpArgs a) {
     const u32 c = a.code[t];
     u8 f = 0;
     if (c != RP_NONE) {
-        f = 1;
-        const u64 i = a.i0 + t;
-        if (t > 0 && i > a.roff[a.mread[i]]) {             // (the range starts at a read's first index)
-            const u32 pc = a.code[t - 1];
-            if (pc != RP_NONE && continues(a, pc, c)) f = 0;
-        }
+        u32 pc;
+        f = !(adjacent_in_read(a.code, a.roff, a.mread, a.i0, t, c, &pc) && continues(a, pc, c));
     }
     a.flag[t] = f;
 }
@@ -127,12 +104,11 @@ __global__ __launch_bounds__(256) void reads_kernel(RpArgs a) {
     a.ordinal[q] = a.by_slot_first[lo] + (slot - a.by_slot0[lo]);
 }
 
-RpArgs args_of(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& rg) {
+RpArgs args_of(ReadPathBuffers* B, const PlacementView& V, const UnitigResult& ul, const ReadPathRange& rg) {
     RpArgs a; memset(&a, 0, sizeof a);
-    a.U = ul.n_unitigs; a.N = ul.n_entries; a.offsets = ul.offsets; a.node = ul.node; a.circ = ul.circular;
-    a.entry_of_row = B->entry_of_row.as<u32>(); a.unitig_of_entry = B->unitig_of_entry.as<u32>();
+    a.U = ul.n_unitigs; a.offsets = ul.offsets; a.circ = ul.circular; a.unitig_of_entry = V.unitig_of_entry;
     a.roff = rg.roff; a.mread = rg.mread; a.r0 = rg.first_read; a.nr = rg.n_reads; a.k = rg.k; a.i0 = rg.i0; a.n_idx = rg.i1 - rg.i0;
-    a.code = B->code.as<u32>(); a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.counters = B->counters.as<u64>();
+    a.code = V.code; a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.counters = V.counters;
     a.ordinal = B->ordinal.as<u64>(); a.read_windows = B->read_windows.as<u32>(); a.step_offsets = B->step_offsets.as<u64>(); a.first_window = B->first_window.as<u32>(); a.step_windows = B->step_windows.as<u32>();
     a.unitig = B->unitig.as<u32>(); a.first_entry = B->first_entry.as<u32>(); a.strand = B->strand.as<u8>(); a.sup_w = B->sup_w.as<u64>(); a.sup_s = B->sup_s.as<u64>();
     a.by_slot0 = rg.by_slot0; a.by_slot_first = rg.by_slot_first; a.n_batches = rg.n_batches;
@@ -144,41 +120,22 @@ RpArgs args_of(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& 
 ReadPathBuffers* read_path_buffers_create() { return new ReadPathBuffers(); }
 void read_path_buffers_destroy(ReadPathBuffers* b) { delete b; }
 
-hipError_t placement_begin(const PlacementArrays& A, const UnitigResult& ul, const u32* index, u64 n_rows, hipStream_t s, ReadPathPlan* plan) {
-    memset(plan, 0, sizeof *plan);
-    if (ul.n_unitigs == 0 || ul.n_entries == 0 || n_rows == 0 || A.n_counters < RP_C_N) return hipErrorInvalidValue;
-    GHIP(hipMemsetAsync(A.counters, 0, (size_t)A.n_counters * 8, s));
-    GHIP(hipMemsetAsync(A.entry_of_row, 0xFF, n_rows * 4, s));
-    RpArgs a; memset(&a, 0, sizeof a);      // (what entry_kernel reads)
-    a.U = ul.n_unitigs; a.N = ul.n_entries; a.offsets = ul.offsets; a.node = ul.node; a.index = index; a.n_rows = n_rows;
-    a.entry_of_row = A.entry_of_row; a.unitig_of_entry = A.unitig_of_entry; a.counters = A.counters;
-    hipLaunchKernelGGL(entry_kernel, dim3(grid_for(a.N)), dim3(256), 0, s, a);
-    plan->entry_of_row = A.entry_of_row; plan->n_rows = n_rows; plan->ori = ul.ori; plan->code = A.code; plan->counters = A.counters;
-    return hipGetLastError();
-}
-
-hipError_t read_paths_begin(ReadPathBuffers* B, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan) {
-    memset(plan, 0, sizeof *plan);
-    const u64 U = ul.n_unitigs, N = ul.n_entries, n_idx = rg.i1 - rg.i0, nr = rg.n_reads;
-    if (U == 0 || N == 0 || n_rows == 0 || N >= (1ull << 30) || n_rows >= (1ull << 30) || n_idx >= 0xFFFFFFF0ull) return hipErrorInvalidValue;      // (read_paths_impl has answered MDBG_E_CAPACITY or returned before)
-    if (!B->ev0) { GHIP(hipEventCreate(&B->ev0)); GHIP(hipEventCreate(&B->ev1)); }
+hipError_t read_paths_run(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
+                          hipStream_t s, ReadPathResult* out) {
+    memset(out, 0, sizeof *out);
+    const u64 U = ul.n_unitigs, n_idx = rg.i1 - rg.i0, nr = rg.n_reads;
     // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
-    GHIP(B->counters.ensure(RP_C_N * 8));
-    GHIP(B->entry_of_row.ensure(n_rows * 4)); GHIP(B->unitig_of_entry.ensure(N * 4));
-    GHIP(B->code.ensure(n_idx * 4 + 4)); GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
+    GHIP(placement_reserve(P, ul, n_rows, rg, false));
+    GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
     GHIP(B->ordinal.ensure(nr * 8 + 8)); GHIP(B->read_windows.ensure(nr * 4 + 4)); GHIP(B->step_offsets.ensure((nr + 1) * 8));
     GHIP(B->first_window.ensure(n_idx * 4 + 4)); GHIP(B->step_windows.ensure(n_idx * 4 + 4)); GHIP(B->unitig.ensure(n_idx * 4 + 4)); GHIP(B->first_entry.ensure(n_idx * 4 + 4));
     GHIP(B->strand.ensure(n_idx + 4)); GHIP(B->sup_w.ensure(U * 8)); GHIP(B->sup_s.ensure(U * 8));
     if (n_idx) { size_t tb = 0; GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); GHIP(B->tmp.ensure(tb + 256)); }
-    GHIP(hipEventRecord(B->ev0, s));
+    GHIP(B->timer.start(s));
     GHIP(hipMemsetAsync(B->sup_w.p, 0, U * 8, s)); GHIP(hipMemsetAsync(B->sup_s.p, 0, U * 8, s));
-    const PlacementArrays pa{B->entry_of_row.as<u32>(), B->unitig_of_entry.as<u32>(), B->code.as<u32>(), B->counters.as<u64>(), RP_C_N};
-    return placement_begin(pa, ul, index, n_rows, s, plan);
-}
-
-hipError_t read_paths_end(ReadPathBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, hipStream_t s, ReadPathResult* out) {
-    memset(out, 0, sizeof *out);
-    const RpArgs a = args_of(B, ul, rg);
+    PlacementView V;
+    GHIP(placement_queue(P, ul, index, n_rows, rg, false, RP_C_N, placer, s, &V));
+    const RpArgs a = args_of(B, V, ul, rg);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);
         hipLaunchKernelGGL(head_kernel, dim3(gi), dim3(256), 0, s, a);
@@ -188,11 +145,8 @@ hipError_t read_paths_end(ReadPathBuffers* B, const UnitigResult& ul, const Read
     }
     hipLaunchKernelGGL(reads_kernel, dim3(grid_for((u64)a.nr + 1)), dim3(256), 0, s, a);
     GHIP(hipGetLastError());
-    GHIP(hipEventRecord(B->ev1, s));
     u64 h[RP_C_N];
-    GHIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-    GHIP(hipStreamSynchronize(s));
-    if (hipEventElapsedTime(&out->ms, B->ev0, B->ev1) != hipSuccess) { (void)hipGetLastError(); out->ms = 0; }
+    GHIP(B->timer.stop_and_read(h, a.counters, sizeof h, s, &out->ms));
     out->defect = (u32)h[RP_C_DEFECT];
     if (out->defect) return hipSuccess;
     out->n_reads = a.nr; out->n_windows = h[RP_C_WINDOWS]; out->n_placed = h[RP_C_PLACED]; out->n_steps = h[RP_C_STEPS]; out->n_unitigs = a.U;

@@ -28,6 +28,7 @@ struct Results {
              HostRaw<u8> bases; HostRaw<u64> off, unitig; double ms = 0; } contigs;
     struct { StageBuffers<NodeSeqBuffers, node_seq_buffers_create, node_seq_buffers_destroy> buf;                        // its result lives until the next node-sequence call
              HostRaw<u8> bases; HostRaw<u64> off; double ms = 0; } nseq;
+    struct { StageBuffers<PlacementBuffers, placement_buffers_create, placement_buffers_destroy> buf; } placement;          // holds no result: scratch that any read-path, junction or transit call, or EDGES step of a simplify call, overwrites
     struct { StageBuffers<ReadPathBuffers, read_path_buffers_create, read_path_buffers_destroy> buf;                     // its result lives until the next read-path call
              HostRaw<u64> ord, off, supw, sups; HostRaw<u32> rw, fw, nw, unitig, fe; HostRaw<u8> strand; double ms = 0; } rpaths;
     struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call or simplify call with an EDGES step

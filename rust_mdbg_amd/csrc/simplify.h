@@ -6,12 +6,10 @@
 #include "unitigs.h"
 
 struct SimplifyInfo { uint32_t n_compactions, n_rounds_total, n_syncs, junction_defect; float junction_ms; };      // compactions run, their jumping rounds, host synchronisations of the whole call; of the EDGES steps' junction stages: the defect mask (*broken is set with it) and the device time, summed
-// What an MDBG_SIMPLIFY_EDGES step needs beside the graph: the junction stage's buffers, the node table's index column, the whole resident store as a range of
-// reads, and the window placer.  place_windows_kernel lives in the main translation unit beside the table, which this stage does not include: graph_api.inc
-// hands it over as `place`, called between junctions_begin and junctions_end on the same stream.  has_reads == false: nothing is resident, every record is weak.
+// What an MDBG_SIMPLIFY_EDGES step needs beside the graph to run the junction stage (junctions_run): that stage's buffers and the context's placement scratch, the
+// node table's index column, the whole resident store as a range of reads, and the window placer.  has_reads == false: nothing is resident, every record is weak.
 struct SimplifySupport {
-    JunctionBuffers* jb; const uint32_t* index; uint64_t n_rows; ReadPathRange range; bool has_reads;
-    void (*place)(void* ctx, const ReadPathPlan& plan, hipStream_t s); void* ctx;
+    JunctionBuffers* jb; PlacementBuffers* pb; const uint32_t* index; uint64_t n_rows; ReadPathRange range; bool has_reads; WindowPlacer placer;
 };
 // Runs the schedule on the node table and edge list (mdbg_graph_simplify, include/mdbg_hip.h) and leaves the unitig list of the surviving graph in *out, in
 // the same buffers as build_unitigs (valid until the next call of either).  unitigs_removed / nodes_removed / edges_removed: n_steps host entries.  Return value and *broken as build_unitigs.

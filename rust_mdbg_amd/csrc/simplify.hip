@@ -247,10 +247,8 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
             if (!sup->has_reads || E == 0 || UE == 0) continue;      // nothing is strong, or there is no record: the step removes nothing
             if (!edge_alive) { GHIP(B->edge_alive.ensure(E)); GHIP(hipMemsetAsync(B->edge_alive.p, 1, E, s)); }      // (not handed to a compaction before a record goes)
             GHIP(B->strong.ensure(n2x));
-            ReadPathPlan plan; JunctionResult jr;
-            GHIP(junctions_begin(sup->jb, *out, sup->index, sup->n_rows, sup->range, s, &plan));
-            sup->place(sup->ctx, plan, s);
-            GHIP(junctions_end(sup->jb, *out, sup->range, s, &jr));
+            JunctionResult jr;
+            GHIP(junctions_run(sup->jb, sup->pb, *out, sup->index, sup->n_rows, sup->range, sup->placer, s, &jr));
             ++info->n_syncs; info->junction_ms += jr.ms;
             if (jr.defect) { info->junction_defect = jr.defect; return defect(broken); }
             if (jr.n_records != UE) return defect(broken);

@@ -1,15 +1,14 @@
 // transits.hip — the reads that span a unitig end to end, and which repeats they resolve, on the GPU (gfx950).  Definition: include/mdbg_hip.h
 // (mdbg_graph_transits).  Input: the device arrays of a unitig list (unitigs.hip) with its edge records, the store's read offsets and minimizer -> read map, and
-// the per-index place codes of the read paths (read_paths.h: placement_begin builds the row -> entry map, place_windows_kernel writes code[t] = global entry |
-// strand << 31 or NONE), kept in buffers of this stage.  Vertices, pairs and record keys are packed as record_keys.h says.
+// the placement with records (placement.h): unitig_of_entry, the per-index place codes (code[t] = global entry | strand << 31 or NONE) and the edge records in
+// key order, in the context's one placement scratch.  Vertices, pairs and record keys are packed as placement_dev.h says.
 //
 // A transit key (u, p, q) is sorted as the pair hi = u, lo = p << vb | q with vb the bits of a vertex of this list (2 * n_entries - 1); an index that ends no
 // transit carries hi = n_unitigs, behind every key.  Two stable radix sorts, lo first and then hi, over no more bits than the list needs, give the definition's order.
 //
-//   (memset)            the counters, the map, everything that is counted per unitig and per record <- 0
-//   entry_kernel        (read_paths.hip) the row -> entry map, unitig_of_entry
-//   record_key_kernel   (record_keys.h) rkey[r] = the record's key, rec[r] = r;  (rocPRIM) sort_pairs(rkey, rec): stable, so a key's run starts at its smallest record
-//   place_windows_kernel  (place_windows.hip) code[]
+//   (memset)            everything that is counted per unitig and per record <- 0
+//   (placement_queue)   the counters and the map zeroed, entry_kernel, record_key_kernel, sort_pairs(rkey, rec): stable, so a key's run starts at its smallest
+//                       record; place_windows_kernel: code[]
 //   event_kernel        one thread per minimizer index t of the range classifies the pair code[t - 1] -> code[t]: LINK, CROSS (an explained crossing: its key is
 //                       found in the sorted record keys) or BREAK (an unplaced window, a read's first index, a missing crossing); ev[t] = t + 1 unless LINK, else 0.
 //                       The three counts are reduced per workgroup: one atomic each
@@ -27,24 +26,19 @@
 //   verdict_kernel      one thread per unitig: the first rule that applies; n_repeats and n_resolved reduced per workgroup
 //
 // All sums are integers and every position comes from a sort or a scan: two calls give identical arrays.  No loop but the binary searches; the number of
-// launches is fixed.  Per minimizer index of the range: 35 bytes of temporaries (code 4, kind 1, the keys 12 and their second copy 12, which holds ev and last
-// until the first sort writes it, flag 1, pos 4, the rows' direction bits 1) and 38 bytes of row columns, sized for the worst case because their number is known
-// only on the device.  Per edge record 40 bytes of temporaries (the keys and record numbers, both sorted and not, 24; cin and cout 16).  Per unitig 17 bytes of
-// result and 6 of temporaries.
+// launches is fixed.  Per minimizer index of the range, beside the placement's 4: 31 bytes of temporaries (kind 1, the keys 12 and their second copy 12, which
+// holds ev and last until the first sort writes it, flag 1, pos 4, the rows' direction bits 1) and 38 bytes of row columns, sized for the worst case because their
+// number is known only on the device.  Per edge record, beside the placement's 24: cin and cout 16.  Per unitig 17 bytes of result and 6 of temporaries.
 #include <cstring>
 
 #include "transits.h"
-#include "graph_common.h"
-#include "record_keys.h"
+#include "placement_dev.h"
 
 struct TransitBuffers {
-    Buf entry_of_row, unitig_of_entry, code, counters, tmp;
-    Buf rkey, rkey_sorted, rec, rec_sorted;                 // per edge record
-    Buf kind, klo, khi, klo2, khi2, flag, pos, dirs;        // per minimizer index (klo2 holds ev and last until the first sort)
+    Buf kind, klo, khi, klo2, khi2, flag, pos, dirs, tmp;   // per minimizer index (klo2 holds ev and last until the first sort)
     Buf zeroed;                                             // passes, n_in, n_out, strong, cin, cout, bad, self: one memset per call
     Buf verdict, unitig, iu, ie, is, ou, oe, os, irec, orec, count;      // the result (with passes, n_in, n_out of `zeroed`)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~TransitBuffers() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    StageTimer timer;
 };
 
 namespace {
@@ -62,37 +56,20 @@ struct TxArgs {
     u32* unitig; u32* iu; u32* ie; u8* is; u32* ou; u32* oe; u8* os; u32* irec; u32* orec; u64* count;
 };
 
-// the workgroup's counts (256 threads, NC of them per thread): one atomic each on counters[first .. first + NC)
-template <int NC> __device__ inline void block_add(u32 (&cnt)[NC], u64* counters, int first) {
-    __shared__ u32 wsum[NC][4];
-#pragma unroll
-    for (int q = 0; q < NC; ++q) for (int d = 32; d; d >>= 1) cnt[q] += __shfl_down(cnt[q], d, 64);
-    if ((threadIdx.x & 63) == 0) for (int q = 0; q < NC; ++q) wsum[q][threadIdx.x >> 6] = cnt[q];
-    __syncthreads();
-    if (threadIdx.x < NC) {
-        const u32 v = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
-        if (v) atomicAdd((unsigned long long*)(counters + first + threadIdx.x), (unsigned long long)v);
-    }
-}
-__device__ inline void set_defect(const TxArgs& a, u32 bit) { atomicOr((unsigned long long*)(a.counters + RP_C_DEFECT), (unsigned long long)bit); }
-
 __global__ __launch_bounds__(256) void event_kernel(TxArgs a) {
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     u32 cnt[3] = {0, 0, 0};            // adjacent, links, explained crossings
     if (t < a.n_idx) {
         u8 kind = K_BREAK;
         const u32 c = a.code[t];
-        const u64 i = a.i0 + t;
-        if (c != RP_NONE && t > 0 && i > a.roff[a.mread[i]]) {          // (the range starts at a read's first index; the test of cross_kernel, junctions.hip)
-            const u32 pc = a.code[t - 1];
-            if (pc != RP_NONE) {
-                cnt[0] = 1;
-                if (is_link_of_codes(pc, c, a.unitig_of_entry)) { cnt[1] = 1; kind = K_LINK; }
-                else {
-                    const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
-                    const u64 p = lower_bound(a.rkey_sorted, a.R, key);
-                    if (p < a.R && a.rkey_sorted[p] == key) { cnt[2] = 1; kind = K_CROSS; }
-                }
+        u32 pc;
+        if (adjacent_in_read(a.code, a.roff, a.mread, a.i0, t, c, &pc)) {
+            cnt[0] = 1;
+            if (is_link_of_codes(pc, c, a.unitig_of_entry)) { cnt[1] = 1; kind = K_LINK; }
+            else {
+                const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
+                const u64 p = lower_bound(a.rkey_sorted, a.R, key);
+                if (p < a.R && a.rkey_sorted[p] == key) { cnt[2] = 1; kind = K_CROSS; }
             }
         }
         a.kind[t] = kind;
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(256) void transit_kernel(TxArgs a) {
             const u64 e_first = a.offsets[u], e_last = a.offsets[u + 1] - 1;
             const bool walks_all = a.unitig_of_entry[ex2] == u && cx2 >> 31 == s && t - t0 == e_last - e_first + 1 &&
                                    (s ? ey == e_last && ex2 == e_first : ey == e_first && ex2 == e_last);
-            if (!walks_all) set_defect(a, TX_DEFECT_SHAPE);
+            if (!walks_all) set_defect(a.counters, TX_DEFECT_SHAPE);
             else {
                 const u32 p = s ? vertex_of_code(cy2) ^ 1u : vertex_of_code(cx), q = s ? vertex_of_code(cx) ^ 1u : vertex_of_code(cy2);
                 lo = (u64)p << a.vb | q; hi = u; cnt[0] = 1;
@@ -151,7 +128,7 @@ __global__ __launch_bounds__(256) void row_kernel(TxArgs a) {
     const u64 in_pair = pair_of(p, v_first), out_pair = pair_of(v_last, q);
     const u64 in_key = key_of_pair(p, v_first), out_key = key_of_pair(v_last, q);
     const u64 si = lower_bound(a.rkey_sorted, a.R, in_key), so = lower_bound(a.rkey_sorted, a.R, out_key);
-    if (si >= a.R || so >= a.R || a.rkey_sorted[si] != in_key || a.rkey_sorted[so] != out_key) { set_defect(a, TX_DEFECT_SHAPE); return; }
+    if (si >= a.R || so >= a.R || a.rkey_sorted[si] != in_key || a.rkey_sorted[so] != out_key) { set_defect(a.counters, TX_DEFECT_SHAPE); return; }
     const u32 ri = a.rec_sorted[si], ro = a.rec_sorted[so];
     const u32 di = in_pair != in_key, dout = out_pair != out_key;
     a.unitig[d] = u;
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(256) void ends_kernel(TxArgs a) {
     if (a.n1[r] == a.n2[r]) a.self[a.n1[r]] = 1;
     if (i > 0 && a.rkey_sorted[i - 1] == key) return;
     const u32 x = (u32)(key >> 32), y = (u32)key;
-    if ((x >> 1) >= a.N || (y >> 1) >= a.N) { set_defect(a, JX_DEFECT_EDGE); return; }
+    if ((x >> 1) >= a.N || (y >> 1) >= a.N) { set_defect(a.counters, JX_DEFECT_EDGE); return; }
     const bool own_mirror = mirror_of_pair(key) == key;
     const u32 ux = a.unitig_of_entry[x >> 1], uy = a.unitig_of_entry[y >> 1];
     const u32 first_x = (u32)(a.offsets[ux] << 1), last_x = (u32)((a.offsets[ux + 1] - 1) << 1);
@@ -190,7 +167,7 @@ __global__ __launch_bounds__(256) void check_kernel(TxArgs a) {
     const u64 d = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= a.n_idx || a.counters[RP_C_DEFECT] || d >= a.counters[TX_C_TRANSITS] || a.count[d] < a.min_support) return;      // (after a defect a row may not be written)
     const u32 dirs = a.dirs[d];
-    if (a.irec[d] >= a.R || a.orec[d] >= a.R || a.unitig[d] >= a.U) { set_defect(a, TX_DEFECT_SHAPE); return; }
+    if (a.irec[d] >= a.R || a.orec[d] >= a.R || a.unitig[d] >= a.U) { set_defect(a.counters, TX_DEFECT_SHAPE); return; }
     if (a.cin[2 * (u64)a.irec[d] + (dirs & 1u)] != 1u || a.cout[2 * (u64)a.orec[d] + (dirs >> 1)] != 1u) a.bad[a.unitig[d]] = 1;
 }
 
@@ -222,13 +199,13 @@ Zeroed zeroed_of(u64 U, u64 R) {
     return z;
 }
 
-TxArgs args_of(TransitBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, u64 min_support) {
+TxArgs args_of(TransitBuffers* B, const PlacementView& V, const UnitigResult& ul, const ReadPathRange& rg, u64 min_support) {
     TxArgs a; memset(&a, 0, sizeof a);
-    a.U = ul.n_unitigs; a.N = ul.n_entries; a.R = ul.edges.n; a.offsets = ul.offsets; a.unitig_of_entry = B->unitig_of_entry.as<u32>(); a.n1 = ul.edges.n1; a.n2 = ul.edges.n2;
-    a.rkey_sorted = B->rkey_sorted.as<u64>(); a.rec_sorted = B->rec_sorted.as<u32>();
+    a.U = ul.n_unitigs; a.N = ul.n_entries; a.R = V.R; a.offsets = ul.offsets; a.unitig_of_entry = V.unitig_of_entry; a.n1 = ul.edges.n1; a.n2 = ul.edges.n2;
+    a.rkey_sorted = V.rkey_sorted; a.rec_sorted = V.rec_sorted;
     a.roff = rg.roff; a.mread = rg.mread; a.i0 = rg.i0; a.n_idx = rg.i1 - rg.i0;
-    a.code = B->code.as<u32>(); a.kind = B->kind.as<u8>(); a.ev = B->klo2.as<u32>(); a.last = a.ev + a.n_idx + 1; a.klo = B->klo.as<u64>(); a.khi = B->khi.as<u32>();
-    a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.dirs = B->dirs.as<u8>(); a.counters = B->counters.as<u64>();
+    a.code = V.code; a.kind = B->kind.as<u8>(); a.ev = B->klo2.as<u32>(); a.last = a.ev + a.n_idx + 1; a.klo = B->klo.as<u64>(); a.khi = B->khi.as<u32>();
+    a.flag = B->flag.as<u8>(); a.pos = B->pos.as<u32>(); a.dirs = B->dirs.as<u8>(); a.counters = V.counters;
     a.vb = bits_of(2 * a.N - 1); a.min_support = min_support;
     const Zeroed z = zeroed_of(a.U, a.R);
     char* zp = B->zeroed.as<char>();
@@ -245,48 +222,33 @@ TxArgs args_of(TransitBuffers* B, const UnitigResult& ul, const ReadPathRange& r
 TransitBuffers* transit_buffers_create() { return new TransitBuffers(); }
 void transit_buffers_destroy(TransitBuffers* b) { delete b; }
 
-hipError_t transits_begin(TransitBuffers* B, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, hipStream_t s, ReadPathPlan* plan) {
-    memset(plan, 0, sizeof *plan);
-    const u64 U = ul.n_unitigs, N = ul.n_entries, R = ul.edges.n, n_idx = rg.i1 - rg.i0;
-    if (U == 0 || N == 0 || n_rows == 0 || U > N || N >= (1ull << 30) || n_rows >= (1ull << 30) || n_idx >= 0xFFFFFFF0ull || R >= 0xFFFFFFF0ull) return hipErrorInvalidValue;      // (transits_impl has answered MDBG_E_CAPACITY or returned before)
-    if (!B->ev0) { GHIP(hipEventCreate(&B->ev0)); GHIP(hipEventCreate(&B->ev1)); }
+hipError_t transits_run(TransitBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, u64 min_support,
+                        const WindowPlacer& placer, hipStream_t s, TransitResult* out) {
+    memset(out, 0, sizeof *out);
+    const u64 U = ul.n_unitigs, R = ul.edges.n, n_idx = rg.i1 - rg.i0;
+    if (U > ul.n_entries) return hipErrorInvalidValue;
     // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
+    GHIP(placement_reserve(P, ul, n_rows, rg, true));
     const Zeroed z = zeroed_of(U, R);
-    GHIP(B->counters.ensure(TX_C_N * 8)); GHIP(B->zeroed.ensure(z.bytes)); GHIP(B->verdict.ensure(U + 4));
-    GHIP(B->entry_of_row.ensure(n_rows * 4)); GHIP(B->unitig_of_entry.ensure(N * 4)); GHIP(B->code.ensure(n_idx * 4 + 4));
-    GHIP(B->rkey.ensure(R * 8 + 8)); GHIP(B->rkey_sorted.ensure(R * 8 + 8)); GHIP(B->rec.ensure(R * 4 + 4)); GHIP(B->rec_sorted.ensure(R * 4 + 4));
+    GHIP(B->zeroed.ensure(z.bytes)); GHIP(B->verdict.ensure(U + 4));
     GHIP(B->kind.ensure(n_idx + 4)); GHIP(B->klo.ensure(n_idx * 8 + 8)); GHIP(B->klo2.ensure(n_idx * 8 + 8)); GHIP(B->khi.ensure(n_idx * 4 + 4)); GHIP(B->khi2.ensure(n_idx * 4 + 4));
     GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4)); GHIP(B->dirs.ensure(n_idx + 4));
     GHIP(B->unitig.ensure(n_idx * 4 + 4)); GHIP(B->iu.ensure(n_idx * 4 + 4)); GHIP(B->ie.ensure(n_idx * 4 + 4)); GHIP(B->is.ensure(n_idx + 4));
     GHIP(B->ou.ensure(n_idx * 4 + 4)); GHIP(B->oe.ensure(n_idx * 4 + 4)); GHIP(B->os.ensure(n_idx + 4));
     GHIP(B->irec.ensure(n_idx * 4 + 4)); GHIP(B->orec.ensure(n_idx * 4 + 4)); GHIP(B->count.ensure(n_idx * 8 + 8));
-    {   // the largest temporary of the rocPRIM calls, so that `tmp` does not grow between them
+    if (n_idx) {   // the largest temporary of the stage's rocPRIM calls, so that `tmp` does not grow between them
         size_t tb = 0, most = 0;
-        if (R) { GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->rkey.as<u64>(), B->rkey_sorted.as<u64>(), B->rec.as<u32>(), B->rec_sorted.as<u32>(), (size_t)R, 0u, 64u, s)); most = tb; }
-        if (n_idx) {
-            GHIP(rocprim::inclusive_scan(nullptr, tb, B->klo2.as<u32>(), B->klo2.as<u32>(), (size_t)n_idx, rocprim::maximum<u32>(), s)); if (tb > most) most = tb;
-            GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->klo.as<u64>(), B->klo2.as<u64>(), B->khi.as<u32>(), B->khi2.as<u32>(), (size_t)n_idx, 0u, 64u, s)); if (tb > most) most = tb;
-            GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->khi2.as<u32>(), B->khi.as<u32>(), B->klo2.as<u64>(), B->klo.as<u64>(), (size_t)n_idx, 0u, 32u, s)); if (tb > most) most = tb;
-            GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); if (tb > most) most = tb;
-        }
+        GHIP(rocprim::inclusive_scan(nullptr, most, B->klo2.as<u32>(), B->klo2.as<u32>(), (size_t)n_idx, rocprim::maximum<u32>(), s));
+        GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->klo.as<u64>(), B->klo2.as<u64>(), B->khi.as<u32>(), B->khi2.as<u32>(), (size_t)n_idx, 0u, 64u, s)); if (tb > most) most = tb;
+        GHIP(rocprim::radix_sort_pairs(nullptr, tb, B->khi2.as<u32>(), B->khi.as<u32>(), B->klo2.as<u64>(), B->klo.as<u64>(), (size_t)n_idx, 0u, 32u, s)); if (tb > most) most = tb;
+        GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); if (tb > most) most = tb;
         GHIP(B->tmp.ensure(most + 256));
     }
-    GHIP(hipEventRecord(B->ev0, s));
+    GHIP(B->timer.start(s));
     GHIP(hipMemsetAsync(B->zeroed.p, 0, z.bytes, s));
-    const PlacementArrays pa{B->entry_of_row.as<u32>(), B->unitig_of_entry.as<u32>(), B->code.as<u32>(), B->counters.as<u64>(), TX_C_N};
-    GHIP(placement_begin(pa, ul, index, n_rows, s, plan));
-    if (R) {
-        const RecordKeyArgs rk{U, R, ul.offsets, ul.edges.n1, ul.edges.o1, ul.edges.n2, ul.edges.o2, B->rkey.as<u64>(), B->rec.as<u32>(), B->counters.as<u64>() + RP_C_DEFECT, JX_DEFECT_EDGE};
-        hipLaunchKernelGGL(record_key_kernel, dim3(grid_for(R)), dim3(256), 0, s, rk);
-        GHIP(hipGetLastError());
-        GHIP(sort_pairs(B->tmp, (const u64*)rk.rkey, B->rkey_sorted.as<u64>(), (const u32*)rk.rec, B->rec_sorted.as<u32>(), (size_t)R, 0u, 64u, s));
-    }
-    return hipSuccess;
-}
-
-hipError_t transits_end(TransitBuffers* B, const UnitigResult& ul, const ReadPathRange& rg, u64 min_support, hipStream_t s, TransitResult* out) {
-    memset(out, 0, sizeof *out);
-    const TxArgs a = args_of(B, ul, rg, min_support);
+    PlacementView V;
+    GHIP(placement_queue(P, ul, index, n_rows, rg, true, TX_C_N, placer, s, &V));
+    const TxArgs a = args_of(B, V, ul, rg, min_support);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);
         const size_t n = (size_t)a.n_idx;
@@ -311,11 +273,8 @@ hipError_t transits_end(TransitBuffers* B, const UnitigResult& ul, const ReadPat
     if (a.n_idx) hipLaunchKernelGGL(check_kernel, dim3(grid_for(a.n_idx)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(verdict_kernel, dim3(grid_for(a.U)), dim3(256), 0, s, a);
     GHIP(hipGetLastError());
-    GHIP(hipEventRecord(B->ev1, s));
     u64 h[TX_C_N];
-    GHIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-    GHIP(hipStreamSynchronize(s));
-    if (hipEventElapsedTime(&out->ms, B->ev0, B->ev1) != hipSuccess) { (void)hipGetLastError(); out->ms = 0; }
+    GHIP(B->timer.stop_and_read(h, a.counters, sizeof h, s, &out->ms));
     out->defect = (u32)h[RP_C_DEFECT];
     if (out->defect) return hipSuccess;
     out->n_reads = rg.n_reads; out->n_crossings = h[TX_C_ADJACENT] - h[TX_C_LINKS]; out->n_explained = h[TX_C_EXPLAINED]; out->n_passes = h[TX_C_PASSES];
