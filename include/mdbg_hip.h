@@ -767,6 +767,21 @@ int mdbg_synth_reads_device(mdbg_ctx* ctx, const mdbg_synth_params* sp, uint64_t
  * out[2] = list entries, out[3] = hashes packed. */
 int mdbg_dbg_segments_ms(mdbg_ctx* ctx, uint32_t world, uint32_t skip, const uint64_t* counts, const uint32_t* d_lists, double* out);
 
+/* ---- test hooks ------------------------------------------------------------------------------------
+ * MDBG_GUARD (environment, read once): every device block of the library is an allocation of its own, exactly as large as the stage asked for, poisoned
+ * with 0xA5 and fenced by two bands of 4096 bytes, one in front and one behind, inside the same allocation.  A kernel that writes up to 4 KiB outside its buffer
+ * damages a band instead of a neighbour or the slack of the buffer.  Writes only: a read outside a block leaves no trace.  Unset, nothing changes.
+ * mdbg_guard_check: waits for the device, compares both bands of every live block (and repairs a damaged one, so that it counts once) and returns the number of
+ * damaged bands found so far, those found when a block was given back included; *n_blocks / *n_bytes <- live blocks and payload bytes looked at (either may be
+ * NULL).  0 and zeros when MDBG_GUARD is unset.
+ * mdbg_guard_report: the first violation as text, "block of 1234 bytes: byte +3 behind the end (5 damaged)" or "...: byte -8 in front (8 damaged)": the size names the
+ * request, the offset the damaged byte next to the payload.  "" when there is none.  Valid until the next call.
+ * mdbg_guard_selftest: plants one byte behind the end and one in front of a 1000-byte block of its own (inside that block's allocation), expects each to be counted
+ * once and named, and takes both out of the count again.  0 = the guard works, -1 = MDBG_GUARD is unset, > 0 = the step that failed. */
+uint64_t mdbg_guard_check(uint64_t* n_blocks, uint64_t* n_bytes);
+const char* mdbg_guard_report(void);
+int mdbg_guard_selftest(void);
+
 #ifdef __cplusplus
 }
 #endif

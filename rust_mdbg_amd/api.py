@@ -320,7 +320,8 @@ EXPORTS = ["mdbg_abi_version", "mdbg_build_flags", "mdbg_create", "mdbg_destroy"
            "mdbg_graph_simplify", "mdbg_graph_simplify_device", "mdbg_simplify_edges_removed", "mdbg_graph_components", "mdbg_graph_components_device", "mdbg_graph_contigs", "mdbg_graph_contigs_device", "mdbg_kept_reads", "mdbg_contigs_ms", "mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms", "mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms",
            "mdbg_graph_junctions", "mdbg_graph_junctions_device", "mdbg_junctions_ms", "mdbg_graph_transits", "mdbg_graph_transits_device", "mdbg_transits_ms",
            "mdbg_ingest_batch_packed", "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device", "mdbg_query_batch", "mdbg_owner_lists", "mdbg_sketch_commit_listed", "mdbg_mark", "mdbg_rewind", "mdbg_set_lmer_filter",
-           "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms"]
+           "mdbg_release_cached_memory", "mdbg_host_alloc", "mdbg_host_free", "mdbg_host_is_pinned", "mdbg_dbg_segments_ms",
+           "mdbg_guard_check", "mdbg_guard_report", "mdbg_guard_selftest"]
 
 
 def lib_path():
@@ -353,6 +354,10 @@ def load_library():
     L.mdbg_host_free.restype = None
     L.mdbg_host_free.argtypes = [vp]
     L.mdbg_host_is_pinned.argtypes = [vp]
+    L.mdbg_guard_check.restype = u64
+    L.mdbg_guard_check.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+    L.mdbg_guard_report.restype = C.c_char_p
+    L.mdbg_guard_selftest.restype = C.c_int
     L.mdbg_create.restype = vp
     L.mdbg_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_int)]
     L.mdbg_destroy.restype = None
@@ -448,7 +453,31 @@ def load_library():
 
 def release_cached_memory():
     """hands the device blocks the library keeps for reuse back to the runtime; returns the number of bytes released (include/mdbg_hip.h)"""
-    return int(load_library().mdbg_release_cached_memory())
+    n = int(load_library().mdbg_release_cached_memory())
+    guard_check()
+    return n
+
+
+# MDBG_GUARD (test hook, include/mdbg_hip.h): every device block lies between two bands that nobody may write.  With it in the environment at import every library call
+# of a context is followed by a check of all bands, so that a damaged band is pinned to the call that did it, not to a later free.  GUARD_SEEN: checks made, and the most
+# live blocks / payload bytes one of them looked at (tests/test_gpu_guard.py prints them: a run that checked nothing must not pass).
+GUARD = "MDBG_GUARD" in os.environ
+GUARD_SEEN = {"calls": 0, "blocks": 0, "bytes": 0, "violations": 0}
+
+
+def guard_check():
+    """no-op unless MDBG_GUARD was set at import; AssertionError(report) as soon as a band is damaged"""
+    if not GUARD:
+        return
+    L = load_library()
+    nb, by = C.c_uint64(0), C.c_uint64(0)
+    bad = L.mdbg_guard_check(C.byref(nb), C.byref(by))
+    GUARD_SEEN["calls"] += 1
+    GUARD_SEEN["blocks"] = max(GUARD_SEEN["blocks"], int(nb.value))
+    GUARD_SEEN["bytes"] = max(GUARD_SEEN["bytes"], int(by.value))
+    if bad > GUARD_SEEN["violations"]:         # (the count never goes down: what has been raised once is not raised again by the calls that follow, a close() on the way out among them)
+        GUARD_SEEN["violations"] = int(bad)
+        raise AssertionError("MDBG_GUARD: %d damaged band(s); first: %s" % (bad, L.mdbg_guard_report().decode()))
 
 
 def _np(ptr, n, dtype):
@@ -489,6 +518,7 @@ class Mdbg:
         self.k = k
 
     def _chk(self, e):
+        guard_check()
         if e != 0:
             raise MdbgError(e, (self.L.mdbg_last_error(self.h) or self.L.mdbg_strerror(e)).decode())
 
@@ -949,6 +979,7 @@ class Mdbg:
         if getattr(self, "h", None):
             self.L.mdbg_destroy(self.h)
             self.h = None
+            guard_check()
 
     def __enter__(self):
         return self

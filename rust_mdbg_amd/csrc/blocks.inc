@@ -57,8 +57,116 @@ struct BlockCache {
     }
 };
 inline BlockCache& block_cache() { static BlockCache* const c = new BlockCache(); return *c; }     // (never destroyed: blocks may be returned by static destructors)
+
+// ---- MDBG_GUARD (test hook): a fence around every block -------------------------------------------------------------------------------------
+// No test that compares a stage's outputs can see a kernel that writes a few elements outside the buffer the host sized for it: the write lands in the slack of
+// Buf::ensure / DevBuf::ensure, or in the up-to-twice-the-request of a cached block.  With MDBG_GUARD set every block is an allocation of its own, G + bytes + G, the
+// payload exactly as large as the request (whoever adds slack asks mdbg_guard_mode() and adds none), poisoned like MDBG_POISON's, between two bands of
+// BAND bytes that nobody may touch.  G = one workgroup's widest row of stores (256 lanes x 16 B); it keeps the alignment of the handed pointer, and both bands belong to
+// the allocation, so what the guard catches has damaged nothing.  The bands are compared on every mdbg_guard_check and when the block is given back.  Writes only:
+// a read outside a block leaves no trace.
+struct GuardState {
+    static constexpr size_t G = 4096;
+    static constexpr int BAND = 0x5C;
+    struct Blk { size_t bytes; int dev; };
+    std::mutex mu; std::map<uintptr_t, Blk> live;      // base of the allocation -> its payload (handed out: base + G)
+    uint64_t violations = 0; std::string first;
+    // compares the host copy of one band with its pattern (mu held, the block's device current and idle).  A damaged band is counted once: it is reported and filled again.
+    void judge_band(const unsigned char* h, uintptr_t band, const Blk& b, bool front) {
+        size_t n_bad = 0, lo = G, hi = 0;
+        for (size_t i = 0; i < G; ++i) if (h[i] != (unsigned char)BAND) { ++n_bad; lo = std::min(lo, i); hi = i; }
+        if (!n_bad) return;
+        ++violations;
+        if (first.empty()) {         // the damaged byte next to the payload names the overrun: the first one behind the end, the last one in front
+            char t[160];
+            if (front) snprintf(t, sizeof t, "block of %zu bytes: byte -%zu in front (%zu damaged)", b.bytes, G - hi, n_bad);
+            else snprintf(t, sizeof t, "block of %zu bytes: byte +%zu behind the end (%zu damaged)", b.bytes, lo, n_bad);
+            first = t;
+        }
+        if (hipMemset((void*)band, BAND, G) != hipSuccess) (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+    }
+    // one block, when it is given back
+    void check_block(uintptr_t base, const Blk& b) {
+        int cur = 0; (void)hipGetDevice(&cur);
+        if (b.dev != cur) (void)hipSetDevice(b.dev);
+        (void)hipDeviceSynchronize();
+        unsigned char h[2 * G];
+        if (hipMemcpy(h, (const void*)base, G, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(h + G, (const void*)(base + G + b.bytes), G, hipMemcpyDeviceToHost) == hipSuccess) {
+            judge_band(h, base, b, true); judge_band(h + G, base + G + b.bytes, b, false);
+        } else (void)hipGetLastError();
+        if (b.dev != cur) (void)hipSetDevice(cur);
+    }
+    // every live block (mdbg_guard_check runs after every library call of a guarded test): per device one wait, the bands queued into one page-locked buffer, one more wait
+    unsigned char* stage = nullptr; size_t stage_cap = 0;
+    void check_all(uint64_t* n_blocks, uint64_t* n_bytes) {
+        const size_t need = live.size() * 2 * G;
+        if (need > stage_cap) {
+            if (stage) (void)hipHostFree(stage);
+            stage = nullptr; stage_cap = 0;
+            if (hipHostMalloc((void**)&stage, 2 * need, hipHostMallocDefault) == hipSuccess) stage_cap = 2 * need; else (void)hipGetLastError();
+        }
+        int cur = 0; (void)hipGetDevice(&cur);
+        std::vector<int> devs;
+        for (const auto& b : live) { *n_blocks += 1; *n_bytes += b.second.bytes; if (std::find(devs.begin(), devs.end(), b.second.dev) == devs.end()) devs.push_back(b.second.dev); }
+        if (need > stage_cap) { for (const auto& b : live) check_block(b.first, b.second); return; }
+        for (int dev : devs) {
+            if (dev != cur) (void)hipSetDevice(dev);
+            (void)hipDeviceSynchronize();
+            bool ok = true; size_t i = 0;
+            for (const auto& b : live) {
+                if (b.second.dev != dev) continue;
+                ok = ok && hipMemcpyAsync(stage + i, (const void*)b.first, G, hipMemcpyDeviceToHost, nullptr) == hipSuccess
+                        && hipMemcpyAsync(stage + i + G, (const void*)(b.first + G + b.second.bytes), G, hipMemcpyDeviceToHost, nullptr) == hipSuccess;
+                i += 2 * G;
+            }
+            ok = ok && hipStreamSynchronize(nullptr) == hipSuccess;
+            i = 0;
+            for (const auto& b : live) {
+                if (b.second.dev != dev) continue;
+                if (ok) { judge_band(stage + i, b.first, b.second, true); judge_band(stage + i + G, b.first + G + b.second.bytes, b.second, false); }
+                i += 2 * G;
+            }
+            if (!ok) (void)hipGetLastError();
+            if (dev != cur) (void)hipSetDevice(cur);
+        }
+    }
+};
+inline GuardState& guard_state() { static GuardState* const g = new GuardState(); return *g; }
+hipError_t guard_alloc(void** p, size_t bytes, size_t* cap) {
+    constexpr size_t G = GuardState::G;
+    int dev = 0; (void)hipGetDevice(&dev);
+    char* base = nullptr;
+    hipError_t e = hipMalloc((void**)&base, G + bytes + G);
+    if (e != hipSuccess) return e;
+    e = hipMemset(base, GuardState::BAND, G);
+    if (e == hipSuccess && bytes) e = hipMemset(base + G, 0xA5, bytes);
+    if (e == hipSuccess) e = hipMemset(base + G + bytes, GuardState::BAND, G);
+    if (e == hipSuccess) e = hipDeviceSynchronize();      // (the fills run on the null stream, which the contexts' streams do not wait for)
+    if (e != hipSuccess) { (void)hipFree(base); return e; }
+    GuardState& g = guard_state();
+    { std::lock_guard<std::mutex> l(g.mu); g.live[(uintptr_t)base] = GuardState::Blk{bytes, dev}; }
+    *p = base + G; *cap = bytes;
+    return hipSuccess;
+}
+void guard_free(void* p) {      // in this order: wait for the device (check_block), compare both bands, forget the block, hipFree
+    GuardState& g = guard_state();
+    const uintptr_t base = (uintptr_t)p - GuardState::G;
+    {
+        std::lock_guard<std::mutex> l(g.mu);
+        auto it = g.live.find(base);
+        if (it == g.live.end()) { ++g.violations; if (g.first.empty()) g.first = "a block was given back that the guard did not hand out"; return; }
+        g.check_block(base, it->second);
+        g.live.erase(it);
+    }
+    (void)hipFree((void*)base);
+}
 }  // namespace
+// read once; the places that add slack to a request (Buf::ensure in graph_common.h, both attempts of DevBuf::ensure) ask it; keep_batch (store.inc) asks for exactly its sizes
+// already.  Hidden: not an export of the library.
+__attribute__((visibility("hidden"))) bool mdbg_guard_mode() { static const bool on = getenv("MDBG_GUARD") != nullptr; return on; }
 hipError_t mdbg_block_alloc(void** p, size_t bytes, size_t* cap) {
+    if (mdbg_guard_mode()) return guard_alloc(p, bytes, cap);
     int dev = 0; (void)hipGetDevice(&dev);
     const double t0 = now_ms();
     bool cached = true;
@@ -82,6 +190,7 @@ hipError_t mdbg_block_alloc(void** p, size_t bytes, size_t* cap) {
 }
 void mdbg_block_free(void* p, size_t cap) {
     if (!p) return;
+    if (mdbg_guard_mode()) { guard_free(p); return; }
     int dev = 0; (void)hipGetDevice(&dev);
     // what hipFree guarantees and the callers rely on: nothing on the device still uses the block when somebody else gets it
     if (cap >= BlockCache::MIN_BLOCK) (void)hipDeviceSynchronize();
@@ -96,8 +205,9 @@ struct DevBuf {
         if (bytes <= cap) return hipSuccess;
         size_t ncap = 0;
         void* np = nullptr;
-        hipError_t e = mdbg_block_alloc(&np, bytes + bytes / 4 + 256, &ncap);
-        if (e != hipSuccess) { (void)hipGetLastError(); e = mdbg_block_alloc(&np, bytes + 256, &ncap); if (e != hipSuccess) return e; }
+        const bool exact = mdbg_guard_mode();       // MDBG_GUARD: no slack, so that the first byte behind what the stage asked for is a band's
+        hipError_t e = mdbg_block_alloc(&np, exact ? bytes : bytes + bytes / 4 + 256, &ncap);
+        if (e != hipSuccess) { (void)hipGetLastError(); e = mdbg_block_alloc(&np, exact ? bytes : bytes + 256, &ncap); if (e != hipSuccess) return e; }
         if (p && keep) { e = hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, s); if (e != hipSuccess) { mdbg_block_free(np, ncap); return e; } (void)hipStreamSynchronize(s); }
         if (p) mdbg_block_free(p, cap);      // (every user of the old block was ordered before the copy or is done: callers grow a buffer only between its uses)
         p = np; cap = ncap;
@@ -198,4 +308,51 @@ int mdbg_host_is_pinned(const void* p) {
     return it && it->second.in_use && it->second.state == 1 ? 1 : 0;
 }
 uint64_t mdbg_release_cached_memory(void) { (void)host_cache_trim(); return (uint64_t)block_cache().trim(); }
+// ---- test hooks of MDBG_GUARD (include/mdbg_hip.h) ----
+uint64_t mdbg_guard_check(uint64_t* n_blocks, uint64_t* n_bytes) {
+    uint64_t nb = 0, by = 0, v = 0;
+    if (mdbg_guard_mode()) {
+        GuardState& g = guard_state();
+        std::lock_guard<std::mutex> l(g.mu);
+        g.check_all(&nb, &by);
+        v = g.violations;
+    }
+    if (n_blocks) *n_blocks = nb;
+    if (n_bytes) *n_bytes = by;
+    return v;
+}
+const char* mdbg_guard_report(void) {
+    if (!mdbg_guard_mode()) return "";
+    GuardState& g = guard_state();
+    std::lock_guard<std::mutex> l(g.mu);
+    static std::string out;          // (the text outlives the lock; the first report only ever changes from empty to set, the self-test aside)
+    out = g.first;
+    return out.c_str();
+}
+// A check that cannot fail is no check: one byte behind the end of a 1000-byte block and one byte in front of it, both inside the block's own allocation, have
+// to be counted and named.  The two planted violations are taken out of the count again.  0 = the guard works; -1 = guard mode is off; > 0 = the step that failed.
+int mdbg_guard_selftest(void) {
+    if (!mdbg_guard_mode()) { fprintf(stderr, "mdbg_guard_selftest: MDBG_GUARD is not set\n"); return -1; }
+    GuardState& g = guard_state();
+    void* p = nullptr; size_t cap = 0;
+    if (mdbg_block_alloc(&p, 1000, &cap) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    uint64_t v0 = 0; std::string kept;
+    { v0 = mdbg_guard_check(nullptr, nullptr); std::lock_guard<std::mutex> l(g.mu); kept.swap(g.first); }
+    int bad = cap == 1000 ? 0 : 2;
+    uint64_t nb = 0, by = 0;
+    if (!bad && (hipMemset(p, 0, 1001) != hipSuccess || mdbg_guard_check(&nb, &by) != v0 + 1 || nb < 1 || by < 1000)) bad = 3;
+    if (!bad && strstr(mdbg_guard_report(), "block of 1000 bytes: byte +0 behind the end") == nullptr) bad = 4;
+    { std::lock_guard<std::mutex> l(g.mu); g.first.clear(); }
+    if (!bad && (hipMemset((char*)p - 1, 0, 1) != hipSuccess || mdbg_guard_check(nullptr, nullptr) != v0 + 2)) bad = 5;
+    if (!bad && strstr(mdbg_guard_report(), "block of 1000 bytes: byte -1 in front") == nullptr) bad = 6;
+    if (!bad && mdbg_guard_check(nullptr, nullptr) != v0 + 2) bad = 7;          // an intact block adds nothing
+    // both bands as they were, whatever happened above, so that giving the block back counts nothing
+    if (hipMemset((char*)p - GuardState::G, GuardState::BAND, GuardState::G) != hipSuccess || hipMemset((char*)p + 1000, GuardState::BAND, GuardState::G) != hipSuccess) { (void)hipGetLastError(); if (!bad) bad = 8; }
+    (void)hipDeviceSynchronize();
+    { std::lock_guard<std::mutex> l(g.mu); g.violations = v0; g.first.swap(kept); }
+    mdbg_block_free(p, cap);
+    if (!bad && mdbg_guard_check(nullptr, nullptr) != v0) bad = 9;
+    (void)hipGetLastError();
+    return bad;
+}
 }  // extern "C"

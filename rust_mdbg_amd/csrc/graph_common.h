@@ -12,6 +12,8 @@ typedef uint8_t u8; typedef uint16_t u16; typedef uint32_t u32; typedef uint64_t
 // are kept and handed out again.  *cap <- usable size (>= bytes).
 hipError_t mdbg_block_alloc(void** p, size_t bytes, size_t* cap);
 void mdbg_block_free(void* p, size_t cap);
+// MDBG_GUARD (test hook, blocks.inc): every block is handed out exactly as large as it was asked for, between two bands that are checked for writes; whoever adds slack to a request asks this first
+__attribute__((visibility("hidden"))) bool mdbg_guard_mode();
 
 // the one error convention of the graph stages: every host function returns the failing HIP error (a broken invariant has its own out-parameter, unitigs.h)
 #define GHIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
@@ -26,7 +28,7 @@ struct Buf {
         if (bytes <= cap) return hipSuccess;
         if (p) mdbg_block_free(p, cap);
         p = nullptr; cap = 0;
-        return mdbg_block_alloc(&p, bytes + bytes / 8 + 256, &cap);
+        return mdbg_block_alloc(&p, mdbg_guard_mode() ? bytes : bytes + bytes / 8 + 256, &cap);
     }
     template <class T> T* as() const { return (T*)p; }
 };
