@@ -1,9 +1,7 @@
 """Connected components of the unitig graph and the small-component step without a GPU: the checker (tests/components_restatement.py) is itself
 checked on hand-made graphs with the answer written out and, on the fuzz graphs, against a flood fill over the NODE-level edge records that knows
 nothing of unitigs; the constants and the ctypes mirror are checked against the header.  The GPU side is tests/test_gpu_components.py."""
-import ctypes as C
 import os
-import subprocess
 
 import pytest
 
@@ -26,21 +24,6 @@ def test_constants():
     assert {"mdbg_graph_components", "mdbg_graph_components_device"} <= set(api.EXPORTS)
     assert [f for f, _, _ in api.COMPONENT_FIELDS] == [f for f, _ in api.ComponentList._fields_[2:]]
     assert all(s[0] != K for s in api.MAGIC_SIMPLIFY_STEPS)                   # the default schedule is what it was
-
-
-def test_component_list_mirror_matches_the_c_compiler(tmp_path):
-    """size and field offsets of mdbg_component_list as gcc lays out the header's own definition (the pattern of test_abi_exports)"""
-    from rust_mdbg_amd import api
-    fs = [f for f, _ in api.ComponentList._fields_]
-    body = 'printf("size %zu\\n", sizeof(mdbg_component_list));\n' + "".join('printf("%s %%zu\\n", offsetof(mdbg_component_list, %s));\n' % (f, f) for f in fs)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mdbg_hip.h"\nint main(void) {\n' + body + 'return 0; }\n')
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
-    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip().split("\n"))
-    assert int(got["size"]) == C.sizeof(api.ComponentList) == 9 * 8
-    for f in fs:
-        assert int(got[f]) == getattr(api.ComponentList, f).offset, f
 
 
 def hand_components(abund, edges, length=None):

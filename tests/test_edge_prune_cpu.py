@@ -153,7 +153,6 @@ def test_tips_and_bubbles_decide_on_a_graph_with_dead_arcs():
 
 # ---- the C side ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_python_mirror_and_the_c99_header(tmp_path):
-    import ctypes as C
     from rust_mdbg_amd import api
     assert api.MDBG_SIMPLIFY_EDGES == EDGES == 8 and "mdbg_simplify_edges_removed" in api.EXPORTS and hasattr(api.load_library(), "mdbg_simplify_edges_removed")
     arr, n = api.simplify_steps([(api.MDBG_SIMPLIFY_EDGES, 2, 0)])
@@ -163,10 +162,10 @@ def test_python_mirror_and_the_c99_header(tmp_path):
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mdbg_hip.h"\n'
                    "int main(void) {\n    mdbg_simplify_step st = {MDBG_SIMPLIFY_EDGES, 2, 0};\n    const uint64_t* per_step = NULL; uint64_t total = 0;\n"
                    "    int rc = mdbg_simplify_edges_removed(NULL, &per_step, &total);\n"
-                   '    printf("%u %zu %zu %d %u\\n", st.kind, sizeof st, sizeof(mdbg_simplify_stats), rc, (unsigned)MDBG_ABI_VERSION);\n    return 0;\n}\n')
+                   '    printf("%u %d %u\\n", st.kind, rc, (unsigned)MDBG_ABI_VERSION);\n    return 0;\n}\n')
     exe = str(tmp_path / "edges_step")
     lib = os.path.join(ROOT, "rust_mdbg_amd")
     subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + lib, "-lmdbg_hip", "-Wl,-rpath," + lib,
                     "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
-    assert out == ["8", str(C.sizeof(api.SimplifyStep)), str(C.sizeof(api.SimplifyStats)), "-1", "3"]      # the layouts are the parent's; a null context is MDBG_E_PARAM
+    assert out == ["8", "-1", "3"]      # a null context is MDBG_E_PARAM (the layouts: tests/test_abi_exports.py)

@@ -85,7 +85,6 @@ def test_new_arguments_and_the_cli_flag(tmp_path):
     p = inspect.signature(E.Emitter.write_sequences_from_kept).parameters
     assert list(p)[:5] == ["self", "prefix", "nodes", "l", "m"] and p["threads"].default == 1 and p["chunk_bases"].default == 256 << 20
     assert "mdbg_seqfile_write_nodes" in E.EXPORTS and {"mdbg_graph_node_seqs", "mdbg_graph_node_seqs_device", "mdbg_node_seqs_ms"} <= set(api.EXPORTS)
-    assert C.sizeof(api.NodeSeqs) == 5 * 8
     lib = os.path.join(ROOT, "rust_mdbg_amd")
     exe = str(tmp_path / "mdbg_cli")
     subprocess.run(["gcc", "-O1", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "mdbg_cli.c"), "-L" + lib, "-lmdbg_hip", "-lmdbg_emit",

@@ -157,22 +157,3 @@ def test_the_library_side_writer_prints_the_same_text():
     assert api.read_path_text(as_library_result(r, range(len(c.reads))), u["circular"]) == SHORT_READS_TSV
     c, u, r = plain("bubble 7/3")
     assert api.read_path_text(as_library_result(r, range(50, 60)), np.array(u["circular"], np.uint8)) == RP.tsv_text(r, range(50, 60), u["circular"])
-
-
-def test_python_mirror_of_the_result_struct_matches_the_c_compiler(tmp_path):
-    import ctypes as C
-    import subprocess
-    from rust_mdbg_amd import api
-    fields = [f for f, _ in api.ReadPathList._fields_]
-    assert fields == ["first_read", "n_reads", "n_windows", "n_placed", "n_steps", "n_unitigs", "ordinal", "read_windows", "step_offsets", "first_window", "step_windows",
-                      "unitig", "first_entry", "strand", "support_windows", "support_steps"]
-    body = 'printf("%zu\\n", sizeof(mdbg_read_path_list));\n' + "".join('printf("%%zu\\n", offsetof(mdbg_read_path_list, %s));\n' % f for f in fields)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mdbg_hip.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
-    got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [C.sizeof(api.ReadPathList)] + [getattr(api.ReadPathList, f).offset for f in fields]
-    L = api.load_library()
-    for f in ("mdbg_graph_read_paths", "mdbg_graph_read_paths_device", "mdbg_read_paths_ms"):
-        assert hasattr(L, f) and f in api.EXPORTS
