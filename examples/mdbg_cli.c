@@ -4,7 +4,9 @@
  *   `gfatools asm -u` + to_basespace + gfa2fasta.sh; no tip or bubble removal)
  *   -c N,L: a small-component step in the schedule (every unitig of a non-circular connected component of at most N nodes and L bases is removed; 0 = no limit
  *   on that side); -e N: an edge-pruning step in the schedule (every edge record crossed by fewer than N resident reads goes where reads leave its source
- *   and enter its target another way: MDBG_SIMPLIFY_EDGES, mdbg_hip.h); --components: the number of connected components of the unitig graph and the largest one (mdbg_graph_components)
+ *   and enter its target another way: MDBG_SIMPLIFY_EDGES, mdbg_hip.h); -r N: a repeat step (every unitig the resident reads resolve at min_support N is
+ *   duplicated, one copy per strong transit key, so the contigs cross it: MDBG_SIMPLIFY_REPEATS; one per schedule, no -e behind it; the copied entries are printed,
+ *   and --transits then writes no .msimpl.transits.tsv: no read is placed on a list with copies); --components: the number of connected components of the unitig graph and the largest one (mdbg_graph_components)
  *   --read-paths (implies --contigs): the resident reads threaded through the unitig list (mdbg_graph_read_paths, in ranges of 2^20 reads): one summary line
  *   --junctions (implies --contigs): the reads that cross each edge record of the unitig list (mdbg_graph_junctions, in ranges of 2^20 reads, the supports summed):
  *   one summary line
@@ -212,6 +214,13 @@ int main(int argc, char** argv) {
             if (*end || !*a || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c / -e\n"); return 2; }
             steps[n_steps++] = st; simplify = 1;
         }
+        else if (!strcmp(argv[i], "-r") && i + 1 < argc) {              /* the unitigs the reads resolve at min_support N are duplicated (one per schedule, no -e behind it) */
+            char* end = NULL; const char* a = argv[++i];
+            mdbg_simplify_step st; st.kind = MDBG_SIMPLIFY_REPEATS; st.max_bases = 0;
+            st.max_nodes = (uint32_t)strtoul(a, &end, 10);              /* (the field carries min_support for this kind) */
+            if (*end || !*a || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c / -e / -r\n"); return 2; }
+            steps[n_steps++] = st; simplify = 1;
+        }
         else if (!strcmp(argv[i], "--components")) components = 1;
         else if (!strcmp(argv[i], "--read-paths")) read_paths = 1;
         else if (!strcmp(argv[i], "--junctions")) junctions = 1;
@@ -222,7 +231,7 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
     if (simplify || components || read_paths || junctions || transits) contigs = 1;
     if (!contigs) keep_reads = 0;
@@ -334,17 +343,20 @@ int main(int argc, char** argv) {
         mdbg_unitig_list sl; mdbg_simplify_stats ss;
         rc = mdbg_graph_simplify(ctx, steps, n_steps, &sl, &ss);
         if (rc) die(ctx, "mdbg_graph_simplify", rc);
-        const uint64_t* edges_removed = NULL; uint64_t total_edges_removed = 0; int edge_steps = 0;
+        const uint64_t* edges_removed = NULL; uint64_t total_edges_removed = 0; int edge_steps = 0, repeat_steps = 0;
         rc = mdbg_simplify_edges_removed(ctx, &edges_removed, &total_edges_removed);
         if (rc) die(ctx, "mdbg_simplify_edges_removed", rc);
         for (uint32_t j = 0; j < ss.n_steps; ++j)
-            if (steps[j].kind == MDBG_SIMPLIFY_EDGES) { printf("simplify step %u (edges %u): %llu edge records removed\n", j + 1, steps[j].max_nodes, (unsigned long long)edges_removed[j]); edge_steps = 1; }
+            if (steps[j].kind == MDBG_SIMPLIFY_REPEATS) { printf("simplify step %u (repeats %u)\n", j + 1, steps[j].max_nodes); repeat_steps = 1; }
+            else if (steps[j].kind == MDBG_SIMPLIFY_EDGES) { printf("simplify step %u (edges %u): %llu edge records removed\n", j + 1, steps[j].max_nodes, (unsigned long long)edges_removed[j]); edge_steps = 1; }
             else printf("simplify step %u (%s %u,%llu): %llu unitigs, %llu nodes removed\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_TIPS ? "tips" : steps[j].kind == MDBG_SIMPLIFY_BUBBLES ? "bubbles" : "components", steps[j].max_nodes,
                    (unsigned long long)steps[j].max_bases, (unsigned long long)ss.unitigs_removed[j], (unsigned long long)ss.nodes_removed[j]);
         printf("simplify: %llu unitigs, %llu nodes removed; %llu contigs left\n", (unsigned long long)ss.total_unitigs_removed, (unsigned long long)ss.total_nodes_removed,
                (unsigned long long)sl.n_unitigs);
         if (edge_steps) printf("simplify: %llu edge records removed\n", (unsigned long long)total_edges_removed);
-        if (transits) { snprintf(path, sizeof path, "%s.msimpl.transits.tsv", prefix); write_transits(ctx, &sl, path, transits, " (simplified)"); }
+        /* n_entries == rows of the node table - total_nodes_removed + copies (mdbg_hip.h); no read is placed on a list with copies: no .msimpl.transits.tsv then */
+        if (repeat_steps) printf("simplify: %llu entries copied\n", (unsigned long long)(sl.n_entries ? sl.n_entries + ss.total_nodes_removed - nodes.n : 0));
+        if (transits && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl.transits.tsv", prefix); write_transits(ctx, &sl, path, transits, " (simplified)"); }
         sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
         if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
         if (keep_reads) {                                           /* the sequences from the device store instead of the second pass */

@@ -406,12 +406,45 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   or not, out of a dead-end side stays, so a coverage gap does not cut a contig; the step removes no node (unitigs_removed[k] == nodes_removed[k] == 0
  *   for it); a compaction follows iff it removed a record; if no read is resident nothing is strong and the step removes nothing.  The removed records are
  *   counted by mdbg_simplify_edges_removed.
+ *   REPEATS, {MDBG_SIMPLIFY_REPEATS, min_support, 0}: as for EDGES, max_nodes carries min_support (>= 1) and max_bases is reserved (0).  The step duplicates the
+ *   unitigs the resident reads resolve (mdbg_graph_transits below), so that the next compaction makes contigs that cross the repeat.  It decides against the
+ *   current unitig list L as it is when the step starts, with what mdbg_graph_transits gives for L over the WHOLE resident store (first_read = 0, max_reads = 0) at
+ *   that min_support.  Vertex (u, j, s), pair, mirror, key, link and m(u) are those of the junction and transit definitions.  A unitig u is RESOLVED iff
+ *   verdict[u] == MDBG_TRANSIT_RESOLVED; its strong keys, in key order, are (u, p_0, q_0) < ... < (u, p_{m-1}, q_{m-1}) with m = n_in[u] = n_out[u] >= 2, and by the
+ *   verdict the p are pairwise different and so are the q.
+ *   Copies.  Let X = 1 + the largest DbgEntry.index of the node table.  Go through the resolved unitigs in ascending u, for each through i = 1 .. m-1, and within
+ *   that through the entries j = 0 .. m(u)-1 of u's walk: the copy (u, i, j) is a new node with index X + c, c counting from 0 in that order.  A copy has every
+ *   column of its original (abundance, source read and span, shift, reversed); copy i = 0 is the originals themselves.  Abundances are not divided: kc_sum counts
+ *   the repeat's windows in every copy.
+ *   Arcs.  Take every edge record of the current graph (both nodes in S, its arc not in D); its pair is (x, y) in L's coordinates.  An interior link of a resolved
+ *   u stays, and for every i >= 1 one more record joins the copies (u, i, .) of its two nodes, with the same orientations and the same overlap.  Otherwise each of
+ *   its two ends is treated on its own.  Source end: if x == (u, m(u)-1, 0) with u resolved, the end belongs to the i with q_i == y; if x == (u, 0, 1), to the i
+ *   with p_i == (y.u, y.j, 1 - y.s).  Target end: if y == (u, 0, 0), to the i with p_i == x; if y == (u, m(u)-1, 1), to the i with q_i == (x.u, x.j, 1 - x.s).  The
+ *   node at that end is replaced by its copy i (i = 0: unchanged).  Exactly one such i exists, because the matching is perfect and n_in == m; if the device finds
+ *   none or two, that is a defect: MDBG_E_DEVICE, nothing guessed and nothing indexed outside.  A record that joins two resolved unitigs is redirected at both ends.
+ *   Consequences: a record, its mirror record and their duplicates move together (equal junction keys); no record is removed; every copy of u has exactly one
+ *   distinct in-arc and one distinct out-arc; the step removes nothing (unitigs_removed[k] == nodes_removed[k] == 0, and its mdbg_simplify_edges_removed entry is
+ *   0); a compaction follows iff the step copied something; with no resident reads nothing resolves.
+ *   State afterwards: S gains the copies and the arc set is the redirected one.  TIPS, BUBBLES and COMPONENTS steps behind it run unchanged on that graph, and
+ *   their nodes_removed count copies like nodes.  Unitig order and orientation ("index of the first node") use the copies' indices; the list's node[] reports the
+ *   ORIGINAL's index, so an index may occur in several entries.  n_entries == rows of the node table - total_nodes_removed + copies.
+ *   Limits of this round, MDBG_E_PARAM while the schedule is validated: min_support == 0, max_bases != 0, more than one REPEATS step in a schedule, an EDGES step
+ *   behind a REPEATS step (reads cannot be placed on copied nodes).  MDBG_E_CAPACITY: 2^30 rows including the copies, or 2^32 records including the added ones.
+ *   A list that holds copies: mdbg_graph_read_paths*, mdbg_graph_junctions* and mdbg_graph_transits* on it answer MDBG_E_STATE (a table row would belong to several
+ *   entries); the context stays usable, and a list built by a REPEATS step that copied nothing is placed as always.  mdbg_graph_components*, mdbg_graph_contigs* and
+ *   the emitters work on it unchanged: they read the list, not the table.  Placing reads on copies, and with it a second round of resolution, is not built.
+ *   The number of copied entries follows from the identity above (a schedule holds at most one such step); a per-step count of resolved unitigs would need a new
+ *   entry point and waits for a change that may touch the number of prototypes.
  *   Result: n_entries = |S|; edges = every edge record whose two nodes survive, whose arc is not in D and is not an interior link, in source order.
  * An EDGES step needs what mdbg_graph_junctions needs on top of a current edge list — the node table current, the bounds of the read paths —, and the call
  * refuses with the same code before anything is launched; the context stays usable.  The step uses the context's junction buffers: a junction result the
  * caller holds ends with a simplify call that has an EDGES step, exactly as a component result ends with one that has a COMPONENTS step; a held read-path,
  * component or contig result is untouched.  The defect flags of the junction stage surface as MDBG_E_DEVICE.
- * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, an EDGES step with min_support == 0 or max_bases != 0, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
+ * A REPEATS step needs what mdbg_graph_transits needs, and the call refuses with the same codes before anything is launched.  It uses the context's transit
+ * buffers and placement scratch: a transit result the caller holds ends with a simplify call that has a REPEATS step; after such a call mdbg_transits_ms gives the
+ * device time of the step's transit stage.  It waits once for its transit stage and, if something resolves, twice more (the totals that size the copies, its
+ * defect flag); one more wait at the end of the schedule maps node[] to the originals.
+ * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, an EDGES or REPEATS step with min_support == 0 or max_bases != 0, a second REPEATS step, an EDGES step behind a REPEATS step, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
  * entries owned by the context (valid like the list); n_compactions: compactions run (a step that removes nothing is followed by none);
  * n_syncs: host synchronisations of the call (per step: those of one compaction + 1; a COMPONENTS step adds none of its own; an EDGES step that has
  * records and resident reads to look at waits twice — the one wait of its junction stage, then its own counter, which the junction stage's wait cannot
@@ -423,6 +456,7 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
 #define MDBG_SIMPLIFY_BUBBLES 2u
 #define MDBG_SIMPLIFY_COMPONENTS 4u
 #define MDBG_SIMPLIFY_EDGES 8u     /* {EDGES, min_support, 0} */
+#define MDBG_SIMPLIFY_REPEATS 16u  /* {REPEATS, min_support, 0} */
 typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
 typedef struct mdbg_simplify_stats {
     uint32_t n_steps, n_compactions;
@@ -623,7 +657,7 @@ int mdbg_junctions_ms(mdbg_ctx* ctx, double* ms);
  * can.  This call lists, per unitig of the CURRENT list, every (entrance, exit) pair the resident reads take through it, with counts, and says per unitig whether
  * those pairs match its entrances to its exits one to one.  It works on what mdbg_graph_junctions works on, with the same state requirements, the same range of reads
  * [first_read, first_read + max_reads) (max_reads = 0: to the end), the same capacity bounds and the same defect flags.  It changes nothing: duplicating a resolved
- * unitig is a later step's business.  SINGLE GPU ONLY.
+ * unitig is the business of a simplify step (MDBG_SIMPLIFY_REPEATS, mdbg_graph_simplify above), which runs this stage on the list it decides against.  SINGLE GPU ONLY.
  *
  * Definition.  Windows, PLACED, vertex (u, j, s), pair, MIRROR, KEY, LINK, CROSSING, the key of an edge record and m(u) are those of mdbg_graph_junctions.  A crossing
  * is EXPLAINED iff its key is some record's key.

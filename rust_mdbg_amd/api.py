@@ -280,6 +280,7 @@ class SimplifyStats(C.Structure):      # mdbg_simplify_stats
 MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
 MDBG_SIMPLIFY_COMPONENTS = 4      # (kind, max_nodes, max_bases): every unitig of a non-circular connected component of at most max_nodes nodes and max_bases bases goes
 MDBG_SIMPLIFY_EDGES = 8           # (kind, min_support, 0): every edge record crossed by fewer than min_support resident reads goes where reads leave its source and enter its target another way
+MDBG_SIMPLIFY_REPEATS = 16        # (kind, min_support, 0): every unitig the resident reads resolve at min_support (graph_transits) is duplicated, one copy per strong key; at most one per schedule, no EDGES step behind it
 _T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
 # the schedule of the first `gfatools asm` line of utils/magic_simplify, as (kind, max_nodes, max_bases): -t N,L = tips of at most N nodes and L bases,
 # -b L = bubbles whose branches have at most L bases.  Same schedule, this project's own order-free rules (include/mdbg_hip.h): not gfatools parity.
@@ -592,12 +593,13 @@ class Mdbg:
         nd = Nodes()
         if gfa_only:
             self._chk(self.L.mdbg_finalize_gfa(self.h, C.byref(nd)))
-            n = int(nd.n)
+            n = self._table_rows = int(nd.n)
             return dict(n_nodes=n, n_nodes_before=int(nd.n_distinct), n_wrapped=int(nd.n_wrapped), k=int(nd.k), keys=None, index=_np(nd.index, n, np.uint32),
                         abundance=_np(nd.abundance, n, np.uint16), seqlen=_np(nd.seqlen, n, np.uint32), shift=None, shift_full=None, src_read=None, src_start=None,
                         src_end=None, reversed=None)
         self._chk(self.L.mdbg_finalize(self.h, C.byref(nd)))
         n, k = nd.n, nd.k
+        self._table_rows = int(n)
         return dict(n_nodes=int(n), n_nodes_before=int(nd.n_distinct), n_wrapped=int(nd.n_wrapped),
                     keys=_np(nd.keys, n * k, np.uint64).reshape(n, k), index=_np(nd.index, n, np.uint32),
                     abundance=_np(nd.abundance, n, np.uint16), seqlen=_np(nd.seqlen, n, np.uint32),
@@ -609,6 +611,7 @@ class Mdbg:
         """node table left in device memory; returns the raw mdbg_nodes struct (device pointers)"""
         nd = Nodes()
         self._chk(self.L.mdbg_finalize_device(self.h, C.byref(nd)))
+        self._table_rows = int(nd.n)
         return nd
 
     def set_timing(self, level):
@@ -735,14 +738,22 @@ class Mdbg:
         self._chk(self.L.mdbg_graph_unitigs_device(self.h, C.byref(u)))
         return u
 
-    def _simplify_stats(self, st):
+    def _simplify_stats(self, st, steps, n_entries):
+        """entries_copied: the entries a REPEATS step added, from n_entries == rows of the node table - total_nodes_removed + copies (exact: a schedule holds at
+        most one such step); 0 for a schedule without one, None if this object has not seen the finalize call that made the table"""
         n = int(st.n_steps)
         per_step, total = C.POINTER(C.c_uint64)(), C.c_uint64()
         self._chk(self.L.mdbg_simplify_edges_removed(self.h, C.byref(per_step), C.byref(total)))
         return dict(unitigs_removed=[int(st.unitigs_removed[i]) for i in range(n)], nodes_removed=[int(st.nodes_removed[i]) for i in range(n)],
                     edges_removed=[int(per_step[i]) for i in range(n)], total_unitigs_removed=int(st.total_unitigs_removed),
                     total_nodes_removed=int(st.total_nodes_removed), total_edges_removed=int(total.value), n_compactions=int(st.n_compactions),
-                    n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs))
+                    n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs), entries_copied=self._entries_copied(steps, int(n_entries), int(st.total_nodes_removed)))
+
+    def _entries_copied(self, steps, n_entries, total_nodes_removed):
+        if not any(int(s[0]) == MDBG_SIMPLIFY_REPEATS for s in steps) or n_entries == 0:
+            return 0
+        rows = getattr(self, "_table_rows", None)
+        return None if rows is None else n_entries - (rows - total_nodes_removed)
 
     def graph_simplify(self, steps, raw=False):
         """the unitigs that are left after a schedule of tip, simple-bubble, small-component and edge-pruning steps, decided and compacted on the GPU (mdbg_graph_simplify, include/mdbg_hip.h: this
@@ -752,7 +763,7 @@ class Mdbg:
         arr, n = simplify_steps(steps)
         u, st = UnitigList(), SimplifyStats()
         self._chk(self.L.mdbg_graph_simplify(self.h, arr, n, C.byref(u), C.byref(st)))
-        stats = self._simplify_stats(st)
+        stats = self._simplify_stats(st, steps, u.n_entries)
         if raw:
             return u, stats
         return dict(self._unitig_dict(u), stats=stats)
@@ -762,7 +773,7 @@ class Mdbg:
         arr, n = simplify_steps(steps)
         u, st = UnitigList(), SimplifyStats()
         self._chk(self.L.mdbg_graph_simplify_device(self.h, arr, n, C.byref(u), C.byref(st)))
-        return u, self._simplify_stats(st)
+        return u, self._simplify_stats(st, steps, u.n_entries)
 
     def graph_components(self):
         """connected components of the current unitig list (the last graph_unitigs* / graph_simplify* call), found on the GPU: two unitigs are joined iff an edge of

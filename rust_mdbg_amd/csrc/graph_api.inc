@@ -1,6 +1,7 @@
 // graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip, bubble and small-component
 // removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip), and the stages that
-// decide with the resident reads: read paths (read_paths.hip), read support per junction (junctions.hip) and transits (transits.hip), each ONE call over the
+// decide with the resident reads: read paths (read_paths.hip), read support per junction (junctions.hip) and transits (transits.hip; a REPEATS step of a simplify
+// schedule runs them too and duplicates what they resolve, repeats.hip), each ONE call over the
 // context's one placement scratch (placement.hip, c->res.placement) and the one window placer below.
 // Host code; included by api.inc, whose context, fail(), MDBG_ENTER and HandOver it uses; what is current is asked of c->res (results.inc).
 
@@ -79,6 +80,8 @@ static int stage_prologue(mdbg_ctx* c, const char* what_is, uint64_t first_read,
     *ms = 0; *empty = true;
     int e;
     if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
+    if (c->res.unitig_list_copies())
+        return fail(c, MDBG_E_STATE, "the current unitig list holds copies made by a REPEATS step: a row of the node table belongs to several entries, so no read can be placed on it");
     const UnitigResult& ul = c->res.unitigs.last;
     if ((e = store_range(c, ul.n_unitigs, ul.n_entries, first_read, max_reads, pw, empty)) || *empty) return e;
     return with_records ? refuse_too_many_records(c, ul.edges.n) : MDBG_OK;
@@ -123,13 +126,18 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     memset(out, 0, sizeof *out);
     Results& R = c->res;
     auto& UL = R.unitigs;
-    bool with_components = false, with_edges = false;
+    bool with_components = false, with_edges = false, with_repeats = false;
     if (stats) {
         memset(stats, 0, sizeof *stats);
         for (uint32_t i = 0; i < n_steps; ++i) {
             const uint32_t kind = steps[i].kind;
-            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES)
+            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES && kind != MDBG_SIMPLIFY_REPEATS)
                 return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
+            if (kind == MDBG_SIMPLIFY_REPEATS && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
+                return fail(c, MDBG_E_PARAM, "a repeat step takes {REPEATS, min_support >= 1, 0}");
+            if (kind == MDBG_SIMPLIFY_REPEATS && with_repeats) return fail(c, MDBG_E_PARAM, "a schedule holds at most one REPEATS step: reads cannot be placed on copied nodes");
+            if (kind == MDBG_SIMPLIFY_EDGES && with_repeats) return fail(c, MDBG_E_PARAM, "an EDGES step cannot follow a REPEATS step: reads cannot be placed on copied nodes");
+            with_repeats |= kind == MDBG_SIMPLIFY_REPEATS;
             if (kind == MDBG_SIMPLIFY_EDGES && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
                 return fail(c, MDBG_E_PARAM, "an edge step takes {EDGES, min_support >= 1, 0}");
             with_edges |= kind == MDBG_SIMPLIFY_EDGES;
@@ -147,30 +155,37 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (R.n_rows() == 0) { R.unitig_list_is(UnitigResult{}); return MDBG_OK; }
     if (with_components) R.comps.buf.get();
     SimplifySupport sup{}; PlaceWindows pw{};
-    if (with_edges) {                                // what the junction support asks, before anything of the schedule is launched
+    if (with_edges || with_repeats) {                // what the junction support and the transits ask, before anything of the schedule is launched
         int e; bool empty;
         if ((e = refuse_too_many_records(c, R.edges.last.n)) || (e = store_range(c, 1, R.n_rows(), 0, 0, &pw, &empty))) return e;
-        sup.jb = R.junctions.buf.get(); sup.pb = R.placement.buf.get(); sup.index = c->finF.o_index; sup.n_rows = R.n_rows(); sup.range = pw.rg; sup.has_reads = !empty;
+        sup.pb = R.placement.buf.get(); sup.index = c->finF.o_index; sup.n_rows = R.n_rows(); sup.range = pw.rg; sup.has_reads = !empty;
         sup.placer = WindowPlacer{place_windows, &pw};
-        R.junctions.ms = 0;
+        if (with_edges) { sup.jb = R.junctions.buf.get(); R.junctions.ms = 0; }
+        if (with_repeats) { sup.tb = R.transits.buf.get(); R.transits.ms = 0; }
     }
     const FinArgs& F = c->finF;
     UnitigNodes nd; nd.index = F.o_index; nd.abund = F.o_abund; nd.shift_full = F.o_shift_full; nd.src_read = F.o_src_read; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end;
     nd.reversed = F.o_rev; nd.n = R.n_rows();
     UnitigResult r; int broken = 0;
     SimplifyInfo si{};
-    const hipError_t he = stats ? simplify_unitigs(UL.buf.get(), R.comps.buf.have(), with_edges ? &sup : nullptr, nd, R.edges.last, steps, n_steps, c->stream, &r, UL.removed_unitigs.data(),
+    const hipError_t he = stats ? simplify_unitigs(UL.buf.get(), R.comps.buf.have(), with_edges || with_repeats ? &sup : nullptr, nd, R.edges.last, steps, n_steps, c->stream, &r, UL.removed_unitigs.data(),
                                                    UL.removed_nodes.data(), UL.removed_edges.data(), &si, &broken)
                                 : build_unitigs(UL.buf.get(), nd, R.edges.last, c->stream, &r, &broken);
     if (he != hipSuccess) return fail_hip(c, "build_unitigs", he);
     if (with_edges) R.junctions.ms = si.junction_ms;
+    if (with_repeats) R.transits.ms = si.transit_ms;
     if (broken && si.junction_defect) return stage_defect(c, si.junction_defect);
+    if (broken && si.transit_defect) return stage_defect(c, si.transit_defect);
+    if (broken && si.repeats_too_large) return fail(c, MDBG_E_CAPACITY, "the copies of a REPEATS step would bring the graph to 2^30 nodes or 2^32 edge records");
+    if (broken && si.repeats_defect)
+        return fail(c, MDBG_E_DEVICE, si.repeats_defect & RX_DEFECT_MATCH ? "an end of an edge record at a resolved unitig belongs to no strong transit key, or to two: nothing was copied"
+                                                                             : "a vertex of the last compaction or a transit row lies outside the unitig list: nothing was copied");
     if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, or the walk broke an invariant");
     if (stats) {
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
         for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += UL.removed_unitigs[i]; stats->total_nodes_removed += UL.removed_nodes[i]; }
     }
-    R.unitig_list_is(r);
+    R.unitig_list_is(r, si.copies);
     const u64 U = r.n_unitigs, N = r.n_entries;
     out->n_unitigs = U; out->n_entries = N; out->n_rounds = r.n_rounds; out->edges.n = r.edges.n;
     if (U == 0) return MDBG_OK;                      // a schedule that removed everything: the empty list, as an empty context gives it

@@ -33,13 +33,14 @@ struct Results {
              HostRaw<u64> ord, off, supw, sups; HostRaw<u32> rw, fw, nw, unitig, fe; HostRaw<u8> strand; double ms = 0; } rpaths;
     struct { StageBuffers<JunctionBuffers, junction_buffers_create, junction_buffers_destroy> buf;                       // its result lives until the next junction call or simplify call with an EDGES step
              HostRaw<u64> support, count; HostRaw<u32> u1, e1, u2, e2; HostRaw<u8> s1, s2; double ms = 0; } junctions;
-    struct { StageBuffers<TransitBuffers, transit_buffers_create, transit_buffers_destroy> buf;                          // its result lives until the next transit call
+    struct { StageBuffers<TransitBuffers, transit_buffers_create, transit_buffers_destroy> buf;                          // its result lives until the next transit call or simplify call with a REPEATS step
              HostRaw<u64> count, passes; HostRaw<u32> unitig, iu, ie, ou, oe, irec, orec, n_in, n_out; HostRaw<u8> is, os, verdict; double ms = 0; } transits;
 
     // ---- what is current.  ONLY the functions from here to prefix_is_summed write these members; everybody else asks the predicates below.
     struct { NodeTable table = NodeTable::NONE; u64 rows = 0;
              bool edges = false;         // edges.last belongs to the node table as it stands (unitigs.hip reads both)
              bool ulist = false;         // unitigs.last is current: no edge, finalize, ingest, rewind or reset call since
+             u64 copies = 0;             // entries of unitigs.last that a REPEATS step of its schedule copied: a table row may then belong to several entries
              bool prefix = false; } cur; // nseq.buf holds the prefix of the rows' lengths of the node table as it stands
     void invalidate(ResultsFrom from) {
         if (from <= FROM_NODES) { cur.table = NodeTable::NONE; cur.prefix = false; }
@@ -53,7 +54,7 @@ struct Results {
         cur.table = t; cur.rows = t == NodeTable::ROWS ? n : 0; cur.prefix = false;
     }
     void edge_list_is(const EdgeResult& r, bool current) { edges.last = r; cur.edges = current; }
-    void unitig_list_is(const UnitigResult& r) { unitigs.last = r; cur.ulist = true; }
+    void unitig_list_is(const UnitigResult& r, u64 copies = 0) { unitigs.last = r; cur.ulist = true; cur.copies = copies; }
     void prefix_is_summed() { cur.prefix = true; }
 
     // The readers ask two DIFFERENT questions about the node table, and the answers differ on a context that holds nothing and was never finalized:
@@ -67,6 +68,7 @@ struct Results {
     u64 n_rows() const { return has_rows_table() ? cur.rows : 0; }
     bool edge_list_current() const { return has_rows_table() && cur.edges; }
     bool unitig_list_current() const { return cur.ulist; }
+    u64 unitig_list_copies() const { return cur.ulist ? cur.copies : 0; }
     bool prefix_summed() const { return cur.prefix; }
 };
 }  // namespace

@@ -23,10 +23,16 @@
 //   edge_decide_kernel   kept weak record with strong[eu] and strong[comp(ev)] -> edge_alive[e] = 0; counts the records
 // The record mask is closed under mirroring and duplication because equal junction keys carry equal supports; the next compaction takes it beside the node mask.
 //
+// MDBG_SIMPLIFY_REPEATS removes nothing: the transit stage (transits.hip) says which unitigs of the current list the reads resolve, and repeats.hip appends the
+// copies to the node columns, the masks and the edge records; the next compaction takes the larger graph as any other, and the schedule goes on with it.  The
+// list's node[] names the originals: one kernel at the end of the schedule (repeats_report_originals).
+//
 // Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks; an EDGES step
-// waits once for its junction stage and once for its counter.  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
+// waits once for its junction stage and once for its counter; a REPEATS step once for its transit stage and, if something resolves, once for the totals that size
+// the copies and once for its defect flag.  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
 #include <cstring>
 
+#include "repeats.h"
 #include "simplify.h"
 #include "unitigs_priv.h"
 
@@ -209,19 +215,21 @@ __global__ __launch_bounds__(256) void edge_decide_kernel(EdgeArgs a) {
 
 }  // namespace
 
-hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const SimplifySupport* sup, const UnitigNodes& nd, const EdgeResult& ed, const mdbg_simplify_step* steps, uint32_t n_steps,
+hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const SimplifySupport* sup, const UnitigNodes& nd0, const EdgeResult& ed0, const mdbg_simplify_step* steps, uint32_t n_steps,
                      hipStream_t s, UnitigResult* out, uint64_t* unitigs_removed, uint64_t* nodes_removed, uint64_t* edges_removed, SimplifyInfo* info, int* broken) {
     memset(info, 0, sizeof *info);
     for (uint32_t k = 0; k < n_steps; ++k) edges_removed[k] = 0;
-    if (n_steps == 0 || nd.n == 0) {                          // the empty schedule IS the unitig call
-        const hipError_t rc = build_unitigs(B, nd, ed, s, out, broken);
-        if (rc == hipSuccess && !*broken && nd.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed.n ? 1 : 0); }
+    if (n_steps == 0 || nd0.n == 0) {                         // the empty schedule IS the unitig call
+        const hipError_t rc = build_unitigs(B, nd0, ed0, s, out, broken);
+        if (rc == hipSuccess && !*broken && nd0.n) { info->n_compactions = 1; info->n_rounds_total = out->n_rounds; info->n_syncs = out->n_rounds + 3 + (ed0.n ? 1 : 0); }
         return rc;
     }
-    const u64 n = nd.n;
+    UnitigNodes nd = nd0; EdgeResult ed = ed0;               // a REPEATS step replaces both by the graph with the copies
+    u64 n = nd.n;
     *broken = 0;
     if (n >= (1ull << 30)) return defect(broken);
-    const u32 n2x = (u32)(2 * n);
+    u32 n2x = (u32)(2 * n);
+    RepeatsResult rr; memset(&rr, 0, sizeof rr);
     GHIP(B->alive.ensure(n));
     GHIP(hipMemsetAsync(B->alive.p, 1, n, s));
     u8* alive = B->alive.as<u8>();
@@ -270,6 +278,25 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
             if (gone) { edge_alive = B->edge_alive.as<u8>(); stale = true; }
             continue;
         }
+        if (steps[k].kind == MDBG_SIMPLIFY_REPEATS) {
+            if (!sup || !sup->tb) return hipErrorInvalidValue;
+            if (!sup->has_reads || ed.n == 0 || out->edges.n == 0) continue;      // nothing resolves without reads, and a repeat has records
+            TransitResult tr;
+            GHIP(transits_run(sup->tb, sup->pb, *out, sup->index, sup->n_rows, sup->range, steps[k].max_nodes, sup->placer, s, &tr));
+            ++info->n_syncs; info->transit_ms += tr.ms;
+            if (tr.defect) { info->transit_defect = tr.defect; return defect(broken); }
+            if (tr.n_unitigs != U) return defect(broken);
+            if (tr.n_resolved == 0 || tr.n_transits == 0) continue;
+            GHIP(repeats_run(B, tr, steps[k].max_nodes, *out, nd, ed, alive, edge_alive, s, &rr));
+            info->n_syncs += rr.too_large ? 1 : 2;
+            if (rr.too_large) { info->repeats_too_large = true; return defect(broken); }
+            if (rr.defect) { info->repeats_defect = rr.defect; return defect(broken); }
+            if (rr.copies == 0) return defect(broken);      // a resolved unitig has two entrances and an entry
+            nd = rr.nd; ed = rr.ed; alive = rr.alive; edge_alive = rr.edge_alive;
+            n = nd.n; n2x = (u32)(2 * n); n_alive += rr.copies; info->copies = rr.copies;
+            stale = true;
+            continue;
+        }
         GHIP(B->uhead.ensure(n * 4)); GHIP(B->utail.ensure(n * 4)); GHIP(B->att.ensure(n * 4)); GHIP(B->rem.ensure(n)); GHIP(B->owner.ensure((size_t)n2x * 4));
         u32* d_ctr = B->ctr.as<u32>();                        // (the compaction is over: its round counters are free)
         GHIP(hipMemsetAsync(d_ctr, 0, 8, s));
@@ -312,5 +339,6 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
         stale = got[1] != 0;
     }
     if (stale) { GHIP(compact()); if (*broken) return hipSuccess; }
+    if (rr.copies) { GHIP(repeats_report_originals(B, *out, rr, s)); GHIP(hipStreamSynchronize(s)); ++info->n_syncs; }
     return hipGetLastError();
 }
