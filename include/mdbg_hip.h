@@ -386,8 +386,8 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   BUBBLES (simple ones only).  A small unitig u with first vertex f and last vertex t is a branch iff f has exactly one in-arc
  *   p -> f, t exactly one out-arc t -> q, neither node(p) nor node(q) lies on u, and q != comp(p).  Its key is the smaller of (p, q)
  *   and (comp(q), comp(p)) under the vertex order 2 * index + minus.  Of the branches with one key all but the one that beats the
- *   others are removed.  Branches that branch themselves (superbubbles) are not treated; repeated tip and bubble steps reduce many
- *   of them to simple ones.
+ *   others are removed.  Branches that branch themselves are not treated by this kind (repeated tip and bubble steps reduce many
+ *   of them to simple ones); they are the SUPERBUBBLES kind's, below.
  *   COMPONENTS.  The step decides against the current unitigs and their edges as they are when the step starts, grouped into connected components
  *   by the definition of mdbg_graph_components below.  A component is SMALL for the step iff its `circular` is 0, its `nodes` <= max_nodes and its
  *   `bases` <= max_bases (0 = no limit on that side): the limits apply to the component's sums, not to one unitig.  Every unitig of a small component
@@ -435,6 +435,32 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   the emitters work on it unchanged: they read the list, not the table.  Placing reads on copies, and with it a second round of resolution, is not built.
  *   The number of copied entries follows from the identity above (a schedule holds at most one such step); a per-step count of resolved unitigs would need a new
  *   entry point and waits for a change that may touch the number of prototypes.
+ *   SUPERBUBBLES, {MDBG_SIMPLIFY_SUPERBUBBLES, max_nodes, max_bases}: what `gfatools asm -b` (gfa_pop_bubble) is after — a bubble whose inside branches again, is
+ *   cross-linked or holds bubbles of its own — by an order-free rule.  Like every kind the step decides against the graph as it is when the step starts.  Vertices:
+ *   the oriented current unitigs (u, strand).  Arcs: the unitig edge records between surviving nodes whose arc is not in D, plus their mirrors; parallel records
+ *   and duplicates count as one arc.  For a vertex s with at least two distinct out-neighbours, (s, t) BOUNDS A SUPERBUBBLE WITH INTERIOR I iff I is a non-empty
+ *   set of vertices, s and t are not in I, t != s, and
+ *     (a) every out-neighbour of s and of every x in I lies in I + {t}, and every x in I has at least one (an interior dead end is the TIPS step's business);
+ *     (b) every in-neighbour of t and of every x in I lies in I + {s}, and every x in I has at least one (the mirror image of (a): with it the mirror reading
+ *         below is a superbubble by the same text, and I is exactly what s reaches without leaving t);
+ *     (c) the arcs among I + {s, t} contain no cycle;
+ *     (d) no two members of I + {s, t} are each other's complement, so the unitigs involved are pairwise different (hence no circular unitig is inside);
+ *     (e) t is the first such vertex: no t' in I bounds a superbubble with s over a subset of I;
+ *     (f) |I| <= MDBG_SUPERBUBBLE_MAX_UNITIGS.
+ *   The bubble FITS iff max_nodes == 0 or the entries of the unitigs of I sum to at most max_nodes, and max_bases == 0 or their `length` sums to at most
+ *   max_bases (overlaps are counted twice: a limit, not a measure).  Both 0 is allowed; (f) still bounds it.
+ *   (s, t, I) and its mirror (comp t, comp s, comp I) are one bubble; the reading whose source has the smaller (unitig number, strand) is the CANONICAL one, and it
+ *   alone decides which path is kept.
+ *   Kept path.  mean(x) = kc_sum / entries, compared exactly by cross products.  val(s) = +infinity; for x in I in any topological order best(x) is the in-neighbour
+ *   with the largest val, ties going to the one that BEATS the other (the total order above: mean, then length, then the smaller number), and
+ *   val(x) = min(mean(x), val(best(x))); best(t) is chosen likewise.  The kept path is t, best(t), best(best(t)), ... back to s: the path whose weakest unitig is
+ *   strongest.  When every branch is a single unitig this is the BUBBLES rule's winner.
+ *   Applied bubbles.  Let J be the union of I + comp(I) over all fitting bubbles.  A fitting bubble is APPLIED iff neither s nor comp(t) lies in J: the outermost
+ *   fitting bubble wins, an inner one pops only when the bubble around it does not fit or is no bubble, and back-to-back bubbles that share t = s' are both applied.
+ *   Removal.  Every unitig of an applied bubble's I that is not on its kept path is removed; unitigs_removed[k] / nodes_removed[k] count as for TIPS.  The step
+ *   removes no record of its own and never removes s or t; a compaction follows iff something was removed; behind a REPEATS step it runs unchanged on the larger
+ *   graph, and behind an EDGES step it sees the masked arcs.  Two fitting bubbles are nested or have disjoint interiors, so applied bubbles never touch each
+ *   other's kept path (tests/superbubble_restatement.py asserts it on every graph it sees).
  *   Result: n_entries = |S|; edges = every edge record whose two nodes survive, whose arc is not in D and is not an interior link, in source order.
  * An EDGES step needs what mdbg_graph_junctions needs on top of a current edge list — the node table current, the bounds of the read paths —, and the call
  * refuses with the same code before anything is launched; the context stays usable.  The step uses the context's junction buffers: a junction result the
@@ -457,6 +483,8 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
 #define MDBG_SIMPLIFY_COMPONENTS 4u
 #define MDBG_SIMPLIFY_EDGES 8u     /* {EDGES, min_support, 0} */
 #define MDBG_SIMPLIFY_REPEATS 16u  /* {REPEATS, min_support, 0} */
+#define MDBG_SIMPLIFY_SUPERBUBBLES 64u   /* {SUPERBUBBLES, max_nodes, max_bases}; 32 is no kind */
+#define MDBG_SUPERBUBBLE_MAX_UNITIGS 64u /* (f): the interior and the sink of one bubble fit the 2 x 64 slots of one wave */
 typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
 typedef struct mdbg_simplify_stats {
     uint32_t n_steps, n_compactions;

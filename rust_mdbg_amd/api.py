@@ -281,11 +281,15 @@ MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
 MDBG_SIMPLIFY_COMPONENTS = 4      # (kind, max_nodes, max_bases): every unitig of a non-circular connected component of at most max_nodes nodes and max_bases bases goes
 MDBG_SIMPLIFY_EDGES = 8           # (kind, min_support, 0): every edge record crossed by fewer than min_support resident reads goes where reads leave its source and enter its target another way
 MDBG_SIMPLIFY_REPEATS = 16        # (kind, min_support, 0): every unitig the resident reads resolve at min_support (graph_transits) is duplicated, one copy per strong key; at most one per schedule, no EDGES step behind it
+MDBG_SIMPLIFY_SUPERBUBBLES = 64   # (kind, max_nodes, max_bases): every bubble whose inside may branch (at most max_nodes entries and max_bases bases inside, 0 = no limit) keeps the path whose weakest unitig is strongest
+MDBG_SUPERBUBBLE_MAX_UNITIGS = 64 # the unitigs inside one such bubble
 _T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
 # the schedule of the first `gfatools asm` line of utils/magic_simplify, as (kind, max_nodes, max_bases): -t N,L = tips of at most N nodes and L bases,
 # -b L = bubbles whose branches have at most L bases.  Same schedule, this project's own order-free rules (include/mdbg_hip.h): not gfatools parity.
 MAGIC_SIMPLIFY_STEPS = [_T, _T, _B, _B, _T, _B, _B, _B, _T, _B, _T, (MDBG_SIMPLIFY_BUBBLES, 0, 1000000), (MDBG_SIMPLIFY_TIPS, 10, 150000),
                         (MDBG_SIMPLIFY_BUBBLES, 0, 1000000)]
+# the same schedule with every bubble step as a superbubble step with the same limits (they then bound the bubble's inside, not one branch)
+MAGIC_SUPERBUBBLE_STEPS = [(MDBG_SIMPLIFY_SUPERBUBBLES, mn, mb) if kind == MDBG_SIMPLIFY_BUBBLES else (kind, mn, mb) for kind, mn, mb in MAGIC_SIMPLIFY_STEPS]
 
 
 def simplify_steps(steps):

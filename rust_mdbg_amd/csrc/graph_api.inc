@@ -131,7 +131,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
         memset(stats, 0, sizeof *stats);
         for (uint32_t i = 0; i < n_steps; ++i) {
             const uint32_t kind = steps[i].kind;
-            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES && kind != MDBG_SIMPLIFY_REPEATS)
+            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES && kind != MDBG_SIMPLIFY_REPEATS && kind != MDBG_SIMPLIFY_SUPERBUBBLES)
                 return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
             if (kind == MDBG_SIMPLIFY_REPEATS && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
                 return fail(c, MDBG_E_PARAM, "a repeat step takes {REPEATS, min_support >= 1, 0}");
@@ -180,7 +180,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (broken && si.repeats_defect)
         return fail(c, MDBG_E_DEVICE, si.repeats_defect & RX_DEFECT_MATCH ? "an end of an edge record at a resolved unitig belongs to no strong transit key, or to two: nothing was copied"
                                                                              : "a vertex of the last compaction or a transit row lies outside the unitig list: nothing was copied");
-    if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, or the walk broke an invariant");
+    if (broken) return fail(c, MDBG_E_DEVICE, "unitig ranking did not settle within ceil(log2(2n)) + 1 rounds, a union-find of a component step ran into its bound, a superbubble step met a vertex outside the list, or the walk broke an invariant");
     if (stats) {
         stats->n_compactions = si.n_compactions; stats->n_rounds_total = si.n_rounds_total; stats->n_syncs = si.n_syncs;
         for (uint32_t i = 0; i < n_steps; ++i) { stats->total_unitigs_removed += UL.removed_unitigs[i]; stats->total_nodes_removed += UL.removed_nodes[i]; }

@@ -27,6 +27,9 @@
 // copies to the node columns, the masks and the edge records; the next compaction takes the larger graph as any other, and the schedule goes on with it.  The
 // list's node[] names the originals: one kernel at the end of the schedule (repeats_report_originals).
 //
+// MDBG_SIMPLIFY_SUPERBUBBLES has a translation unit of its own (superbubbles.hip): it reads uhead / utail of ends_kernel and the sorted arcs, writes rem[] and the unitig
+// counter, and shares scatter_kernel and the one wait with the other removing kinds; its defect word travels in that wait as a component step's does.
+//
 // Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks; an EDGES step
 // waits once for its junction stage and once for its counter; a REPEATS step once for its transit stage and, if something resolves, once for the totals that size
 // the copies and once for its defect flag.  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
@@ -34,6 +37,7 @@
 
 #include "repeats.h"
 #include "simplify.h"
+#include "superbubbles.h"
 #include "unitigs_priv.h"
 
 namespace {
@@ -305,7 +309,7 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
         a.offsets = out->offsets; a.length = out->length; a.kc = out->kc_sum; a.circ = out->circular; a.max_nodes = steps[k].max_nodes; a.max_bases = steps[k].max_bases;
         a.uhead = B->uhead.as<u32>(); a.utail = B->utail.as<u32>(); a.att = B->att.as<u32>(); a.owner = B->owner.as<u32>(); a.rem = B->rem.as<u8>(); a.ctr = d_ctr; a.alive = alive;
         const unsigned gu = grid_for(U), gv = grid_for(n2x);
-        const u32* d_cstatus = nullptr;                       // a component step: where its stage reports a defect
+        const u32* d_cstatus = nullptr;                       // a component or superbubble step: where its stage reports a defect
         if (steps[k].kind == MDBG_SIMPLIFY_COMPONENTS) {
             if (!CB) return hipErrorInvalidValue;
             ComponentResult cr;
@@ -318,6 +322,8 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
                 GHIP(hipMemsetAsync(B->owner.p, 0xFF, (size_t)n2x * 4, s));
                 hipLaunchKernelGGL(tip_cand_kernel, dim3(gu), dim3(256), 0, s, a);
                 hipLaunchKernelGGL(tip_decide_kernel, dim3(gu), dim3(256), 0, s, a);
+            } else if (steps[k].kind == MDBG_SIMPLIFY_SUPERBUBBLES) {
+                GHIP(superbubbles_run(B, *out, n2x, a.uhead, a.utail, a.max_nodes, a.max_bases, a.rem, d_ctr, s, &d_cstatus));      // (superbubbles.hip: rem[] and the unitig counter)
             } else {
                 GHIP(B->bkey.ensure(n * 8)); GHIP(B->bkey2.ensure(n * 8)); GHIP(B->bval.ensure(n * 4)); GHIP(B->bval2.ensure(n * 4));
                 a.bkey = B->bkey.as<u64>(); a.bval = B->bval.as<u32>(); a.skey = B->bkey2.as<u64>(); a.sval = B->bval2.as<u32>();

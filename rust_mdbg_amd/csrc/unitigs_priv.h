@@ -1,5 +1,5 @@
-// unitigs_priv.h — what the compaction (unitigs.hip) shows the simplification stage (simplify.hip, repeats.hip): its buffers, its vertex codes and the masked compaction.
-// Included by those three translation units only.
+// unitigs_priv.h — what the compaction (unitigs.hip) shows the simplification stage (simplify.hip, repeats.hip, superbubbles.hip): its buffers, its vertex codes and the masked compaction.
+// Included by those four translation units only.
 #pragma once
 #include "graph_common.h"
 #include "unitigs.h"
@@ -26,6 +26,7 @@ struct UnitigBuffers {
     // repeats.hip, the REPEATS step: its temporaries (per transit row, per unitig, per record), then the node columns, masks and edge records extended by the copies
     Buf x_strong, x_rank, x_rows, x_rowbase, x_ecnt, x_ebase, x_ctr;
     Buf x_index, x_abund, x_shift, x_sread, x_sstart, x_send, x_rev, x_alive, x_origin, x_n1, x_o1, x_n2, x_o2, x_ov, x_ealive;
+    Buf sb_cand, sb_app, sb_J, sb_ctr;      // superbubbles.hip, the SUPERBUBBLES step: candidate sources, canonical fitting sources, the interiors' unitigs, its counters
 };
 
 // build_unitigs restricted by `alive` (device, one byte per row of the node table; null = every node) to the surviving nodes and the arcs between them; n_alive = how many;

@@ -28,7 +28,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
     to_basespace only, no tip or bubble removal.  Adds n_unitigs to the counters.
-    simplify (with contigs): a schedule of tip / bubble / component / edge-pruning steps, e.g. api.MAGIC_SIMPLIFY_STEPS or [(api.MDBG_SIMPLIFY_EDGES, 1, 0)] + those (the
+    simplify (with contigs): a schedule of tip / bubble / superbubble / component / edge-pruning steps, e.g. api.MAGIC_SIMPLIFY_STEPS, api.MAGIC_SUPERBUBBLE_STEPS or [(api.MDBG_SIMPLIFY_EDGES, 1, 0)] + those (the
     sketch store is still resident when the schedule runs, which is all an edge step needs; its count is simplify["total_edges_removed"]) — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
     Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
     A schedule may hold one (api.MDBG_SIMPLIFY_REPEATS, min_support, 0) step, which duplicates the unitigs the resident reads resolve (simplify["entries_copied"]); no read can be
@@ -296,7 +296,7 @@ def concat_records(seqs):
 
 def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
                strip_newlines=False, device=-1, contigs_fn=None, min_contig_len=100000, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-               keep_reads=False):
+               keep_reads=False, simplify_steps=None):
     """One pass over the reads, one graph per k (the k sweep of the reference's utils/multik:69-78): the reads are sketched once,
     the sketches stay resident on the GPU, and every k only clears and refills the counting table (mdbg_reset) and rebuilds nodes
     and edges.  Writes <prefix>-k<k>.gfa; -> {k: counters}.
@@ -309,12 +309,14 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     contigs_fn="unitigs": the built-in producer — the round's unitigs (Mdbg.graph_unitigs: `gfatools asm -u` + to_basespace, WITHOUT magic_simplify's tip and
     bubble rounds), stitched from the previous round's contigs and one more pass over the reads per round.
     contigs_fn="simplified": the same with the tip and bubble rounds — the contigs left after Mdbg.graph_simplify(api.MAGIC_SIMPLIFY_STEPS): the schedule of
-    magic_simplify's first gfatools line under this project's own rules (include/mdbg_hip.h), not gfatools parity.
+    magic_simplify's first gfatools line under this project's own rules (include/mdbg_hip.h), not gfatools parity.  simplify_steps: another schedule for that
+    producer, e.g. api.MAGIC_SUPERBUBBLE_STEPS (steps that need no resident reads: tips, bubbles, superbubbles, components).
     keep_reads (with the two built-in producers): the reads stay packed on the device (Mdbg(keep_reads=True)); a round's contigs are stitched there
     (mdbg_graph_contigs_device(min_contig_len)) and ingested for the next round straight from that device buffer, twice, with first ordinals 0 and C — the
     ordinals the concatenated contigs + contigs batch gives.  No Reader is opened after the first pass; same counters, same files."""
     import ctypes
     ks = list(ks)
+    schedule = MAGIC_SIMPLIFY_STEPS if simplify_steps is None else list(simplify_steps)
     on_device = bool(keep_reads and contigs_fn in ("unitigs", "simplified"))
     out = {}
     n_reads = n_bases = 0
@@ -354,7 +356,7 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
                 if contigs_fn == "unitigs":
                     m.graph_unitigs_device()
                 else:
-                    m.graph_simplify_device(MAGIC_SIMPLIFY_STEPS)
+                    m.graph_simplify_device(schedule)
                 cs = m.graph_contigs(min_contig_len, device=True)
                 dev_contigs = (ctypes.cast(cs.bases, ctypes.c_void_p).value or 0, ctypes.cast(cs.offsets, ctypes.c_void_p).value or 0, int(cs.n_contigs), int(cs.n_bases))
             elif contigs_fn in ("unitigs", "simplified"):
@@ -366,7 +368,7 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
                         for bases, offs in r2.batches(batch_bases, copy=False):
                             yield bases, offs, first
                             first += len(offs) - 1
-                plan, n_nodes = (m.graph_unitigs(raw=True), nodes["n_nodes"]) if contigs_fn == "unitigs" else (m.graph_simplify(MAGIC_SIMPLIFY_STEPS, raw=True)[0], None)
+                plan, n_nodes = (m.graph_unitigs(raw=True), nodes["n_nodes"]) if contigs_fn == "unitigs" else (m.graph_simplify(schedule, raw=True)[0], None)
                 with em.contigs(plan, fed(), n_nodes=n_nodes) as ctg:
                     contigs = [c for c in ctg.sequences() if len(c) >= min_contig_len]
             elif contigs_fn is not None:
