@@ -359,10 +359,7 @@ __global__ __launch_bounds__(256) void insert_listed_entries_kernel(TableArgs T,
     bool claimed, found;
     const u64 s = upsert_wave_h(T, ok, (u32)i, i, w, k, rev, h, claimed, found);      // (li = the store index: consecutive windows of a read are consecutive indices; no lane leaves early)
     if (claimed) { mread[i] = slot; if (T.claim) T.claim[i] = 1; }      // (the batch's bytes of the claim map were zeroed in front of the launch: api.inc, insert_resident_impl)
-    if (found) {
-        atomicAdd(&T.tab[s].count, 1u);
-        push_ordinal(T, s, ord);
-    }
+    if (found) record_hit(T, s, ord);
 }
 // (95 registers = five waves per SIMD; forced to six or eight — 12 / 84 bytes of scratch — the kernel is slower: 5.87 / 7.00 against 5.48 ms per 46 M windows)
 static void launch_listed_entries(const TableArgs& T, const u64* mh, u32* mread, const u64* roff, u64 m0, u64 m1, const u32* list, u64 n, u32 slot0, u32 n_reads, u64 first_ordinal,
@@ -428,10 +425,7 @@ __global__ __launch_bounds__(256) void insert_listed_span_kernel(TableArgs T, co
         bool claimed, found;
         const u64 s = upsert_wave(T, ok, li, i, sh_keys + li, k, claimed, found);      // (a wave-wide call: no lane leaves the loop early)
         if (claimed) { mread[i] = slot; if (T.claim) cl[li] = 1; }      // (mread: rep_ordinal() finds the representative's read through it; the rest of a listed batch's map is filled on demand)
-        if (found) {
-            atomicAdd(&T.tab[s].count, 1u);
-            push_ordinal(T, s, ord);
-        }
+        if (found) record_hit(T, s, ord);
     }
     if (T.claim) {                                 // the span's claim bytes, 64 consecutive bytes per wave and store
         __syncthreads();

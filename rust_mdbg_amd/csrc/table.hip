@@ -116,19 +116,32 @@ struct TableArgs {
 // fingerprint, and must stay independent of the position inside one rank's table.
 __device__ inline u64 home_slot(u64 h, u64 cap) { return __umul64hi(h << 24, cap); }
 
-// insert ordinal x into the slot's A smallest
+// insert ordinal x into the slot's A smallest (exact whatever the other lanes do: every level is an atomicMin, a displaced value moves one level down)
 __device__ inline void push_ordinal(const TableArgs& T, u64 s, u64 x) {
     Slot* e = T.tab + s;
     const u32 A = T.A;
-    // cheap reject: x larger than the current A-th smallest (values only ever decrease)
-    const u64* last = A == 1 ? &e->m1 : A == 2 ? &e->m2 : &T.mx[s * (A - 2) + (A - 3)];
-    if (x > load_relaxed(last)) return;
     u64 carry = x;
     for (u32 lvl = 0; lvl < A && carry != EMPTY; ++lvl) {
         u64* m = lvl == 0 ? &e->m1 : lvl == 1 ? &e->m2 : &T.mx[s * (A - 2) + (lvl - 2)];
         const u64 old = atomicMin((unsigned long long*)m, (unsigned long long)carry);
         if (old > carry) carry = old;          // I displaced `old`; it moves one level down
     }
+}
+// A later occurrence (ordinal x) of the key in slot s: one more sighting, and x is offered to the slot's A smallest.  The one owner of what follows a confirmed match
+// (the four insertion kernels, here and in owner.hip).
+// Order: (1) `last`, the slot's current A-th smallest (m1, m2 or the last of mx[]), is loaded FIRST — the probe fetched that line a moment ago, it is still in the XCD's L2;
+// (2) the cheap reject and, for an ordinal that passes, the atomicMin cascade; (3) the count, as the lane's LAST memory operation.  A device-scope atomic is executed at the
+// memory side and drops the line from the L2, and one without a return value stays counted in vmcnt for its whole round trip (600 - 3,000 cycles): with the count in front
+// (until round 6) the load of `last` was a certain L2 miss and the wait in front of the compare covered an atomic whose result nobody reads.
+// Exact: m1, m2 and mx[] only ever decrease, so a value of `last` that is stale — from before another lane's update, or from this XCD's L2 — is larger than or equal to the
+// true one.  It can only let an ordinal through to the cascade, which is exact on its own; it can never reject one that belongs.  The count is a sum: its place in the order
+// does not change it, and nobody reads it before the kernel has ended.
+__device__ inline void record_hit(const TableArgs& T, u64 s, u64 x) {
+    Slot* e = T.tab + s;
+    const u32 A = T.A;
+    const u64* last = A == 1 ? &e->m1 : A == 2 ? &e->m2 : &T.mx[s * (A - 2) + (A - 3)];
+    if (x <= load_relaxed(last)) push_ordinal(T, s, x);      // (else: x is larger than the A-th smallest — values only ever decrease)
+    atomicAdd(&e->count, 1u);
 }
 
 // find-or-claim the slot of a key; same_key(word) = full comparison of my key with the representative a slot word names.
@@ -429,10 +442,7 @@ __global__ __launch_bounds__(256) void insert_windows_kernel(TableArgs T, const 
         bool claimed, found;
         const u64 s = upsert_wave(T, act, li, i, sh_keys + li, k, claimed, found);
         if (claimed && T.claim) cl[li] = 1;
-        if (found) {
-            atomicAdd(&T.tab[s].count, 1u);
-            push_ordinal(T, s, ord);
-        }
+        if (found) record_hit(T, s, ord);
     }
     if (T.claim) {                             // the span's claim bytes, 64 consecutive bytes per wave and store (a slice's last workgroup stops at its end: n_lim)
         __syncthreads();
@@ -458,8 +468,7 @@ __global__ __launch_bounds__(256) void insert_records_kernel(TableArgs T, u64 r0
     bool claimed;
     const u64 s = upsert_slot(T, h, (1ull << 33) | (u64)(u32)r, [&](u64 word) { return same_key_window(T.ks, word, key, false); }, claimed);   // record keys are canonical
     if (claimed || s == ~0ull) return;
-    atomicAdd(&T.tab[s].count, 1u);
-    push_ordinal(T, s, key[k]);
+    record_hit(T, s, key[k]);
     (void)n_windows;
 }
 void launch_insert_records(const TableArgs& T, u64 r0, u64 r1, u64* n_windows, hipStream_t s) {
