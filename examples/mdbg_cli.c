@@ -6,7 +6,9 @@
  *   on that side); -e N: an edge-pruning step in the schedule (every edge record crossed by fewer than N resident reads goes where reads leave its source
  *   and enter its target another way: MDBG_SIMPLIFY_EDGES, mdbg_hip.h); -r N: a repeat step (every unitig the resident reads resolve at min_support N is
  *   duplicated, one copy per strong transit key, so the contigs cross it: MDBG_SIMPLIFY_REPEATS; one per schedule, no -e behind it; the copied entries are printed,
- *   and --transits then writes no .msimpl.transits.tsv: no read is placed on a list with copies); -B N,L: a superbubble step (a bubble whose inside branches again, of at most
+ *   and --transits then writes no .msimpl.transits.tsv: no read is placed on a list with copies); -R N: a nested repeat step (MDBG_SIMPLIFY_NESTED: the same at min_support N on a list that may
+ *   hold copies, so it may stand behind -r or another -R, any number of times, and resolves a repeat that is one unitig only once its middle has been resolved; no
+ *   -e and no -r behind it); -B N,L: a superbubble step (a bubble whose inside branches again, of at most
  *   N entries and L bases inside, 0 = no limit on that side, keeps the path whose weakest unitig is strongest: MDBG_SIMPLIFY_SUPERBUBBLES); --components: the number of connected components of the unitig graph and the largest one (mdbg_graph_components)
  *   --read-paths (implies --contigs): the resident reads threaded through the unitig list (mdbg_graph_read_paths, in ranges of 2^20 reads): one summary line
  *   --junctions (implies --contigs): the reads that cross each edge record of the unitig list (mdbg_graph_junctions, in ranges of 2^20 reads, the supports summed):
@@ -163,7 +165,7 @@ int main(int argc, char** argv) {
     const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0; uint64_t transits = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
-    /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L / -e N / -r N / -B N,L append steps of their own, in command-line order */
+    /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L / -e N / -r N / -R N / -B N,L append steps of their own, in command-line order */
     static const mdbg_simplify_step magic[] = {{MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000},
         {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000},
         {MDBG_SIMPLIFY_BUBBLES, 0, 100000}, {MDBG_SIMPLIFY_TIPS, 10, 50000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}, {MDBG_SIMPLIFY_TIPS, 10, 150000}, {MDBG_SIMPLIFY_BUBBLES, 0, 1000000}};
@@ -219,7 +221,14 @@ int main(int argc, char** argv) {
             char* end = NULL; const char* a = argv[++i];
             mdbg_simplify_step st; st.kind = MDBG_SIMPLIFY_REPEATS; st.max_bases = 0;
             st.max_nodes = (uint32_t)strtoul(a, &end, 10);              /* (the field carries min_support for this kind) */
-            if (*end || !*a || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c / -e / -r\n"); return 2; }
+            if (*end || !*a || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c / -e / -r / -R\n"); return 2; }
+            steps[n_steps++] = st; simplify = 1;
+        }
+        else if (!strcmp(argv[i], "-R") && i + 1 < argc) {              /* a repeat step on a list that may hold copies: behind -r or another -R (no -e, no -r behind it) */
+            char* end = NULL; const char* a = argv[++i];
+            mdbg_simplify_step st; st.kind = MDBG_SIMPLIFY_NESTED; st.max_bases = 0;
+            st.max_nodes = (uint32_t)strtoul(a, &end, 10);              /* (the field carries min_support for this kind) */
+            if (*end || !*a || n_steps >= MAX_STEPS) { fprintf(stderr, "bad or too many -t / -b / -c / -e / -r / -R\n"); return 2; }
             steps[n_steps++] = st; simplify = 1;
         }
         else if (!strcmp(argv[i], "-B") && i + 1 < argc) {              /* bubbles whose inside branches: a bubble of at most N entries and L bases inside keeps its strongest path */
@@ -241,7 +250,7 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
     if (simplify || components || read_paths || junctions || transits) contigs = 1;
     if (!contigs) keep_reads = 0;
@@ -357,7 +366,7 @@ int main(int argc, char** argv) {
         rc = mdbg_simplify_edges_removed(ctx, &edges_removed, &total_edges_removed);
         if (rc) die(ctx, "mdbg_simplify_edges_removed", rc);
         for (uint32_t j = 0; j < ss.n_steps; ++j)
-            if (steps[j].kind == MDBG_SIMPLIFY_REPEATS) { printf("simplify step %u (repeats %u)\n", j + 1, steps[j].max_nodes); repeat_steps = 1; }
+            if (steps[j].kind == MDBG_SIMPLIFY_REPEATS || steps[j].kind == MDBG_SIMPLIFY_NESTED) { printf("simplify step %u (%s %u)\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_NESTED ? "nested repeats" : "repeats", steps[j].max_nodes); repeat_steps = 1; }
             else if (steps[j].kind == MDBG_SIMPLIFY_EDGES) { printf("simplify step %u (edges %u): %llu edge records removed\n", j + 1, steps[j].max_nodes, (unsigned long long)edges_removed[j]); edge_steps = 1; }
             else printf("simplify step %u (%s %u,%llu): %llu unitigs, %llu nodes removed\n", j + 1, steps[j].kind == MDBG_SIMPLIFY_TIPS ? "tips" : steps[j].kind == MDBG_SIMPLIFY_BUBBLES ? "bubbles" : steps[j].kind == MDBG_SIMPLIFY_SUPERBUBBLES ? "superbubbles" : "components", steps[j].max_nodes,
                    (unsigned long long)steps[j].max_bases, (unsigned long long)ss.unitigs_removed[j], (unsigned long long)ss.nodes_removed[j]);

@@ -432,9 +432,40 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  *   behind a REPEATS step (reads cannot be placed on copied nodes).  MDBG_E_CAPACITY: 2^30 rows including the copies, or 2^32 records including the added ones.
  *   A list that holds copies: mdbg_graph_read_paths*, mdbg_graph_junctions* and mdbg_graph_transits* on it answer MDBG_E_STATE (a table row would belong to several
  *   entries); the context stays usable, and a list built by a REPEATS step that copied nothing is placed as always.  mdbg_graph_components*, mdbg_graph_contigs* and
- *   the emitters work on it unchanged: they read the list, not the table.  Placing reads on copies, and with it a second round of resolution, is not built.
+ *   the emitters work on it unchanged: they read the list, not the table.  Placing reads on copies, and with it a second round of resolution, is the NESTED
+ *   kind's (below); the REPEATS kind keeps meaning "the graph holds no copies", and everything said here about it stays as it is.
  *   The number of copied entries follows from the identity above (a schedule holds at most one such step); a per-step count of resolved unitigs would need a new
  *   entry point and waits for a change that may touch the number of prototypes.
+ *   NESTED, {MDBG_SIMPLIFY_NESTED, min_support, 0}: a repeats step that may stand anywhere in a schedule, in particular behind a REPEATS step or another NESTED
+ *   step, any number of times: a repeat whose middle occurs elsewhere too becomes one unitig only when its middle has been resolved, and the next step resolves it.
+ *   max_nodes carries min_support (>= 1) and max_bases is reserved (0).  The step decides against the current list L as it is when the step starts, copies included,
+ *   with the transits of L over the whole resident store under the placement on a list that holds copies (below).  Verdicts, strong keys, copies, arcs and
+ *   consequences are the REPEATS text, with these additions.
+ *   Originals.  origin(x) of a node is the DbgEntry.index of the table row it descends from: an original is its own origin, the origin of a copy of a copy is the
+ *   table row's.  A copy has every column of the node it was copied from.
+ *   Indices.  X stays 1 + the largest DbgEntry.index of the node table for the whole schedule; the copies of a later step continue the numbering behind all earlier
+ *   copies of the schedule, in the same order (ascending u, then i, then j).
+ *   Reported list.  At the end of the schedule node[] reports the origin.  n_entries == rows of the node table - total_nodes_removed + all copies of the schedule.
+ *   No copies yet.  On a graph that holds no copies the step IS the REPEATS step: the same launches, the same waits, the same arrays.
+ *   MDBG_E_PARAM while the schedule is validated: min_support == 0, max_bases != 0, an EDGES step behind a NESTED step (edge pruning on a graph that holds copies is
+ *   not in this change), a REPEATS step behind a NESTED step.  MDBG_E_CAPACITY and the defect flags are those of REPEATS.  After a schedule whose NESTED step copied
+ *   something mdbg_graph_read_paths*, mdbg_graph_junctions* and mdbg_graph_transits* go on answering MDBG_E_STATE, as after REPEATS.
+ *   PLACEMENT ON A LIST THAT HOLDS COPIES.  row(e) of list entry e is the table row of origin(node of e).  mult(r) is the number of entries e of L with row(e) == r;
+ *   removed nodes are not entries, so a copy that a TIPS step removed makes its row unique again.  A window whose key is row r of the node table (the test of
+ *   mdbg_graph_read_paths) is: not placed if mult(r) == 0; UNIQUE if mult(r) == 1, placed on that entry as always; AMBIGUOUS if mult(r) >= 2.  Windows are numbered
+ *   along their read.  For an AMBIGUOUS window w the LEFT ANCHOR is the nearest window a < w of the same read that is not AMBIGUOUS, provided it is UNIQUE: if that
+ *   window is not placed, or the read starts first, w has no left anchor.  With the anchor on entry e_a in strand s_a the LEFT CANDIDATE is the entry
+ *   e = e_a + (w - a) if s_a == 0, e_a - (w - a) if s_a == 1.  It is VALID iff e lies in the same unitig as e_a (no wrap, also on a circular unitig), row(e) is w's
+ *   row, and rev(w) XOR (ori[e] == '-') == s_a.  The RIGHT ANCHOR b > w and the RIGHT CANDIDATE are defined alike: e_b - (b - w) if s_b == 0, e_b + (b - w) if
+ *   s_b == 1.  Verdict on w: both candidates valid and equal, or exactly one valid: w is placed there, in the anchor's strand; both valid and different (a CONFLICT)
+ *   or none valid: w is not placed.  Links, crossings, explained crossings, transits and the consequence "a transit walks all of one unitig" are the existing text
+ *   over these placements.  Every window decides alone from its own two anchors, so the result is order-free and two calls give identical arrays.
+ *   Waits.  A NESTED step on a graph with copies waits as a REPEATS step does: once for its transit stage (the placement's extra launches — one kernel, two scans,
+ *   one kernel — ride in it) and, if something resolves, twice more; the one wait at the end of the schedule maps node[] to the origins of all copies.
+ *   The placement counts its ambiguous windows and those it placed (resolved), found in conflict, or left without a valid candidate (unanchored).  The ABI has no
+ *   room for them: with MDBG_NESTED_STATS in the environment a simplify call with a NESTED step writes them, summed over its NESTED steps on a graph with
+ *   copies, as one line to stderr.  That line is a diagnostic for measurements and tests, NOT part of this interface: its name and form may change or go without
+ *   a new ABI version, and no program should depend on it.
  *   SUPERBUBBLES, {MDBG_SIMPLIFY_SUPERBUBBLES, max_nodes, max_bases}: what `gfatools asm -b` (gfa_pop_bubble) is after — a bubble whose inside branches again, is
  *   cross-linked or holds bubbles of its own — by an order-free rule.  Like every kind the step decides against the graph as it is when the step starts.  Vertices:
  *   the oriented current unitigs (u, strand).  Arcs: the unitig edge records between surviving nodes whose arc is not in D, plus their mirrors; parallel records
@@ -470,7 +501,8 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
  * buffers and placement scratch: a transit result the caller holds ends with a simplify call that has a REPEATS step; after such a call mdbg_transits_ms gives the
  * device time of the step's transit stage.  It waits once for its transit stage and, if something resolves, twice more (the totals that size the copies, its
  * defect flag); one more wait at the end of the schedule maps node[] to the originals.
- * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, an EDGES or REPEATS step with min_support == 0 or max_bases != 0, a second REPEATS step, an EDGES step behind a REPEATS step, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
+ * A NESTED step needs and uses what a REPEATS step does.
+ * MDBG_E_PARAM: an unknown kind, a COMPONENTS step without a limit, an EDGES, REPEATS or NESTED step with min_support == 0 or max_bases != 0, a second REPEATS step, an EDGES step behind a REPEATS or NESTED step, a REPEATS step behind a NESTED step, steps == NULL with n_steps > 0, stats == NULL.  stats->unitigs_removed / nodes_removed: n_steps HOST
  * entries owned by the context (valid like the list); n_compactions: compactions run (a step that removes nothing is followed by none);
  * n_syncs: host synchronisations of the call (per step: those of one compaction + 1; a COMPONENTS step adds none of its own; an EDGES step that has
  * records and resident reads to look at waits twice — the one wait of its junction stage, then its own counter, which the junction stage's wait cannot
@@ -484,6 +516,7 @@ int mdbg_graph_unitigs_device(mdbg_ctx* ctx, mdbg_unitig_list* out);
 #define MDBG_SIMPLIFY_EDGES 8u     /* {EDGES, min_support, 0} */
 #define MDBG_SIMPLIFY_REPEATS 16u  /* {REPEATS, min_support, 0} */
 #define MDBG_SIMPLIFY_SUPERBUBBLES 64u   /* {SUPERBUBBLES, max_nodes, max_bases}; 32 is no kind */
+#define MDBG_SIMPLIFY_NESTED 128u  /* {NESTED, min_support, 0} */
 #define MDBG_SUPERBUBBLE_MAX_UNITIGS 64u /* (f): the interior and the sink of one bubble fit the 2 x 64 slots of one wave */
 typedef struct mdbg_simplify_step { uint32_t kind, max_nodes; uint64_t max_bases; } mdbg_simplify_step;
 typedef struct mdbg_simplify_stats {

@@ -281,6 +281,7 @@ MDBG_SIMPLIFY_TIPS, MDBG_SIMPLIFY_BUBBLES = 1, 2
 MDBG_SIMPLIFY_COMPONENTS = 4      # (kind, max_nodes, max_bases): every unitig of a non-circular connected component of at most max_nodes nodes and max_bases bases goes
 MDBG_SIMPLIFY_EDGES = 8           # (kind, min_support, 0): every edge record crossed by fewer than min_support resident reads goes where reads leave its source and enter its target another way
 MDBG_SIMPLIFY_REPEATS = 16        # (kind, min_support, 0): every unitig the resident reads resolve at min_support (graph_transits) is duplicated, one copy per strong key; at most one per schedule, no EDGES step behind it
+MDBG_SIMPLIFY_NESTED = 128        # (kind, min_support, 0): a repeats step that may stand behind a REPEATS step or another NESTED step: the reads are placed on the list with its copies, so a repeat that only exists once its middle is resolved is resolved too; no EDGES or REPEATS step behind it
 MDBG_SIMPLIFY_SUPERBUBBLES = 64   # (kind, max_nodes, max_bases): every bubble whose inside may branch (at most max_nodes entries and max_bases bases inside, 0 = no limit) keeps the path whose weakest unitig is strongest
 MDBG_SUPERBUBBLE_MAX_UNITIGS = 64 # the unitigs inside one such bubble
 _T, _B = (MDBG_SIMPLIFY_TIPS, 10, 50000), (MDBG_SIMPLIFY_BUBBLES, 0, 100000)
@@ -743,8 +744,8 @@ class Mdbg:
         return u
 
     def _simplify_stats(self, st, steps, n_entries):
-        """entries_copied: the entries a REPEATS step added, from n_entries == rows of the node table - total_nodes_removed + copies (exact: a schedule holds at
-        most one such step); 0 for a schedule without one, None if this object has not seen the finalize call that made the table"""
+        """entries_copied: the entries the REPEATS and NESTED steps added, from n_entries == rows of the node table - total_nodes_removed + all copies of the
+        schedule; 0 for a schedule without such a step, None if this object has not seen the finalize call that made the table"""
         n = int(st.n_steps)
         per_step, total = C.POINTER(C.c_uint64)(), C.c_uint64()
         self._chk(self.L.mdbg_simplify_edges_removed(self.h, C.byref(per_step), C.byref(total)))
@@ -754,7 +755,7 @@ class Mdbg:
                     n_rounds_total=int(st.n_rounds_total), n_syncs=int(st.n_syncs), entries_copied=self._entries_copied(steps, int(n_entries), int(st.total_nodes_removed)))
 
     def _entries_copied(self, steps, n_entries, total_nodes_removed):
-        if not any(int(s[0]) == MDBG_SIMPLIFY_REPEATS for s in steps) or n_entries == 0:
+        if not any(int(s[0]) in (MDBG_SIMPLIFY_REPEATS, MDBG_SIMPLIFY_NESTED) for s in steps) or n_entries == 0:
             return 0
         rows = getattr(self, "_table_rows", None)
         return None if rows is None else n_entries - (rows - total_nodes_removed)

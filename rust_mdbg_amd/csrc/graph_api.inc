@@ -1,7 +1,7 @@
 // graph_api.inc — C ABI of the graph stages on the last finalized node table: edges (edges.hip), unitigs (unitigs.hip), tip, bubble and small-component
 // removal (simplify.hip), connected components (components.hip), stitched contigs (contigs.hip), node sequences (node_seqs.hip), and the stages that
-// decide with the resident reads: read paths (read_paths.hip), read support per junction (junctions.hip) and transits (transits.hip; a REPEATS step of a simplify
-// schedule runs them too and duplicates what they resolve, repeats.hip), each ONE call over the
+// decide with the resident reads: read paths (read_paths.hip), read support per junction (junctions.hip) and transits (transits.hip; a REPEATS or NESTED step of a
+// simplify schedule runs them too and duplicates what they resolve, repeats.hip), each ONE call over the
 // context's one placement scratch (placement.hip, c->res.placement) and the one window placer below.
 // Host code; included by api.inc, whose context, fail(), MDBG_ENTER and HandOver it uses; what is current is asked of c->res (results.inc).
 
@@ -81,7 +81,7 @@ static int stage_prologue(mdbg_ctx* c, const char* what_is, uint64_t first_read,
     int e;
     if ((e = refuse_multi_gpu(c, what_is)) || (e = refuse_without_unitig_list(c))) return e;
     if (c->res.unitig_list_copies())
-        return fail(c, MDBG_E_STATE, "the current unitig list holds copies made by a REPEATS step: a row of the node table belongs to several entries, so no read can be placed on it");
+        return fail(c, MDBG_E_STATE, "the current unitig list holds copies made by a REPEATS or NESTED step: a row of the node table belongs to several entries, so no read can be placed on it");
     const UnitigResult& ul = c->res.unitigs.last;
     if ((e = store_range(c, ul.n_unitigs, ul.n_entries, first_read, max_reads, pw, empty)) || *empty) return e;
     return with_records ? refuse_too_many_records(c, ul.edges.n) : MDBG_OK;
@@ -126,18 +126,22 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     memset(out, 0, sizeof *out);
     Results& R = c->res;
     auto& UL = R.unitigs;
-    bool with_components = false, with_edges = false, with_repeats = false;
+    bool with_components = false, with_edges = false, with_repeats = false, with_nested = false;      // with_repeats: a REPEATS step was seen; with_nested: a NESTED step
     if (stats) {
         memset(stats, 0, sizeof *stats);
         for (uint32_t i = 0; i < n_steps; ++i) {
             const uint32_t kind = steps[i].kind;
-            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES && kind != MDBG_SIMPLIFY_REPEATS && kind != MDBG_SIMPLIFY_SUPERBUBBLES)
+            if (kind != MDBG_SIMPLIFY_TIPS && kind != MDBG_SIMPLIFY_BUBBLES && kind != MDBG_SIMPLIFY_COMPONENTS && kind != MDBG_SIMPLIFY_EDGES && kind != MDBG_SIMPLIFY_REPEATS && kind != MDBG_SIMPLIFY_SUPERBUBBLES && kind != MDBG_SIMPLIFY_NESTED)
                 return fail(c, MDBG_E_PARAM, "unknown kind of simplification step");
             if (kind == MDBG_SIMPLIFY_REPEATS && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
                 return fail(c, MDBG_E_PARAM, "a repeat step takes {REPEATS, min_support >= 1, 0}");
             if (kind == MDBG_SIMPLIFY_REPEATS && with_repeats) return fail(c, MDBG_E_PARAM, "a schedule holds at most one REPEATS step: reads cannot be placed on copied nodes");
             if (kind == MDBG_SIMPLIFY_EDGES && with_repeats) return fail(c, MDBG_E_PARAM, "an EDGES step cannot follow a REPEATS step: reads cannot be placed on copied nodes");
-            with_repeats |= kind == MDBG_SIMPLIFY_REPEATS;
+            if (kind == MDBG_SIMPLIFY_NESTED && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
+                return fail(c, MDBG_E_PARAM, "a nested repeat step takes {NESTED, min_support >= 1, 0}");
+            if (kind == MDBG_SIMPLIFY_EDGES && with_nested) return fail(c, MDBG_E_PARAM, "an EDGES step cannot follow a NESTED step: edge pruning on a graph that holds copies is not built");
+            if (kind == MDBG_SIMPLIFY_REPEATS && with_nested) return fail(c, MDBG_E_PARAM, "a REPEATS step cannot follow a NESTED step: REPEATS means the graph holds no copies (use NESTED)");
+            with_repeats |= kind == MDBG_SIMPLIFY_REPEATS; with_nested |= kind == MDBG_SIMPLIFY_NESTED;
             if (kind == MDBG_SIMPLIFY_EDGES && (steps[i].max_nodes == 0 || steps[i].max_bases != 0))
                 return fail(c, MDBG_E_PARAM, "an edge step takes {EDGES, min_support >= 1, 0}");
             with_edges |= kind == MDBG_SIMPLIFY_EDGES;
@@ -155,6 +159,7 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (R.n_rows() == 0) { R.unitig_list_is(UnitigResult{}); return MDBG_OK; }
     if (with_components) R.comps.buf.get();
     SimplifySupport sup{}; PlaceWindows pw{};
+    with_repeats |= with_nested;                     // from here on: a step that runs the transit stage
     if (with_edges || with_repeats) {                // what the junction support and the transits ask, before anything of the schedule is launched
         int e; bool empty;
         if ((e = refuse_too_many_records(c, R.edges.last.n)) || (e = store_range(c, 1, R.n_rows(), 0, 0, &pw, &empty))) return e;
@@ -174,9 +179,12 @@ static int unitigs_impl(mdbg_ctx* c, const mdbg_simplify_step* steps, uint32_t n
     if (he != hipSuccess) return fail_hip(c, "build_unitigs", he);
     if (with_edges) R.junctions.ms = si.junction_ms;
     if (with_repeats) R.transits.ms = si.transit_ms;
+    if (with_nested && getenv("MDBG_NESTED_STATS"))      // (diagnostic, no part of the interface: mdbg_simplify_stats has no room for these four counts)
+        fprintf(stderr, "mdbg nested: ambiguous %llu resolved %llu conflicts %llu unanchored %llu\n", (unsigned long long)si.ambiguous, (unsigned long long)si.resolved,
+                (unsigned long long)si.conflicts, (unsigned long long)si.unanchored);
     if (broken && si.junction_defect) return stage_defect(c, si.junction_defect);
     if (broken && si.transit_defect) return stage_defect(c, si.transit_defect);
-    if (broken && si.repeats_too_large) return fail(c, MDBG_E_CAPACITY, "the copies of a REPEATS step would bring the graph to 2^30 nodes or 2^32 edge records");
+    if (broken && si.repeats_too_large) return fail(c, MDBG_E_CAPACITY, "the copies of a REPEATS step or NESTED step would bring the graph to 2^30 nodes or 2^32 edge records");
     if (broken && si.repeats_defect)
         return fail(c, MDBG_E_DEVICE, si.repeats_defect & RX_DEFECT_MATCH ? "an end of an edge record at a resolved unitig belongs to no strong transit key, or to two: nothing was copied"
                                                                              : "a vertex of the last compaction or a transit row lies outside the unitig list: nothing was copied");

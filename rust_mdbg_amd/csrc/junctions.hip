@@ -110,11 +110,11 @@ JunctionBuffers* junction_buffers_create() { return new JunctionBuffers(); }
 void junction_buffers_destroy(JunctionBuffers* b) { delete b; }
 
 hipError_t junctions_run(JunctionBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
-                         hipStream_t s, JunctionResult* out) {
+                         hipStream_t s, JunctionResult* out, const OriginMap& om) {
     memset(out, 0, sizeof *out);
     const u64 R = ul.edges.n, n_idx = rg.i1 - rg.i0;
     // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
-    GHIP(placement_reserve(P, ul, n_rows, rg, true));
+    GHIP(placement_reserve(P, ul, n_rows, rg, true, om));
     GHIP(B->slot.ensure(R * 8 + 8)); GHIP(B->support.ensure(R * 8 + 8));
     GHIP(B->mkey.ensure(n_idx * 8 + 8)); GHIP(B->mkey_sorted.ensure(n_idx * 8 + 8)); GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
     GHIP(B->mu1.ensure(n_idx * 4 + 4)); GHIP(B->me1.ensure(n_idx * 4 + 4)); GHIP(B->ms1.ensure(n_idx + 4)); GHIP(B->mu2.ensure(n_idx * 4 + 4)); GHIP(B->me2.ensure(n_idx * 4 + 4)); GHIP(B->ms2.ensure(n_idx + 4));
@@ -128,7 +128,7 @@ hipError_t junctions_run(JunctionBuffers* B, PlacementBuffers* P, const UnitigRe
     GHIP(B->timer.start(s));
     if (R) GHIP(hipMemsetAsync(B->slot.p, 0, R * 8, s));
     PlacementView V;
-    GHIP(placement_queue(P, ul, index, n_rows, rg, true, JX_C_N, placer, s, &V));
+    GHIP(placement_queue(P, ul, index, n_rows, rg, true, JX_C_N, placer, s, &V, om));
     const JxArgs a = args_of(B, V, ul, rg);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);

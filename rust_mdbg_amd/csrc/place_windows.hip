@@ -27,6 +27,9 @@ __device__ inline u64 find_slot_bounded(const TableArgs& T, u64 h, EqFn same_key
 constexpr int PW_SPAN = 1024;      // minimizer indices per workgroup, four per lane
 // the kernel's dynamic LDS: the PW_SPAN + k - 1 hashes a workgroup's windows cover (+ one)
 static size_t place_windows_lds(const TableArgs& T) { return ((size_t)PW_SPAN + T.ks.k) * sizeof(u64); }
+// COPIES: the list holds copies (P.mult is set): a row that belongs to two or more entries gives the ambiguous code row | RP_AMBIGUOUS | rev << 31, which
+// resolve_kernel (placement.hip) settles; such a window is not counted as placed here.  Everything else is the plain instantiation's.
+template <bool COPIES>
 __global__ __launch_bounds__(256) void place_windows_kernel(TableArgs T, FinArgs F, u64 fin_words, ReadPathPlan P, const u64* __restrict__ mh, const u32* __restrict__ mread,
                                                             const u64* __restrict__ roff, u64 i0, u64 i1) {
     extern __shared__ u64 sh_keys[];
@@ -68,7 +71,8 @@ __global__ __launch_bounds__(256) void place_windows_kernel(TableArgs T, FinArgs
                     }
                     if (row < P.n_rows) {
                         const u32 e = P.entry_of_row[row];
-                        if (e != RP_NONE) { code = e | ((rev != (P.ori[e] == '-')) ? RP_STRAND : 0u); ++n_placed; }
+                        if (COPIES && P.mult[row] >= 2u) code = (u32)row | RP_AMBIGUOUS | (rev ? RP_STRAND : 0u);
+                        else if (e != RP_NONE) { code = e | ((rev != (P.ori[e] == '-')) ? RP_STRAND : 0u); ++n_placed; }
                     } else defect |= RP_DEFECT_ROW;
                 }
             }
@@ -87,5 +91,7 @@ __global__ __launch_bounds__(256) void place_windows_kernel(TableArgs T, FinArgs
 }
 void launch_place_windows(const TableArgs& T, const FinArgs& F, u64 fin_words, const ReadPathPlan& P, const u64* mh, const u32* mread, const u64* roff, u64 i0, u64 i1, hipStream_t s) {
     if (i1 <= i0) return;
-    hipLaunchKernelGGL(place_windows_kernel, dim3((unsigned)((i1 - i0 + PW_SPAN - 1) / PW_SPAN)), dim3(256), place_windows_lds(T), s, T, F, fin_words, P, mh, mread, roff, i0, i1);
+    const dim3 grid((unsigned)((i1 - i0 + PW_SPAN - 1) / PW_SPAN));
+    if (P.mult) hipLaunchKernelGGL(place_windows_kernel<true>, grid, dim3(256), place_windows_lds(T), s, T, F, fin_words, P, mh, mread, roff, i0, i1);
+    else hipLaunchKernelGGL(place_windows_kernel<false>, grid, dim3(256), place_windows_lds(T), s, T, F, fin_words, P, mh, mread, roff, i0, i1);
 }

@@ -40,7 +40,8 @@ __device__ inline bool is_link_of_codes(u32 pc, u32 c, const u32* unitig_of_entr
     return !((pc ^ c) & RP_STRAND) && unitig_of_entry[e] == unitig_of_entry[pe] && (c & RP_STRAND ? pe == e + 1 : e == pe + 1);
 }
 __device__ inline void set_defect(u64* counters, u32 what) { atomicOr((unsigned long long*)(counters + RP_C_DEFECT), (unsigned long long)what); }
-// the workgroup's counts (256 threads, NC of them per thread): one atomic each on counters[first .. first + NC)
+// the workgroup's counts (256 threads, NC of them per thread): one atomic each on counters[first .. first + NC).  cnt[] is reduced IN PLACE: on return the first
+// lane of every wave holds its wave's sums (the other lanes partial ones).  resolve_kernel (placement.hip) relies on that for a second counter; keep it
 template <int NC> __device__ inline void block_add(u32 (&cnt)[NC], u64* counters, int first) {
     __shared__ u32 wsum[NC][4];
 #pragma unroll

@@ -5,8 +5,12 @@
 //
 // Coordinates.  A node vertex is v = 2 * row + minus (unitigs.hip); the LIST vertex of the definitions is 2 * (offsets[u] + j) + s (placement_dev.h).  list_vertex
 // maps the first to the second through the ranking: v lies on a kept chain (strand 0) or comp(v) does (strand 1), at entry hoff[head] + D.
-// Copy (u, i, j), i >= 1, is row n + rowbase[u] + (i - 1) * m(u) + j with index X + that offset; rowbase is a scan over the unitigs, so the order is the
-// definition's (ascending u, then i, then j).
+// Copy (u, i, j), i >= 1, is row n + rowbase[u] + (i - 1) * m(u) + j with index X + C0 + that offset, C0 the copies of the schedule's earlier steps (a NESTED
+// step behind a step that copied; else 0); rowbase is a scan over the unitigs, so the order is the definition's (ascending u, then i, then j).  X comes from
+// the node table, and a copy's origin is resolved through the earlier steps' origin[], so it always names a table row.
+//
+// With earlier copies the node columns, records and masks the step reads already live in the x_* blocks: it then grows into FRESH blocks, copies the old contents
+// (origin[] included) over, and swaps the blocks in behind its last wait; the old ones go back to the block cache.  Without, it grows the x_* blocks themselves.
 //
 //   strong_kernel    one thread per transit row: flag = the key is strong and its unitig RESOLVED;  (rocPRIM) rank = exclusive scan of the flags: row d of unitig u
 //                    is the strong key number rank[d] - rank[first row of u]
@@ -38,7 +42,8 @@ struct RxArgs {
     const u32* n_in; const u8* verdict;
     // the step's own
     u8* strong; const u32* rank; u64* rows; const u64* rowbase; u32* ecnt; const u64* ebase; u32* defect;
-    u32 X; u64 C, EC;                                       // the totals of the two scans: no copy and no added record lies behind them
+    u32 X; u64 C, EC;                                       // X: the first index of THIS step's copies; the totals of the two scans: no copy and no added record lies behind them
+    u32 X0; u64 C0; const u32* origin0;                     // the earlier steps': their first index (1 + the table's largest), their copies, their origin[]
     UnitigNodes src; EdgeResult esrc;
     u32* x_index; u16* x_abund; u64* x_shift; u64* x_sread; u64* x_sstart; u64* x_send; u8* x_rev; u8* x_alive; u32* x_origin;
     u32* x_n1; u8* x_o1; u32* x_n2; u8* x_o2; u32* x_ov; u8* x_ealive;
@@ -107,7 +112,8 @@ __global__ __launch_bounds__(256) void copy_kernel(RxArgs a) {
         const u64 c = copy_of(a, u, i, j), d = (u64)a.n + c;
         if (c >= a.C) { rx_defect(a, RX_DEFECT_SHAPE); return; }      // cannot happen (the host has sized the blocks by the scan's total); never write outside
         a.x_index[d] = a.X + (u32)c; a.x_abund[d] = abund; a.x_shift[2 * d] = s0; a.x_shift[2 * d + 1] = s1;
-        a.x_sread[d] = sread; a.x_sstart[d] = sstart; a.x_send[d] = send; a.x_rev[d] = rev; a.x_alive[d] = 1; a.x_origin[c] = index;
+        a.x_sread[d] = sread; a.x_sstart[d] = sstart; a.x_send[d] = send; a.x_rev[d] = rev; a.x_alive[d] = 1;
+            a.x_origin[c] = index >= a.X0 && (u64)(index - a.X0) < a.C0 ? a.origin0[index - a.X0] : index;      // (x_origin: this step's part of the array)
     }
 }
 
@@ -175,8 +181,14 @@ __global__ __launch_bounds__(256) void report_kernel(u64 n_entries, u32* __restr
 
 }  // namespace
 
+namespace {
+void swap_blocks(Buf& a, Buf& b) { void* p = a.p; a.p = b.p; b.p = p; const size_t c = a.cap; a.cap = b.cap; b.cap = c; }
+}  // namespace
+
 hipError_t repeats_run(UnitigBuffers* B, const TransitResult& tr, uint64_t min_support, const UnitigResult& ul, const UnitigNodes& nd, const EdgeResult& ed, const uint8_t* alive,
-                       const uint8_t* edge_alive, hipStream_t s, RepeatsResult* out) {
+                       const uint8_t* edge_alive, const uint32_t* table_last_index, const RepeatsResult* earlier, hipStream_t s, RepeatsResult* out) {
+    const u64 C0 = earlier ? earlier->total_copies : 0;
+    const u32* origin0 = C0 ? earlier->origin : nullptr;
     memset(out, 0, sizeof *out);
     const u64 n = nd.n, E = ed.n, U = ul.n_unitigs, T = tr.n_transits;
     if (n == 0 || n >= (1ull << 30) || E == 0 || U == 0 || T == 0 || tr.n_unitigs != U || !alive) return hipErrorInvalidValue;
@@ -201,20 +213,27 @@ hipError_t repeats_run(UnitigBuffers* B, const TransitResult& tr, uint64_t min_s
     ScanLast<u64, u64> rows; ScanLast<u32, u64> recs; u32 largest = 0;
     GHIP(scan_total((const u64*)a.rows, a.rowbase, (size_t)U, s, &rows));
     GHIP(scan_total((const u32*)a.ecnt, a.ebase, (size_t)E, s, &recs));
-    GHIP(hipMemcpyAsync(&largest, nd.index + (n - 1), 4, hipMemcpyDeviceToHost, s));      // (the table is sorted by index)
+    GHIP(hipMemcpyAsync(&largest, table_last_index, 4, hipMemcpyDeviceToHost, s));      // (the table is sorted by index)
     GHIP(hipStreamSynchronize(s));
     const u64 C = rows.total(), EC = recs.total(), n2 = n + C, E2 = E + EC;
-    if (n2 >= (1ull << 30) || E2 >= 0xFFFFFFF0ull || (u64)largest + 1 + C >= 0xFFFFFFF0ull) { out->too_large = true; return hipSuccess; }
-    const u32 X = largest + 1;
-    GHIP(B->x_index.ensure(n2 * 4)); GHIP(B->x_abund.ensure(n2 * 2)); GHIP(B->x_shift.ensure(n2 * 16)); GHIP(B->x_sread.ensure(n2 * 8)); GHIP(B->x_sstart.ensure(n2 * 8));
-    GHIP(B->x_send.ensure(n2 * 8)); GHIP(B->x_rev.ensure(n2)); GHIP(B->x_alive.ensure(n2)); GHIP(B->x_origin.ensure(C * 4 + 4));
-    GHIP(B->x_n1.ensure(E2 * 4)); GHIP(B->x_n2.ensure(E2 * 4)); GHIP(B->x_ov.ensure(E2 * 4)); GHIP(B->x_o1.ensure(E2)); GHIP(B->x_o2.ensure(E2));
-    if (edge_alive) GHIP(B->x_ealive.ensure(E2));
-    a.X = X; a.C = C; a.EC = EC;
-    a.x_index = B->x_index.as<u32>(); a.x_abund = B->x_abund.as<u16>(); a.x_shift = B->x_shift.as<u64>(); a.x_sread = B->x_sread.as<u64>(); a.x_sstart = B->x_sstart.as<u64>();
-    a.x_send = B->x_send.as<u64>(); a.x_rev = B->x_rev.as<u8>(); a.x_alive = B->x_alive.as<u8>(); a.x_origin = B->x_origin.as<u32>();
-    a.x_n1 = B->x_n1.as<u32>(); a.x_o1 = B->x_o1.as<u8>(); a.x_n2 = B->x_n2.as<u32>(); a.x_o2 = B->x_o2.as<u8>(); a.x_ov = B->x_ov.as<u32>(); a.x_ealive = edge_alive ? B->x_ealive.as<u8>() : nullptr;
+    if (n2 >= (1ull << 30) || E2 >= 0xFFFFFFF0ull || (u64)largest + 1 + C0 + C >= 0xFFFFFFF0ull) { out->too_large = true; return hipSuccess; }
+    const u32 X0 = largest + 1;
+    // where the extended arrays go: the x_* blocks, or fresh ones when the step reads the x_* blocks (they are swapped in below)
+    enum { I_INDEX, I_ABUND, I_SHIFT, I_SREAD, I_SSTART, I_SEND, I_REV, I_ALIVE, I_ORIGIN, I_N1, I_N2, I_OV, I_O1, I_O2, I_EALIVE, I_N };
+    Buf fresh[I_N];
+    Buf* const mine[I_N] = {&B->x_index, &B->x_abund, &B->x_shift, &B->x_sread, &B->x_sstart, &B->x_send, &B->x_rev, &B->x_alive, &B->x_origin, &B->x_n1, &B->x_n2, &B->x_ov, &B->x_o1, &B->x_o2, &B->x_ealive};
+    Buf* to[I_N];
+    for (int q = 0; q < I_N; ++q) to[q] = C0 ? &fresh[q] : mine[q];
+    GHIP(to[I_INDEX]->ensure(n2 * 4)); GHIP(to[I_ABUND]->ensure(n2 * 2)); GHIP(to[I_SHIFT]->ensure(n2 * 16)); GHIP(to[I_SREAD]->ensure(n2 * 8)); GHIP(to[I_SSTART]->ensure(n2 * 8));
+    GHIP(to[I_SEND]->ensure(n2 * 8)); GHIP(to[I_REV]->ensure(n2)); GHIP(to[I_ALIVE]->ensure(n2)); GHIP(to[I_ORIGIN]->ensure((C0 + C) * 4 + 4));
+    GHIP(to[I_N1]->ensure(E2 * 4)); GHIP(to[I_N2]->ensure(E2 * 4)); GHIP(to[I_OV]->ensure(E2 * 4)); GHIP(to[I_O1]->ensure(E2)); GHIP(to[I_O2]->ensure(E2));
+    if (edge_alive) GHIP(to[I_EALIVE]->ensure(E2));
+    a.X = X0 + (u32)C0; a.C = C; a.EC = EC; a.X0 = X0; a.C0 = C0; a.origin0 = origin0;
+    a.x_index = to[I_INDEX]->as<u32>(); a.x_abund = to[I_ABUND]->as<u16>(); a.x_shift = to[I_SHIFT]->as<u64>(); a.x_sread = to[I_SREAD]->as<u64>(); a.x_sstart = to[I_SSTART]->as<u64>();
+    a.x_send = to[I_SEND]->as<u64>(); a.x_rev = to[I_REV]->as<u8>(); a.x_alive = to[I_ALIVE]->as<u8>(); a.x_origin = to[I_ORIGIN]->as<u32>() + C0;
+    a.x_n1 = to[I_N1]->as<u32>(); a.x_o1 = to[I_O1]->as<u8>(); a.x_n2 = to[I_N2]->as<u32>(); a.x_o2 = to[I_O2]->as<u8>(); a.x_ov = to[I_OV]->as<u32>(); a.x_ealive = edge_alive ? to[I_EALIVE]->as<u8>() : nullptr;
     const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    if (C0) GHIP(hipMemcpyAsync(to[I_ORIGIN]->p, origin0, C0 * 4, dd, s));
     GHIP(hipMemcpyAsync(a.x_index, nd.index, n * 4, dd, s)); GHIP(hipMemcpyAsync(a.x_abund, nd.abund, n * 2, dd, s)); GHIP(hipMemcpyAsync(a.x_shift, nd.shift_full, n * 16, dd, s));
     GHIP(hipMemcpyAsync(a.x_sread, nd.src_read, n * 8, dd, s)); GHIP(hipMemcpyAsync(a.x_sstart, nd.src_start, n * 8, dd, s)); GHIP(hipMemcpyAsync(a.x_send, nd.src_end, n * 8, dd, s));
     GHIP(hipMemcpyAsync(a.x_rev, nd.reversed, n, dd, s)); GHIP(hipMemcpyAsync(a.x_alive, alive, n, dd, s));
@@ -226,15 +245,16 @@ hipError_t repeats_run(UnitigBuffers* B, const TransitResult& tr, uint64_t min_s
     GHIP(hipGetLastError());
     GHIP(hipMemcpyAsync(&out->defect, a.defect, 4, hipMemcpyDeviceToHost, s));
     GHIP(hipStreamSynchronize(s));
+    if (C0) for (int q = 0; q < I_N; ++q) swap_blocks(*mine[q], fresh[q]);      // (the device is idle: the old blocks are read by nobody)
     out->nd.index = a.x_index; out->nd.abund = a.x_abund; out->nd.shift_full = a.x_shift; out->nd.src_read = a.x_sread; out->nd.src_start = a.x_sstart; out->nd.src_end = a.x_send;
     out->nd.reversed = a.x_rev; out->nd.n = n2;
     out->ed = ed; out->ed.n = E2; out->ed.n1 = a.x_n1; out->ed.o1 = a.x_o1; out->ed.n2 = a.x_n2; out->ed.o2 = a.x_o2; out->ed.overlap = a.x_ov;
-    out->alive = a.x_alive; out->edge_alive = a.x_ealive; out->copies = C; out->records_added = EC; out->first_copy_index = X; out->origin = a.x_origin;
+    out->alive = a.x_alive; out->edge_alive = a.x_ealive; out->copies = C; out->total_copies = C0 + C; out->records_added = EC; out->first_copy_index = X0; out->origin = a.x_origin - C0;
     return hipSuccess;
 }
 
 hipError_t repeats_report_originals(UnitigBuffers* B, const UnitigResult& ul, const RepeatsResult& r, hipStream_t s) {
-    if (ul.n_entries == 0 || r.copies == 0) return hipSuccess;
-    hipLaunchKernelGGL(report_kernel, dim3(grid_for(ul.n_entries)), dim3(256), 0, s, ul.n_entries, B->node.as<u32>(), r.first_copy_index, r.copies, r.origin);
+    if (ul.n_entries == 0 || r.total_copies == 0) return hipSuccess;
+    hipLaunchKernelGGL(report_kernel, dim3(grid_for(ul.n_entries)), dim3(256), 0, s, ul.n_entries, B->node.as<u32>(), r.first_copy_index, r.total_copies, r.origin);
     return hipGetLastError();
 }

@@ -10,10 +10,11 @@
 constexpr uint32_t RX_DEFECT_MATCH = 1;     // an end of an edge record at a resolved unitig belongs to no strong key, or to two
 constexpr uint32_t RX_DEFECT_SHAPE = 2;     // a vertex of the last compaction lies outside the list, or a transit row outside its unitig
 struct SimplifyInfo { uint32_t n_compactions, n_rounds_total, n_syncs, junction_defect; float junction_ms;      // compactions run, their jumping rounds, host synchronisations of the whole call; of the EDGES steps' junction stages: the defect mask (*broken is set with it) and the device time, summed
-                      uint32_t transit_defect, repeats_defect; bool repeats_too_large; float transit_ms; uint64_t copies; };      // of the REPEATS step: its transit stage's defect mask and its own (RX_DEFECT_*; *broken is set with either), the capacity refusal (*broken is set too), the transit stage's device time, the entries it copied
+                      uint32_t transit_defect, repeats_defect; bool repeats_too_large; float transit_ms; uint64_t copies;      // of the REPEATS and NESTED steps: the transit stage's defect mask and their own (RX_DEFECT_*; *broken is set with either), the capacity refusal (*broken is set too), the transit stages' device time, the entries the schedule copied
+                      uint64_t ambiguous, resolved, conflicts, unanchored; };      // of the NESTED steps on a graph with copies, summed: the windows whose row belongs to several entries and what became of them (placement.h, NP_C_*)
 // What an MDBG_SIMPLIFY_EDGES step needs beside the graph to run the junction stage (junctions_run): that stage's buffers and the context's placement scratch, the
 // node table's index column, the whole resident store as a range of reads, and the window placer.  has_reads == false: nothing is resident, every record is weak.
-// An MDBG_SIMPLIFY_REPEATS step needs the same with the transit stage's buffers (transits_run) in place of the junction stage's; nothing resident: nothing resolves.
+// An MDBG_SIMPLIFY_REPEATS or MDBG_SIMPLIFY_NESTED step needs the same with the transit stage's buffers (transits_run) in place of the junction stage's; nothing resident: nothing resolves.
 struct SimplifySupport {
     JunctionBuffers* jb; TransitBuffers* tb; PlacementBuffers* pb; const uint32_t* index; uint64_t n_rows; ReadPathRange range; bool has_reads; WindowPlacer placer;
 };

@@ -26,13 +26,16 @@
 // MDBG_SIMPLIFY_REPEATS removes nothing: the transit stage (transits.hip) says which unitigs of the current list the reads resolve, and repeats.hip appends the
 // copies to the node columns, the masks and the edge records; the next compaction takes the larger graph as any other, and the schedule goes on with it.  The
 // list's node[] names the originals: one kernel at the end of the schedule (repeats_report_originals).
+// MDBG_SIMPLIFY_NESTED is the same branch.  Once the schedule has made copies it hands the transit stage the origin map {X, copies so far, origin[]}, so that the
+// windows are placed on a list that holds copies (placement.hip), and the step itself the earlier result, so that it grows into fresh blocks (repeats.hip).
 //
 // MDBG_SIMPLIFY_SUPERBUBBLES has a translation unit of its own (superbubbles.hip): it reads uhead / utail of ends_kernel and the sorted arcs, writes rem[] and the unitig
 // counter, and shares scatter_kernel and the one wait with the other removing kinds; its defect word travels in that wait as a component step's does.
 //
 // Host round trips per step: those of one compaction (unitigs.hip) plus ONE for the two removal counters, which size the next compaction's checks; an EDGES step
 // waits once for its junction stage and once for its counter; a REPEATS step once for its transit stage and, if something resolves, once for the totals that size
-// the copies and once for its defect flag.  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
+// the copies and once for its defect flag; a NESTED step waits as a REPEATS step does, with or without copies in the graph (the placement's extra launches ride in the transit
+// stage's wait).  A step that removes nothing is followed by no compaction: the next step decides on the same arrays.
 #include <cstring>
 
 #include "repeats.h"
@@ -282,22 +285,28 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
             if (gone) { edge_alive = B->edge_alive.as<u8>(); stale = true; }
             continue;
         }
-        if (steps[k].kind == MDBG_SIMPLIFY_REPEATS) {
+        if (steps[k].kind == MDBG_SIMPLIFY_REPEATS || steps[k].kind == MDBG_SIMPLIFY_NESTED) {
             if (!sup || !sup->tb) return hipErrorInvalidValue;
+            const bool holds_copies = rr.total_copies != 0;      // (the validation admits a NESTED step only: REPEATS means "the graph holds no copies")
+            if (holds_copies && steps[k].kind != MDBG_SIMPLIFY_NESTED) return hipErrorInvalidValue;
             if (!sup->has_reads || ed.n == 0 || out->edges.n == 0) continue;      // nothing resolves without reads, and a repeat has records
             TransitResult tr;
-            GHIP(transits_run(sup->tb, sup->pb, *out, sup->index, sup->n_rows, sup->range, steps[k].max_nodes, sup->placer, s, &tr));
+            if (holds_copies) GHIP(transits_run(sup->tb, sup->pb, *out, sup->index, sup->n_rows, sup->range, steps[k].max_nodes, sup->placer, s, &tr, OriginMap{rr.first_copy_index, rr.total_copies, rr.origin}));
+            else GHIP(transits_run(sup->tb, sup->pb, *out, sup->index, sup->n_rows, sup->range, steps[k].max_nodes, sup->placer, s, &tr));
             ++info->n_syncs; info->transit_ms += tr.ms;
+            info->ambiguous += tr.ambiguous; info->resolved += tr.resolved; info->conflicts += tr.conflicts; info->unanchored += tr.unanchored;
             if (tr.defect) { info->transit_defect = tr.defect; return defect(broken); }
             if (tr.n_unitigs != U) return defect(broken);
             if (tr.n_resolved == 0 || tr.n_transits == 0) continue;
-            GHIP(repeats_run(B, tr, steps[k].max_nodes, *out, nd, ed, alive, edge_alive, s, &rr));
-            info->n_syncs += rr.too_large ? 1 : 2;
-            if (rr.too_large) { info->repeats_too_large = true; return defect(broken); }
-            if (rr.defect) { info->repeats_defect = rr.defect; return defect(broken); }
-            if (rr.copies == 0) return defect(broken);      // a resolved unitig has two entrances and an entry
+            RepeatsResult step;
+            GHIP(repeats_run(B, tr, steps[k].max_nodes, *out, nd, ed, alive, edge_alive, nd0.index + (nd0.n - 1), holds_copies ? &rr : nullptr, s, &step));
+            info->n_syncs += step.too_large ? 1 : 2;
+            if (step.too_large) { info->repeats_too_large = true; return defect(broken); }
+            if (step.defect) { info->repeats_defect = step.defect; return defect(broken); }
+            if (step.copies == 0) return defect(broken);      // a resolved unitig has two entrances and an entry
+            rr = step;
             nd = rr.nd; ed = rr.ed; alive = rr.alive; edge_alive = rr.edge_alive;
-            n = nd.n; n2x = (u32)(2 * n); n_alive += rr.copies; info->copies = rr.copies;
+            n = nd.n; n2x = (u32)(2 * n); n_alive += rr.copies; info->copies = rr.total_copies;
             stale = true;
             continue;
         }
@@ -345,6 +354,6 @@ hipError_t simplify_unitigs(UnitigBuffers* B, ComponentBuffers* CB, const Simpli
         stale = got[1] != 0;
     }
     if (stale) { GHIP(compact()); if (*broken) return hipSuccess; }
-    if (rr.copies) { GHIP(repeats_report_originals(B, *out, rr, s)); GHIP(hipStreamSynchronize(s)); ++info->n_syncs; }
+    if (rr.total_copies) { GHIP(repeats_report_originals(B, *out, rr, s)); GHIP(hipStreamSynchronize(s)); ++info->n_syncs; }
     return hipGetLastError();
 }

@@ -223,12 +223,12 @@ TransitBuffers* transit_buffers_create() { return new TransitBuffers(); }
 void transit_buffers_destroy(TransitBuffers* b) { delete b; }
 
 hipError_t transits_run(TransitBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, u64 min_support,
-                        const WindowPlacer& placer, hipStream_t s, TransitResult* out) {
+                        const WindowPlacer& placer, hipStream_t s, TransitResult* out, const OriginMap& om) {
     memset(out, 0, sizeof *out);
     const u64 U = ul.n_unitigs, R = ul.edges.n, n_idx = rg.i1 - rg.i0;
     if (U > ul.n_entries) return hipErrorInvalidValue;
     // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
-    GHIP(placement_reserve(P, ul, n_rows, rg, true));
+    GHIP(placement_reserve(P, ul, n_rows, rg, true, om));
     const Zeroed z = zeroed_of(U, R);
     GHIP(B->zeroed.ensure(z.bytes)); GHIP(B->verdict.ensure(U + 4));
     GHIP(B->kind.ensure(n_idx + 4)); GHIP(B->klo.ensure(n_idx * 8 + 8)); GHIP(B->klo2.ensure(n_idx * 8 + 8)); GHIP(B->khi.ensure(n_idx * 4 + 4)); GHIP(B->khi2.ensure(n_idx * 4 + 4));
@@ -247,7 +247,7 @@ hipError_t transits_run(TransitBuffers* B, PlacementBuffers* P, const UnitigResu
     GHIP(B->timer.start(s));
     GHIP(hipMemsetAsync(B->zeroed.p, 0, z.bytes, s));
     PlacementView V;
-    GHIP(placement_queue(P, ul, index, n_rows, rg, true, TX_C_N, placer, s, &V));
+    GHIP(placement_queue(P, ul, index, n_rows, rg, true, TX_C_N, placer, s, &V, om));
     const TxArgs a = args_of(B, V, ul, rg, min_support);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);
@@ -273,8 +273,9 @@ hipError_t transits_run(TransitBuffers* B, PlacementBuffers* P, const UnitigResu
     if (a.n_idx) hipLaunchKernelGGL(check_kernel, dim3(grid_for(a.n_idx)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(verdict_kernel, dim3(grid_for(a.U)), dim3(256), 0, s, a);
     GHIP(hipGetLastError());
-    u64 h[TX_C_N];
-    GHIP(B->timer.stop_and_read(h, a.counters, sizeof h, s, &out->ms));
+    u64 h[PLACEMENT_COUNTERS] = {};
+    GHIP(B->timer.stop_and_read(h, a.counters, (om.copies ? PLACEMENT_COUNTERS : TX_C_N) * sizeof(u64), s, &out->ms));
+    out->ambiguous = h[NP_C_AMBIGUOUS]; out->resolved = h[NP_C_RESOLVED]; out->conflicts = h[NP_C_CONFLICTS]; out->unanchored = h[NP_C_UNANCHORED];
     out->defect = (u32)h[RP_C_DEFECT];
     if (out->defect) return hipSuccess;
     out->n_reads = rg.n_reads; out->n_crossings = h[TX_C_ADJACENT] - h[TX_C_LINKS]; out->n_explained = h[TX_C_EXPLAINED]; out->n_passes = h[TX_C_PASSES];

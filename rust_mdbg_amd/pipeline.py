@@ -7,7 +7,7 @@ import queue
 import threading
 import time
 
-from .api import MAGIC_SIMPLIFY_STEPS, MDBG_SIMPLIFY_REPEATS, Mdbg, edge_columns, junction_text, merge_junctions, merge_transits, read_path_text, transit_self_flags, transit_text, unitig_name
+from .api import MAGIC_SIMPLIFY_STEPS, MDBG_SIMPLIFY_NESTED, MDBG_SIMPLIFY_REPEATS, Mdbg, edge_columns, junction_text, merge_junctions, merge_transits, read_path_text, transit_self_flags, transit_text, unitig_name
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions / graph_transits call of run_file
@@ -31,7 +31,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     simplify (with contigs): a schedule of tip / bubble / superbubble / component / edge-pruning steps, e.g. api.MAGIC_SIMPLIFY_STEPS, api.MAGIC_SUPERBUBBLE_STEPS or [(api.MDBG_SIMPLIFY_EDGES, 1, 0)] + those (the
     sketch store is still resident when the schedule runs, which is all an edge step needs; its count is simplify["total_edges_removed"]) — also write <prefix>.msimpl.gfa / .msimpl.fa, the contigs left after
     Mdbg.graph_simplify(steps) (this project's own order-free rules, not gfatools parity); the .unitigs.* files are unchanged.  Adds n_simplified and simplify (stats).
-    A schedule may hold one (api.MDBG_SIMPLIFY_REPEATS, min_support, 0) step, which duplicates the unitigs the resident reads resolve (simplify["entries_copied"]); no read can be
+    A schedule may hold (api.MDBG_SIMPLIFY_NESTED, min_support, 0) steps, repeats steps that may follow a step that copied (a nested repeat needs one step per level), and
+    one (api.MDBG_SIMPLIFY_REPEATS, min_support, 0) step, which duplicates the unitigs the resident reads resolve (simplify["entries_copied"]); no read can be
     placed on a list with copies, so with such a step the <prefix>.msimpl.read_paths / .junctions / .transits.tsv files are not written (simplified_read_evidence_written is False).
     components (with contigs): also write <prefix>.unitigs.components.tsv, one line `utgNAME<TAB>component` per unitig: the connected component of the unitig
     graph each unitig lies in (Mdbg.graph_components; numbered by their smallest unitig), and with simplify <prefix>.msimpl.components.tsv for the simplified
@@ -208,8 +209,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 sctg = Contigs(sl)
                 if components:
                     write_components(sl, prefix + ".msimpl.components.tsv", "n_components_simplified")
-                # a REPEATS step may leave copies in the list, and no read can be placed on a list with copies: the three read-evidence files of the simplified list are not written
-                placeable = not any(int(st[0]) == MDBG_SIMPLIFY_REPEATS for st in simplify)
+                # a REPEATS or NESTED step may leave copies in the list, and no read can be placed on a list with copies: the three read-evidence files of the simplified list are not written
+                placeable = not any(int(st[0]) in (MDBG_SIMPLIFY_REPEATS, MDBG_SIMPLIFY_NESTED) for st in simplify)
                 comp["simplified_read_evidence_written"] = placeable
                 if read_paths and placeable:
                     write_read_paths(sl, prefix + ".msimpl.read_paths.tsv", "n_read_steps_simplified")
