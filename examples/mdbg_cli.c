@@ -244,13 +244,15 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--read-paths")) read_paths = 1;
         else if (!strcmp(argv[i], "--junctions")) junctions = 1;
         else if (!strcmp(argv[i], "--transits") && i + 1 < argc) { transits = strtoull(argv[++i], NULL, 10); if (!transits) { fprintf(stderr, "--transits takes a min_support >= 1\n"); return 2; } }
+        else if (!strcmp(argv[i], "--bf")) p.flags |= MDBG_FLAG_PREFILTER;                      /* main.rs --bf, order-free: the counting pre-filter in front of the node table */
+        else if (!strcmp(argv[i], "--bf-cells") && i + 1 < argc) p.prefilter_cells = strtoull(argv[++i], NULL, 10);   /* its number of 2-bit cells (default 2^32) */
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
         else if (!strcmp(argv[i], "--syncmers")) { p.scheme = MDBG_SCHEME_SYNCMERS; if (!syncmer_s_given) p.syncmer_s = 4; }       /* main.rs:438,491-495: default s = 4 */
         else if ((!strcmp(argv[i], "-s") || !strcmp(argv[i], "--s")) && i + 1 < argc) { p.syncmer_s = (uint32_t)atoi(argv[++i]); syncmer_s_given = 1; }
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--bf [--bf-cells N]] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
     if (simplify || components || read_paths || junctions || transits) contigs = 1;
     if (!contigs) keep_reads = 0;

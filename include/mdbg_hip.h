@@ -26,7 +26,8 @@
  * Conventions: every function returns 0 (MDBG_OK) or a negative error code and never aborts (the reference
  * panics); strings are (ptr,len); the caller owns its input buffers and may free them when a call returns;
  * the library owns the context and every buffer it hands out until the next call that documents otherwise
- * or mdbg_destroy.  Semantics are those of the reference run with `--threads 1` and without `--bf`:
+ * or mdbg_destroy.  Semantics are those of the reference run with `--threads 1` and without `--bf`
+ * (MDBG_FLAG_PREFILTER is this library's order-free counterpart of `--bf`, defined at the flag):
  * results do not depend on how reads are split into batches or on the order of the calls, only on
  * `first_read_ordinal` (the position of the batch's first record in the input file).
  *
@@ -59,7 +60,38 @@ enum {
 #define MDBG_MAX_MINABUND 65535u /* DbgAbundance is a u16 in the reference; up to 8 the table tracks the A-th sighting directly, above it is recovered at finalize */
 #define MDBG_FLAG_FORCE_GENERIC 1u /* every tile takes the generic exact sketch kernel (testing / cross-check) */
 #define MDBG_FLAG_KEEP_READS 2u  /* the context keeps every batch it ingests WITH bases, packed 2 bits per base, in device memory: mdbg_graph_contigs and mdbg_graph_node_seqs gather from that store */
-#define MDBG_SCHEME_DENSITY 0u   /* canonical ntHash <= density * 2^64           Read::extract_density   src/read.rs:176-211 */
+/* MDBG_FLAG_PREFILTER — the counting pre-filter (the reference's --bf, made independent of order).
+ *
+ * The reference's Bloom filter lets a k-min-mer into dbg_nodes at its second sighting (src/main.rs:632-691, Bloom branch); it is racy under --threads and credits a
+ * false positive with abundance 2.  Neither is copied.  A context created with this flag has a filter of n_cells cells, n_cells = mdbg_params.prefilter_cells as
+ * given (0: 2^32; 1 <= n_cells <= 2^36, else MDBG_E_PARAM), fixed for the context's life; a cell is a 2-bit counter that saturates at 2 (n_cells / 4 bytes of
+ * device memory).  The flag needs min_abundance >= 2 (MDBG_E_PARAM with 1).
+ *
+ *   Cell of a window:  cell = mulhi64(fmix64(h ^ 0x9E3779B97F4A7C15), n_cells), mulhi64 = the high 64 bits of the 128-bit product,
+ *     fmix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33   (all arithmetic mod 2^64),
+ *     h = the table's key hash of the window's canonical key c[0 .. k) (KmerVec::normalize: the window, or its reverse when that is the smaller one — ties reversed):
+ *       h0 = 0x243F6A8885A308D3, h1 = 0x13198A2E03707344, h2 = 0xA4093822299F31D0, h3 = 0x082EFA98EC4E6C89;
+ *       for j = 0 .. k-1 in order, with i = j mod 4:   hi = (hi ^ c[j]) * 0x9E3779B97F4A7C15;  hi ^= hi >> 29;
+ *       h = fmix64(h0 ^ rol64(h1, 17) ^ rol64(h2, 31) ^ rol64(h3, 47))                          (rol64: rotate left).
+ *   Cell value:  after counting, min(2, number of window occurrences among ALL resident batches whose key maps to the cell).
+ *   Admission:  a window is admitted iff its cell value is 2, and the table holds exactly the admitted windows, with their true ordinals.  So every key seen at
+ *     least twice is in the table with its exact count, first sighting and A-th sighting; a key seen once is in the table, with count 1, iff it shares its cell
+ *     with another occurrence (of any key).
+ *   Node table:  for min_abundance >= 2 the table of mdbg_finalize* has the same rows in the same order as without the flag; n, keys, abundance, seqlen, shift,
+ *     shift_full, src_read, src_start, src_end, reversed and n_wrapped are bit-identical.  `index` is the rank of the first sighting among the keys the TABLE
+ *     holds (strictly increasing, <= the exact value) and n_distinct is the number of keys the table holds.  With n_cells == 1 and at least two windows everything
+ *     is admitted and the whole result equals the exact mode's.  Like the exact mode, results depend on the reads, their ordinals and the parameters only — never
+ *     on the batch split, the call order or finalizes in between.
+ *   How it runs:  the ingest calls sketch the batch and count its windows into the filter; nothing is inserted.  The admitted windows are inserted at the start
+ *     of every call that reads the table (mdbg_insert_resident, mdbg_finalize*, mdbg_query_batch; the graph stages read the last finalize's table).  Windows of
+ *     earlier batches can become admissible through a later batch, so when a batch was counted since the last insertion and the table is not empty, the table is
+ *     cleared and EVERY resident batch is inserted again: alternating ingest and finalize re-inserts.  mdbg_reset(new_k) and mdbg_rewind make the filter stale
+ *     (counts cannot be taken back): it is zeroed and every resident batch counted again; mdbg_reset(ctx, 0) drops it.
+ *   Not available (MDBG_E_STATE): mdbg_set_partition with world > 1, mdbg_route_pack / mdbg_insert_records / mdbg_routed_export, and the mdbg_dist_* layer
+ *     (mdbg_dist_create).
+ *   mdbg_stats: n_windows_admitted, prefilter_cells. */
+#define MDBG_FLAG_PREFILTER 4u
+#define MDBG_SCHEME_DENSITY 0u  /* canonical ntHash <= density * 2^64           Read::extract_density   src/read.rs:176-211 */
 #define MDBG_SCHEME_SYNCMERS 1u  /* --syncmers: open syncmers (smallest s-mer in the middle), down-sampled by hash(l-mer) <= density * 4^l;
                                   * 2-bit codes, A/a C/c G/g T/t/U/u, any other byte resets (no alphabet error); l <= 31
                                   *                                              Read::extract_syncmers  src/read.rs:215-352 */
@@ -78,7 +110,8 @@ typedef struct mdbg_params {
     uint64_t table_capacity_hint; /* expected number of distinct k-min-mers, 0 = size from the data */
     uint32_t scheme;            /* MDBG_SCHEME_*: how minimizers are selected (Read::extract, src/read.rs:85-90) */
     uint32_t syncmer_s;         /* MDBG_SCHEME_SYNCMERS: s-mer length, 0..min(l, 16) with l - s + 1 <= 32 (-s, default 4 in the reference) */
-    uint64_t reserved[3];
+    uint64_t prefilter_cells;   /* MDBG_FLAG_PREFILTER: number of cells of the counting pre-filter, 1 .. 2^36; 0 = the default 2^32 (1 GiB)  (--bf) */
+    uint64_t reserved[2];
 } mdbg_params;
 
 /* Read-only view of the abundance-filtered node table (what src/main.rs:1014-1117 iterates).
@@ -114,7 +147,9 @@ typedef struct mdbg_stats {
     uint64_t tile_bases;        /* raw bases a tile owns under this context's parameters (n_tiles = sum over batches of ceil(batch bases / tile_bases)) */
     uint64_t n_link_matches;    /* only with MDBG_COUNT_LINKS in the environment (test hook; 0 otherwise): repeats of a key confirmed as a LINK of their left neighbour's
                                  * match (one value compared instead of k: csrc/table.hip, upsert_wave), since create / mdbg_reset */
-    uint64_t reserved[3];
+    uint64_t n_windows_admitted; /* MDBG_FLAG_PREFILTER: windows the pre-filter let into the table (n_windows stays the number of windows of the ingested reads); 0 without the flag */
+    uint64_t prefilter_cells;   /* MDBG_FLAG_PREFILTER: the number of cells in force; 0 without the flag */
+    uint64_t reserved[1];
 } mdbg_stats;
 
 mdbg_ctx* mdbg_create(const mdbg_params* p, int* err);

@@ -15,6 +15,7 @@ _LIB = None
 MDBG_OK, MDBG_E_PARAM, MDBG_E_ALPHABET, MDBG_E_CAPACITY, MDBG_E_DEVICE, MDBG_E_NOMEM, MDBG_E_STATE, MDBG_E_IO = 0, -1, -2, -3, -4, -5, -6, -7
 FLAG_FORCE_GENERIC = 1   # mdbg_params.flags bit 0: every tile takes the generic exact kernel (testing)
 FLAG_KEEP_READS = 2      # mdbg_params.flags bit 1: the context keeps the reads it ingests, packed, on the device (Mdbg.graph_contigs)
+FLAG_PREFILTER = 4       # mdbg_params.flags bit 2: the counting pre-filter in front of the node table (--bf made order-free; include/mdbg_hip.h, MDBG_FLAG_PREFILTER)
 
 
 class MdbgError(RuntimeError):
@@ -26,7 +27,8 @@ class MdbgError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("k", C.c_uint32), ("l", C.c_uint32), ("density", C.c_double), ("min_abundance", C.c_uint32),
                 ("reads_already_hpc", C.c_uint32), ("device", C.c_int32), ("flags", C.c_uint32),
-                ("table_capacity_hint", C.c_uint64), ("scheme", C.c_uint32), ("syncmer_s", C.c_uint32), ("reserved", C.c_uint64 * 3)]
+                ("table_capacity_hint", C.c_uint64), ("scheme", C.c_uint32), ("syncmer_s", C.c_uint32), ("prefilter_cells", C.c_uint64),
+                ("reserved", C.c_uint64 * 2)]
 
 
 class Nodes(C.Structure):
@@ -42,7 +44,7 @@ class Stats(C.Structure):
                 ("n_distinct", C.c_uint64), ("table_capacity", C.c_uint64), ("n_slow_tiles", C.c_uint64), ("n_tiles", C.c_uint64),
                 ("ms_sketch", C.c_double), ("ms_insert", C.c_double), ("ms_finalize", C.c_double), ("ms_sketch_tile", C.c_double),
                 ("n_sketch_tile_launches", C.c_uint64), ("n_sketch_tile_bases", C.c_uint64), ("tile_bases", C.c_uint64),
-                ("n_link_matches", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+                ("n_link_matches", C.c_uint64), ("n_windows_admitted", C.c_uint64), ("prefilter_cells", C.c_uint64), ("reserved", C.c_uint64 * 1)]
 
 
 class RoutedLists(C.Structure):
@@ -509,14 +511,20 @@ def concat_reads(reads):
 class Mdbg:
     """One context = one device-resident sketch store + k-min-mer table (dbg_nodes, src/main.rs:595)."""
 
-    def __init__(self, k, l, density, min_abundance=2, reads_already_hpc=False, device=-1, flags=0, table_capacity_hint=0, syncmer_s=None, keep_reads=False):
-        """keep_reads: the context keeps every batch it ingests with bases, packed 2 bits per base, on the device (MDBG_FLAG_KEEP_READS): graph_contigs()"""
+    def __init__(self, k, l, density, min_abundance=2, reads_already_hpc=False, device=-1, flags=0, table_capacity_hint=0, syncmer_s=None, keep_reads=False,
+                 prefilter=False, prefilter_cells=0):
+        """keep_reads: the context keeps every batch it ingests with bases, packed 2 bits per base, on the device (MDBG_FLAG_KEEP_READS): graph_contigs()
+        prefilter: the counting pre-filter (MDBG_FLAG_PREFILTER, needs min_abundance >= 2): a k-min-mer enters the table only when its filter cell has been hit twice;
+        prefilter_cells: number of 2-bit cells, 0 = 2^32"""
         self.L = load_library()
         if keep_reads:
             flags |= FLAG_KEEP_READS
+        if prefilter:
+            flags |= FLAG_PREFILTER
         self.params = Params(k=k, l=l, density=density, min_abundance=min_abundance, reads_already_hpc=int(reads_already_hpc),
                              device=device, flags=flags, table_capacity_hint=table_capacity_hint,
-                             scheme=0 if syncmer_s is None else 1, syncmer_s=0 if syncmer_s is None else syncmer_s)      # syncmer_s: --syncmers -s
+                             scheme=0 if syncmer_s is None else 1, syncmer_s=0 if syncmer_s is None else syncmer_s,        # syncmer_s: --syncmers -s
+                             prefilter_cells=prefilter_cells)
         err = C.c_int(0)
         self.h = self.L.mdbg_create(C.byref(self.params), C.byref(err))
         if not self.h:

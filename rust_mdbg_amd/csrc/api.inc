@@ -29,6 +29,7 @@
 #include "results.inc"      // the derived graph results and which of them are current
 #include "context.inc"
 #include "store.inc"
+#include "prefilter_api.inc"   // the counting pre-filter in front of the table (MDBG_FLAG_PREFILTER)
 #include "ingest_api.inc"
 extern "C" {                   // entry points and their static helpers only from here on
 #include "finalize_api.inc"

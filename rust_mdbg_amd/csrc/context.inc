@@ -20,6 +20,7 @@ struct Batch { u64 first_ordinal; u32 n_reads; u32 slot0; u64 m0, m1; u64 owned 
                u32 src_rank = ~0u;                                                          // sketch exchange: the rank that sketched the batch (~0: this context); its positions are NOT resident when set
                u64 n_bases = 0;
                bool partial = false;
+               u64 adm_word = ~0ull;                                                        // counting pre-filter: where in mdbg_ctx::pf_adm the batch's admission bits of the running round start (~0: inserted ungated)
                std::shared_ptr<KeptReads> kept; };                                                    // a foreign sketch of which only the hashes of this rank's listed windows are resident (mdbg_dist, segments)                                                         // raw bases of the batch (0: imported sketch)                                                    // false: imported with a list, the minimizer -> read map is filled on demand (ensure_mread)
 
 // shard arrays (CTR_SHARDS u64 each): SH_DISTINCT keys in the table; SH_OWNED / SH_OWNINS: windows a partitioned context owns / inserted (zeroed by their users);
@@ -55,6 +56,13 @@ struct mdbg_ctx {
     u32 slab_cap_min = 0;                    // grown when a tile's records did not fit its slab
     // node table
     DevBuf tab, mx; u64 cap = 0;
+    // the counting pre-filter (MDBG_FLAG_PREFILTER; prefilter_api.inc).  ONLY the functions of prefilter_api.inc write these
+    DevBuf pf_cells, pf_adm;                 // the filter (2 bits per cell), allocated at the first count; the admission bits of the batches of one insertion round
+    u64 pf_n_cells = 0;                      // cells in force (0: no filter on this context)
+    size_t pf_counted = 0;                   // batches [0, pf_counted) have been counted into the filter
+    bool pf_stale = false, pf_dirty = false; // stale: the filter holds counts that no longer stand (a new k, a rewind): zero it and count every batch again;
+                                             // dirty: a batch was counted since the last insertion round
+    u64 n_windows_admitted = 0;
     // routed records
     DevBuf arena, route_out, route_tmp, route_h, route_f; u64 n_records = 0; bool routed = false;
     // finalize
@@ -288,7 +296,7 @@ int clear_table(mdbg_ctx* c) {
     z.p[2] = scal(c) + SC_IMPORTERR; z.n[2] = 1; z.p[3] = scal(c) + SC_PROBEERR; z.n[3] = 1;
     if (c->cap) launch_clear_table(c->tab.as<Slot>(), c->cap, c->mx.as<u64>(), cascade_of(c->P.min_abundance) > 2 ? c->cap * (cascade_of(c->P.min_abundance) - 2) : 0, c->stream, &z);
     else launch_zero_regions(z, c->stream);
-    c->n_distinct = 0; c->n_windows = 0; c->batches_inserted = 0; c->n_records = 0; c->routed = false;
+    c->n_distinct = 0; c->n_windows = 0; c->n_windows_admitted = 0; c->batches_inserted = 0; c->n_records = 0; c->routed = false;      // (the pre-filter's counts stay: they describe the resident batches)
     c->claims_ok = c->claim.p != nullptr; c->claims_fin_batches = 0;      // (an empty table: no finalize has left a mark in the claim map that the insertions will not rewrite)
     return MDBG_OK;
 }
@@ -325,6 +333,7 @@ int check_params(const mdbg_params* p) {
     if (!(p->density == p->density)) return MDBG_E_PARAM;
     if (p->scheme > MDBG_SCHEME_SYNCMERS) return MDBG_E_PARAM;
     if (p->scheme == MDBG_SCHEME_SYNCMERS && (p->l > 31 || p->syncmer_s > 16 || p->syncmer_s > p->l || p->l - p->syncmer_s + 1 > 32)) return MDBG_E_PARAM;
+    if ((p->flags & MDBG_FLAG_PREFILTER) && (p->min_abundance < 2 || p->prefilter_cells > PF_MAX_CELLS)) return MDBG_E_PARAM;      // (a singleton's fate depends on its cell: never a node)
     return MDBG_OK;
 }
 }  // namespace
@@ -362,6 +371,7 @@ mdbg_ctx* mdbg_create(const mdbg_params* p, int* err) {
     for (auto& g : c->stage) if (hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking) != hipSuccess) return bail(MDBG_E_DEVICE);
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return bail(MDBG_E_DEVICE);
     c->bound = make_hash_bound(p->density);
+    if (p->flags & MDBG_FLAG_PREFILTER) c->pf_n_cells = p->prefilter_cells ? p->prefilter_cells : PF_DEFAULT_CELLS;
     if (c->d_t4.ensure((2 << (2 * BS_GS)) * 8, 0, c->stream) != hipSuccess) return bail(MDBG_E_NOMEM);
     { u64 t4[2 << (2 * BS_GS)]; bs_make_table<BS_GS>(t4); if (hipMemcpy(c->d_t4.p, t4, sizeof t4, hipMemcpyHostToDevice) != hipSuccess) return bail(MDBG_E_DEVICE); }
     if (c->scalars.ensure(SC_N * 8, 0, c->stream) != hipSuccess) return bail(MDBG_E_NOMEM);

@@ -206,6 +206,7 @@ int mdbg_comm_rccl(void* nccl_comm, uint32_t rank, uint32_t world, mdbg_comm* ou
 mdbg_dist* mdbg_dist_create(const mdbg_params* p, const mdbg_comm* comm, int* err) {
     if (!p || !comm || !comm->allgather_u64 || !comm->exchange || !comm->allreduce_sum_u64 || comm->world == 0 || comm->rank >= comm->world ||
         comm->world > OWNL_MAX_WORLD) { if (err) *err = MDBG_E_PARAM; return nullptr; }
+    if (p->flags & MDBG_FLAG_PREFILTER) { if (err) *err = MDBG_E_STATE; return nullptr; }      // the counting pre-filter is a one-GPU mode (include/mdbg_hip.h)
     mdbg_ctx* c = mdbg_create(p, err);
     if (!c) return nullptr;
     mdbg_dist* d = new mdbg_dist();

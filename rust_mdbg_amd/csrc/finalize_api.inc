@@ -291,6 +291,7 @@ static int finalize_impl(mdbg_ctx* c, mdbg_nodes* out, NodesTo to) {
     if (c->routed) return fail(c, MDBG_E_STATE, "a routed table is finalized by the distributed driver (mdbg_routed_export / mdbg_resolve_* / mdbg_routed_keys)");
     memset(out, 0, sizeof *out);
     out->k = c->P.k;
+    if (prefilter_on(c)) { const int pe = insert_resident_impl(c); if (pe) return pe; }      // the admitted windows of everything resident, inserted now (the ingest calls only count)
     if (nothing_resident(c)) { c->res.node_table_is(NodeTable::EMPTY, 0); return MDBG_OK; }
     int e = finalize_begin_impl(c, true); if (e) return e;
     return finalize_end_impl(c, out, to, false, nullptr, nullptr, true);
@@ -320,6 +321,7 @@ int mdbg_nodes_digest(mdbg_ctx* c, const mdbg_nodes* nodes, uint64_t* sum, uint6
 int mdbg_finalize_begin(mdbg_ctx* c, uint64_t** d_bm_first, uint64_t** d_bm_solid, uint64_t* n_words) {
     MDBG_ENTER(c, d_bm_first && d_bm_solid && n_words);
     if (c->routed) return fail(c, MDBG_E_STATE, "not available for a routed table");
+    if (prefilter_on(c)) { const int pe = insert_resident_impl(c); if (pe) return pe; }
     if (!c->M) {                       // no minimizer anywhere (empty input, or every read shorter than l): an empty table, not an error
         c->fin_open = true; c->fin_words = 0;      // (nothing resident: no node table can be current, M == 0 since the last clear_table)
         *d_bm_first = nullptr; *d_bm_solid = nullptr; *n_words = 0;

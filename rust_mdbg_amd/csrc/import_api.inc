@@ -4,6 +4,7 @@ int mdbg_set_partition(mdbg_ctx* c, uint32_t world, uint32_t rank) {
     if (!c) return MDBG_E_PARAM;
     MDBG_LOCK(c);
     if (world < 1 || world > 4096 || rank >= world) return fail(c, MDBG_E_PARAM, "bad partition");
+    if (world > 1 && prefilter_on(c)) return fail(c, MDBG_E_STATE, PF_UNAVAILABLE);
     if (c->n_distinct || c->batches_inserted) return fail(c, MDBG_E_STATE, "set the partition before inserting");
     c->own_world = world; c->own_rank = rank;
     return MDBG_OK;

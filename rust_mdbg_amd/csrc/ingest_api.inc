@@ -243,7 +243,7 @@ int sketch_device_impl(mdbg_ctx* c, const SketchInput& in, const u64* d_offsets,
         init0.zero[0] = scal(c) + SC_ERRFLAG; init0.zero[1] = scal(c) + SC_SLOWTOTAL; init0.zero[2] = scal(c) + SC_OVERMAX; init0.set_p = scal(c) + SC_CARRY; init0.set_v = c->M;
         // the insertion can ride behind this sketch when its grid can be sized without the count: the store's free room is the bound, and it must not be
         // much more than the batch is expected to fill (a store sized for many batches would launch mostly idle workgroups)
-        const bool fused = then_insert && inserted && n_tiles_total && tp.part_end.size() == 1 && !phase_dbg && c->cap && c->own_world <= 1 && !c->lmer_on && !c->routed && !c->pending_m &&
+        const bool fused = then_insert && inserted && n_tiles_total && tp.part_end.size() == 1 && !phase_dbg && c->cap && c->own_world <= 1 && !c->lmer_on && !c->routed && !c->pending_m && !prefilter_on(c) &&      // (pre-filter: insertion never rides behind the sketch, the batch is counted first)
                            c->batches_inserted == c->batches.size() && c->mcap > c->M && c->mcap - c->M <= 2 * (want - c->M) + (1u << 20) &&
                            want - c->M <= (48ull << 20);          // (larger rounds are inserted in slices, insert_resident_impl)
         if (fused) init0.zero[3] = scal(c) + SC_BATCHWIN;
@@ -345,7 +345,7 @@ int insert_sliced(mdbg_ctx* c, size_t first, size_t last, u64 slice) {
             const Batch& b = c->batches[sl[j].b];
             launch_slice_check(c->shards.as<u64>(), scal(c) + SC_NDISTINCT, sl[j].hi - sl[j].a, c->cap, flags + 1, scal(c) + SC_SLICEFAIL, (u64)j, s);
             launch_insert_windows(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), sl[j].a, b.m1, b.slot0, b.first_ordinal,
-                                  scal(c) + SC_NWINDOWS, flags, s, nullptr, sl[j].hi - sl[j].a);
+                                  scal(c) + SC_NWINDOWS, flags, s, nullptr, sl[j].hi - sl[j].a, adm_of(c, b), b.m0);
         }
         STAGE_EVENT(c, c->ev1, s);
         e = read_scalars(c, sc); if (e) return e;
@@ -401,7 +401,7 @@ int launch_round_inserts(mdbg_ctx* c, size_t first, size_t last) {
             launch_insert_listed(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), b.m0, b.m1, list_of(b), seg_of(b), b.owned, b.slot0, b.n_reads, b.first_ordinal, flags, s);
         else
             launch_insert_windows(table_args(c), c->mh.as<u64>(), c->mread.as<u32>(), c->roff.as<u64>(), b.m0, b.m1, b.slot0, b.first_ordinal,
-                                  scal(c) + SC_NWINDOWS, flags, s);
+                                  scal(c) + SC_NWINDOWS, flags, s, nullptr, 0, adm_of(c, b), b.m0);
     }
     return MDBG_OK;
 }
@@ -411,7 +411,7 @@ int launch_round_inserts(mdbg_ctx* c, size_t first, size_t last) {
 // trip at the end (the insert kernels do nothing if the table has to grow first; then it is grown and the round repeats).
 // allow_pending: reserved regions may be waiting for their data (the multi-GPU layer inserts what has landed while the next round
 // travels): only committed batches are touched, the regions in flight are not registered yet.
-int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
+int insert_round_impl(mdbg_ctx* c, bool allow_pending) {
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
     if (c->routed) return fail(c, MDBG_E_STATE, "table holds routed records; local insertion is not allowed");
     if (c->pending_m && !allow_pending) return fail(c, MDBG_E_STATE, "reserved sketch regions have not been committed");
@@ -426,7 +426,7 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
     bool counts_known = c->own_world > 1;
     u64 known = 0;
     for (size_t i = first; i < last; ++i) { const Batch& b = c->batches[i]; if (b.m1 == b.m0) continue; if (b.owned == ~0ull) counts_known = false; else known += b.owned; }
-    int e = count_round_windows(c, first, last, counts_known, known); if (e) return e;
+    int e = prefilter_on(c) ? prefilter_admit(c, first, last) : count_round_windows(c, first, last, counts_known, known); if (e) return e;      // (pre-filter: SC_BATCHWIN <- the ADMITTED windows)
     u32* const flags = (u32*)(scal(c) + SC_CAPERR);                // [0] window index overflow, [1] table too small
     u64 total_idx = 0;
     for (size_t i = first; i < last; ++i) total_idx += c->batches[i].m1 - c->batches[i].m0;
@@ -460,6 +460,25 @@ int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
     if (counts_known && sc[SC_OWNINS] != known) return fail(c, MDBG_E_PARAM, mismatch);
     return close_round(c, sc, mismatch, ev_ms(c));      // (a probe error is reported together with the mismatch)
 }
+// The insertion of whatever is resident and not in the table.  With the counting pre-filter the round inserts the ADMITTED windows of its batches, and it starts from
+// batch 0 whenever a batch has been counted since the round before (prefilter_prepare).
+int insert_resident_impl(mdbg_ctx* c, bool allow_pending) {
+    if (!prefilter_on(c)) return insert_round_impl(c, allow_pending);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    if (c->routed || c->own_world > 1 || c->pending_m) return fail(c, MDBG_E_STATE, PF_UNAVAILABLE);
+    int e = prefilter_prepare(c); if (e) return e;
+    bool any = false;
+    for (size_t i = c->batches_inserted; i < c->batches.size(); ++i) any = any || c->batches[i].m1 > c->batches[i].m0;
+    const u64 before = c->n_windows;
+    e = insert_round_impl(c, allow_pending); if (e) return e;
+    if (any) {             // close_round added the round's SC_BATCHWIN, the admitted windows; the round's last read_scalars published SC_NWINDOWS, all windows of its batches
+        c->n_windows_admitted += c->n_windows - before;
+        c->n_windows = before + c->h_scal[SC_NWINDOWS];
+    }
+    return MDBG_OK;
+}
+// What an ingest call does behind its sketch: the batch's windows into the table — or, with the counting pre-filter, into the filter only
+int insert_after_sketch(mdbg_ctx* c) { return prefilter_on(c) ? prefilter_count_pending(c) : insert_resident_impl(c); }
 }  // namespace
 
 extern "C" {
@@ -484,7 +503,7 @@ int mdbg_ingest_batch_device(mdbg_ctx* c, const uint8_t* d_bases, const uint64_t
     bool inserted = false;
     int e = sketch_device_impl(c, d_bases, d_offsets, n_reads, n_bases, first_read_ordinal, true, &inserted);
     if (e) return e;
-    return inserted ? MDBG_OK : insert_resident_impl(c);
+    return inserted ? MDBG_OK : insert_after_sketch(c);
 }
 
 // Copies a host batch into a free staging slot (waits for one), WITHOUT the context lock: the copy of one caller overlaps
@@ -538,7 +557,7 @@ int mdbg_ingest_batch(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
     e = sketch_device_impl(c, hold.g->bases.as<u8>(), hold.g->off.as<u64>(), n_reads, nb, first_read_ordinal); if (e) return e;
-    return insert_resident_impl(c);
+    return insert_after_sketch(c);
 }
 
 // ---- 2-bit packed input (see include/mdbg_hip.h) -------------------------------------------------------------
@@ -554,7 +573,7 @@ static int packed_device_impl(mdbg_ctx* c, const mdbg_packed_batch* b, u64 n_bas
     SketchInput in; in.fmt = FMT_PLANES; in.d_planes = (const uint2*)b->words; in.d_exc_pos = b->exc_pos; in.d_exc_val = b->exc_val; in.n_exc = b->n_exc;
     bool inserted = false;
     e = sketch_device_impl(c, in, b->offsets, b->n_reads, n_bases, first_ordinal, insert, &inserted); if (e) return e;
-    return insert && !inserted ? insert_resident_impl(c) : MDBG_OK;
+    return insert && !inserted ? insert_after_sketch(c) : MDBG_OK;
 }
 int mdbg_ingest_batch_packed_device(mdbg_ctx* c, const mdbg_packed_batch* b, uint64_t n_bases, uint64_t first_read_ordinal) {
     if (!c) return MDBG_E_PARAM;
@@ -672,6 +691,7 @@ int mdbg_query_batch(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets,
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
     if (c->routed) return fail(c, MDBG_E_STATE, "not available for a routed table");
     if (c->own_world > 1) return fail(c, MDBG_E_STATE, "not available for a partitioned table: k-min-mers owned by other ranks would read as absent");
+    if (prefilter_on(c)) { const int e = insert_resident_impl(c); if (e) return e; }      // the table as it stands = the admitted windows of everything resident
     c->q_counts.clear(); c->q_off.assign(n_reads + 1, 0);
     if (n_reads) {
         // sketch into the resident store behind everything that is there, look the windows up; the store is rolled back on every way out of this block
@@ -714,7 +734,8 @@ int mdbg_reset(mdbg_ctx* c, uint32_t new_k) {
     int e = clear_table(c); if (e) return e;
     c->ms_sketch = c->ms_insert = c->ms_finalize = 0; c->ms_tile = 0; c->n_tile_launches = 0; c->n_tile_bases = 0;
     if (c->link_ctr.p) (void)hipMemsetAsync(c->link_ctr.p, 0, 8, c->stream);
-    if (new_k == 0) { store_truncate(c, 0); c->n_tiles = c->n_slow_tiles = 0; return MDBG_OK; }
+    prefilter_invalidate(c);
+    if (new_k == 0) { store_truncate(c, 0); prefilter_drop(c); c->n_tiles = c->n_slow_tiles = 0; return MDBG_OK; }
     if (new_k < 2 || new_k > 4096) return fail(c, MDBG_E_PARAM, "bad k");
     if (new_k != c->P.k) for (Batch& b : c->batches) { b.owned = ~0ull; b.list_off = ~0ull; }      // the senders' window counts and lists were for the old k
     c->P.k = new_k;
@@ -766,6 +787,7 @@ int mdbg_rewind(mdbg_ctx* c, uint64_t mark) {
     c->poisoned = 0;
     int e = clear_table(c); if (e) return e;
     store_truncate(c, (size_t)mark);
+    prefilter_invalidate(c);
     return MDBG_OK;
 }
 
@@ -785,6 +807,7 @@ int mdbg_get_stats(mdbg_ctx* c, mdbg_stats* o) {
     o->ms_sketch = c->ms_sketch; o->ms_insert = c->ms_insert; o->ms_finalize = c->ms_finalize;
     o->ms_sketch_tile = c->ms_tile; o->n_sketch_tile_launches = c->n_tile_launches; o->n_sketch_tile_bases = c->n_tile_bases;
     o->tile_bases = TILE_STRIDE;
+    o->n_windows_admitted = c->n_windows_admitted; o->prefilter_cells = c->pf_n_cells;
     if (c->link_ctr.p) {
         (void)hipSetDevice(c->dev);
         HIPCHK(c, hipStreamSynchronize(c->stream));

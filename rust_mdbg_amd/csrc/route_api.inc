@@ -6,6 +6,7 @@ int mdbg_route_pack(mdbg_ctx* c, uint32_t world, const uint64_t** d_records, uin
     MDBG_LOCK(c);
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    if (prefilter_on(c)) return fail(c, MDBG_E_STATE, PF_UNAVAILABLE);
     if (world < 1 || world > 64) return fail(c, MDBG_E_PARAM, "world must be 1..64");
     hipStream_t s = c->stream;
     const u32 k = c->P.k, RS = k + 2;
@@ -74,6 +75,7 @@ int mdbg_insert_records(mdbg_ctx* c, const uint64_t* d_records, uint64_t n) {
     MDBG_LOCK(c);
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    if (prefilter_on(c)) return fail(c, MDBG_E_STATE, PF_UNAVAILABLE);
     if (!c->routed && c->n_distinct) return fail(c, MDBG_E_STATE, "table already holds locally inserted k-min-mers");
     c->routed = true;
     if (!n) return MDBG_OK;
@@ -103,6 +105,7 @@ int mdbg_routed_export(mdbg_ctx* c, uint32_t world, const uint64_t* span_lo, con
     MDBG_LOCK(c);
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    if (prefilter_on(c)) return fail(c, MDBG_E_STATE, PF_UNAVAILABLE);
     if (world < 1 || world > 64 || n_spans < 1 || n_spans > 4096) return fail(c, MDBG_E_PARAM, "bad world / spans");
     memset(out, 0, sizeof *out);
     hipStream_t s = c->stream;

@@ -376,9 +376,13 @@ static size_t insert_windows_lds(const TableArgs& T) {
     const size_t codes = T.own_world > 1 && T.own_thr ? 2 * ((size_t)OWN_SPAN + T.ks.k) * sizeof(u16) : 0;
     return (OWN_SPAN + T.ks.k) * sizeof(u64) + OWN_SPAN * sizeof(u16) + 16 + OWN_SPAN + codes;
 }
+// GATED (the counting pre-filter, prefilter.hip): a window is inserted only when its admission bit is set — bit (i - adm_i0) of adm[], written by prefilter_admit_kernel
+// for the batch that starts at adm_i0.  That is the only difference: the ungated instantiation is the kernel as it was (adm is never read; its instruction stream is
+// the one of the kernel before the template, profiles/prefilter_notes.md), and both write every claim byte of their span.
+template <bool GATED>
 __global__ __launch_bounds__(256) void insert_windows_kernel(TableArgs T, const u64* __restrict__ mh, const u32* __restrict__ mread,
                                                                    const u64* __restrict__ roff, u64 i0, u64 i1, u32 slot0, u64 first_ordinal,
-                                                                   u32* __restrict__ cap_err, const u64* __restrict__ i1_dev, u64 n_lim) {
+                                                                   u32* __restrict__ cap_err, const u64* __restrict__ i1_dev, u64 n_lim, const u64* __restrict__ adm, u64 adm_i0) {
     extern __shared__ u64 sh_keys[];           // [OWN_SPAN + k] keys, then u16 list[OWN_SPAN], then the counter, then u8 cl[OWN_SPAN], then (partitioned table) 2 x u16 codes[OWN_SPAN + k]
     if (cap_err[1]) return;
     // i1_dev: launched behind the sketch of the same batch before the host knew how many minimizers it has (i1 = an upper bound the grid was
@@ -409,6 +413,7 @@ __global__ __launch_bounds__(256) void insert_windows_kernel(TableArgs T, const 
         const u64 i = b0 + li;
         bool mine = false;
         bool own = i + k <= i1;
+        if (GATED) { if (own) own = (adm[(i - adm_i0) >> 6] >> ((i - adm_i0) & 63)) & 1ull; }
         if (own && T.own_world > 1) {
             if (by_codes) { const u16 x = mc[li], y = mc[li + k - pc]; own = owner_of_code(x < y ? x : y, oc) == T.own_rank; }
             else own = window_owner(sh_keys + li, k, OwnerSpec{T.own_world, T.own_thr}) == T.own_rank;
@@ -450,12 +455,16 @@ __global__ __launch_bounds__(256) void insert_windows_kernel(TableArgs T, const 
         for (u32 li = threadIdx.x; li < hi && li < n_lim - (u64)blockIdx.x * OWN_SPAN; li += 256) T.claim[b0 + li] = cl[li];
     }
 }
+// adm (null: every window): the admission bits of the batch that starts at minimizer index adm_i0, see insert_windows_kernel
 void launch_insert_windows(const TableArgs& T, const u64* mh, const u32* mread, const u64* roff, u64 i0, u64 i1, u32 slot0,
-                           u64 first_ordinal, u64* n_windows, u32* cap_err, hipStream_t s, const u64* i1_dev = nullptr, u64 n_starts = 0) {
+                           u64 first_ordinal, u64* n_windows, u32* cap_err, hipStream_t s, const u64* i1_dev = nullptr, u64 n_starts = 0,
+                           const u64* adm = nullptr, u64 adm_i0 = 0) {
     if (i1 <= i0) return;
     (void)n_windows;
     const u64 n = n_starts ? n_starts : i1 - i0;          // n_starts: only the window starts [i0, i0 + n_starts) (a slice; i1 stays the end of the batch)
-    hipLaunchKernelGGL(insert_windows_kernel, dim3((unsigned)((n + OWN_SPAN - 1) / OWN_SPAN)), dim3(256), insert_windows_lds(T), s, T, mh, mread, roff, i0, i1, slot0, first_ordinal, cap_err, i1_dev, n);
+    const dim3 grid((unsigned)((n + OWN_SPAN - 1) / OWN_SPAN));
+    if (adm) hipLaunchKernelGGL(insert_windows_kernel<true>, grid, dim3(256), insert_windows_lds(T), s, T, mh, mread, roff, i0, i1, slot0, first_ordinal, cap_err, i1_dev, n, adm, adm_i0);
+    else hipLaunchKernelGGL(insert_windows_kernel<false>, grid, dim3(256), insert_windows_lds(T), s, T, mh, mread, roff, i0, i1, slot0, first_ordinal, cap_err, i1_dev, n, adm, adm_i0);
 }
 
 // routed records (k canonical u64, ordinal, key hash) sitting in the arena at record index r0..

@@ -23,7 +23,8 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False, transits=0):
+             threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False, transits=0,
+             prefilter=False, prefilter_cells=0):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -55,6 +56,9 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     store right after the edges (Emitter.write_sequences_from_kept: Mdbg.graph_node_seqs in chunks), not in the second pass — which then only runs if the
     contigs still need it (contigs without keep_reads).  Same lines per file, in row order (byte-identical files when the second pass sees the input as one
     batch).  The time goes to seconds_until["sequences_kept"]; "sequences" keeps meaning the second pass and is absent when there is none.  Adds kept_reads.
+    prefilter: the reference's --bf, order-free (Mdbg(prefilter=True); include/mdbg_hip.h, MDBG_FLAG_PREFILTER): k-min-mers seen once stay out of the table unless they
+    share a filter cell; the same S and L lines up to the node names (DbgEntry.index counts the keys the table holds).  prefilter_cells: 2-bit cells, 0 = 2^32.
+    Needs min_abundance >= 2.  Adds n_windows_admitted.
     threads: host threads of the reader (uncompressed input: mdbg_reader_open_mt) and of the 2-bit packer; packed: hand the GPU 2-bit
     packed batches (a quarter of the bytes over PCIe), default: when threads > 1"""
     if packed is None:
@@ -123,7 +127,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
         stitched = bool(contigs and keep_reads)      # the contigs' bases come from the device store, not from a second pass
         seq_kept = bool(write_sequences and sequences_from_kept)      # so do the node sequences
         kept = None
-        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=stitched or seq_kept) as m:
+        with Mdbg(k, l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=stitched or seq_kept, prefilter=prefilter, prefilter_cells=prefilter_cells) as m:
             apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max)
             tm["open"] = time.perf_counter() - t0
             while True:
@@ -278,6 +282,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
             sctg.write_fasta(prefix + ".msimpl.fa")
             extra["n_simplified"] = len(sctg)
             extra["simplify"] = sstats
+    if prefilter:
+        extra["n_windows_admitted"] = stats["n_windows_admitted"]
     return dict(extra, n_reads=n_reads, n_bases=n_bases, n_minimizers=stats["n_minimizers"], n_windows=stats["n_windows"],
                 n_nodes_before=nodes["n_nodes_before"], n_nodes=nodes["n_nodes"], n_edges=len(edges["n1"]),
                 presimp_removed=edges["presimp_removed"], seconds_until={k_: round(v, 4) for k_, v in tm.items()})
@@ -297,7 +303,7 @@ def concat_records(seqs):
 
 def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
                strip_newlines=False, device=-1, contigs_fn=None, min_contig_len=100000, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
-               keep_reads=False, simplify_steps=None):
+               keep_reads=False, simplify_steps=None, prefilter=False, prefilter_cells=0):
     """One pass over the reads, one graph per k (the k sweep of the reference's utils/multik:69-78): the reads are sketched once,
     the sketches stay resident on the GPU, and every k only clears and refills the counting table (mdbg_reset) and rebuilds nodes
     and edges.  Writes <prefix>-k<k>.gfa; -> {k: counters}.
@@ -314,7 +320,9 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     producer, e.g. api.MAGIC_SUPERBUBBLE_STEPS (steps that need no resident reads: tips, bubbles, superbubbles, components).
     keep_reads (with the two built-in producers): the reads stay packed on the device (Mdbg(keep_reads=True)); a round's contigs are stitched there
     (mdbg_graph_contigs_device(min_contig_len)) and ingested for the next round straight from that device buffer, twice, with first ordinals 0 and C — the
-    ordinals the concatenated contigs + contigs batch gives.  No Reader is opened after the first pass; same counters, same files."""
+    ordinals the concatenated contigs + contigs batch gives.  No Reader is opened after the first pass; same counters, same files.
+    prefilter, prefilter_cells: every round with the counting pre-filter (the script runs `--minabund 2 --bf`), see run_file: the filter is counted anew per k and
+    per round's contigs."""
     import ctypes
     ks = list(ks)
     schedule = MAGIC_SIMPLIFY_STEPS if simplify_steps is None else list(simplify_steps)
@@ -322,7 +330,7 @@ def run_multik(path, prefix, ks, l, density, min_abundance=2, reads_already_hpc=
     out = {}
     n_reads = n_bases = 0
     base = READ_ORDINAL_BASE if contigs_fn is not None else 0
-    with Mdbg(ks[0], l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=on_device) as m, Reader(path, strip_newlines) as r:
+    with Mdbg(ks[0], l, density, min_abundance, reads_already_hpc=reads_already_hpc, device=device, keep_reads=on_device, prefilter=prefilter, prefilter_cells=prefilter_cells) as m, Reader(path, strip_newlines) as r:
         apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_max)
         for bases, offs in r.batches(batch_bases):
             m.ingest(bases, offs, base + n_reads)
