@@ -15,6 +15,11 @@
  *   one summary line
  *   --transits N (implies --contigs): the reads that span a unitig end to end (mdbg_graph_transits, in ranges of 2^20 reads, the counts merged by key) and whether
  *   the pairs seen N times or more match a repeat's entrances to its exits: <prefix>.unitigs.transits.tsv (and <prefix>.msimpl.transits.tsv) and one summary line each
+ *   --gaf (implies --contigs): the resident reads aligned to the unitig list (mdbg_graph_alignments of mdbg_align.h, in ranges of 2^20 reads), one GAF line per
+ *   alignment through libmdbg_emit's mdbg_gaf_append: <prefix>.unitigs.gaf (and <prefix>.msimpl.gaf) and one summary line each; qname is the read's ordinal
+ *   --query FILE (implies --contigs): the sequences of FILE, which are no part of the graph, aligned to the unitig list without changing it
+ *   (mdbg_graph_align_batch): <prefix>.unitigs.query.gaf and <prefix>.unitigs.query.tsv (ordinal, k-min-mers, those found on the list, their share in percent;
+ *   and the .msimpl. pair) and one summary line each
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
  *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
@@ -32,6 +37,7 @@
 #include <string.h>
 #include <time.h>
 
+#include "mdbg_align.h"
 #include "mdbg_emit.h"
 #include "mdbg_hip.h"
 
@@ -90,6 +96,76 @@ static void* nodejob_main(void* arg) {
 static void die(mdbg_ctx* ctx, const char* what, int rc) {
     fprintf(stderr, "%s: %s (%s)\n", what, mdbg_strerror(rc), ctx && mdbg_last_error(ctx) ? mdbg_last_error(ctx) : "");
     exit(1);
+}
+
+/* ---- --gaf and --query: alignments (mdbg_align.h) as GAF lines, through libmdbg_emit's writer ---- */
+static uint64_t* note_lengths(uint64_t* lens, uint64_t* cap, uint64_t first, const uint64_t* offs, uint64_t n) {
+    if (first + n > *cap) {
+        *cap = 2 * (first + n) + 1024;
+        lens = (uint64_t*)realloc(lens, *cap * sizeof *lens);
+        if (!lens) die(NULL, "realloc", MDBG_E_NOMEM);
+    }
+    for (uint64_t q = 0; q < n; ++q) lens[first + q] = offs[q + 1] - offs[q];
+    return lens;
+}
+/* the resident reads in ranges of 2^20, the writer appending range after range; lens[q] = the raw length of read q */
+static void write_gaf(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* path, const uint64_t* lens, const char* what) {
+    uint64_t first = 0, n_aln = 0, n_chained = 0;
+    FILE* f = fopen(path, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    fclose(f);
+    for (;;) {
+        mdbg_alignment_list al;
+        int rc = mdbg_graph_alignments(ctx, first, (uint64_t)1 << 20, &al);
+        if (rc) die(ctx, "mdbg_graph_alignments", rc);
+        if (!al.n_reads) break;
+        rc = mdbg_gaf_append(path, 0, &al, ul, lens + first);
+        if (rc) die(NULL, "mdbg_gaf_append", rc);
+        n_aln += al.n_alignments; n_chained += al.n_chained; first += al.n_reads;
+    }
+    printf("alignments%s: %llu of %llu reads, %llu steps chained over a record\n", what, (unsigned long long)n_aln, (unsigned long long)first, (unsigned long long)n_chained);
+}
+/* the sequences of `file`, which are no part of the graph, in the reader's batches: <stem>.query.gaf and <stem>.query.tsv (ordinal, windows, placed, percent) */
+static void write_query(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* stem, const char* file, int reference, const char* what) {
+    char gaf[4096], tsv[4096];
+    int err = 0;
+    uint64_t first = 0, n_aln = 0, n_found = 0;
+    snprintf(gaf, sizeof gaf, "%s.query.gaf", stem); snprintf(tsv, sizeof tsv, "%s.query.tsv", stem);
+    FILE* f = fopen(gaf, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    fclose(f);
+    f = fopen(tsv, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    mdbg_reader* rd = mdbg_reader_open(file, reference, &err);
+    if (!rd) die(NULL, "mdbg_reader_open", err);
+    for (;;) {
+        const uint8_t* bases; const uint64_t* offs; uint64_t n;
+        int rc = mdbg_reader_next(rd, 256u << 20, &bases, &offs, &n);
+        if (rc) die(NULL, "mdbg_reader_next", rc);
+        if (!n) break;
+        mdbg_alignment_list al;
+        rc = mdbg_graph_align_batch(ctx, bases, offs, n, &al);
+        if (rc) die(ctx, "mdbg_graph_align_batch", rc);
+        uint64_t* lens = (uint64_t*)malloc(2 * n * sizeof *lens);    /* the lengths, and the ordinals in the FILE: the call numbers a batch from 0 */
+        if (!lens) die(NULL, "malloc", MDBG_E_NOMEM);
+        uint64_t* ord = lens + n;
+        for (uint64_t q = 0; q < n; ++q) { lens[q] = offs[q + 1] - offs[q]; ord[q] = first + q; }
+        al.ordinal = ord;
+        rc = mdbg_gaf_append(gaf, 0, &al, ul, lens);
+        if (rc) die(NULL, "mdbg_gaf_append", rc);
+        for (uint64_t q = 0; q < al.n_reads; ++q) {
+            uint64_t placed = 0;
+            for (uint64_t s = al.step_offsets[q]; s < al.step_offsets[q + 1]; ++s) placed += al.step_windows[s];
+            const uint32_t w = al.read_windows[q];
+            fprintf(f, "%llu\t%u\t%llu\t%.2f\n", (unsigned long long)ord[q], w, (unsigned long long)placed, w ? 100.0 * (double)placed / (double)w : 0.0);
+            n_found += placed > 0;
+        }
+        free(lens);
+        n_aln += al.n_alignments; first += n;
+    }
+    mdbg_reader_close(rd);
+    if (fclose(f) != 0) die(NULL, "fclose", MDBG_E_IO);
+    printf("query%s: %llu sequences, %llu with a k-min-mer on the list, %llu alignments\n", what, (unsigned long long)first, (unsigned long long)n_found, (unsigned long long)n_aln);
 }
 
 /* ---- --transits: the rows of the ranges merged by key, the verdict rule of mdbg_graph_transits on the merged counts, the .transits.tsv ---- */
@@ -162,7 +238,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0; uint64_t transits = 0;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0, gaf = 0; uint64_t transits = 0; const char* query = NULL;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L / -e N / -r N / -R N / -B N,L append steps of their own, in command-line order */
@@ -244,6 +320,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--read-paths")) read_paths = 1;
         else if (!strcmp(argv[i], "--junctions")) junctions = 1;
         else if (!strcmp(argv[i], "--transits") && i + 1 < argc) { transits = strtoull(argv[++i], NULL, 10); if (!transits) { fprintf(stderr, "--transits takes a min_support >= 1\n"); return 2; } }
+        else if (!strcmp(argv[i], "--gaf")) gaf = 1;
+        else if (!strcmp(argv[i], "--query") && i + 1 < argc) query = argv[++i];
         else if (!strcmp(argv[i], "--bf")) p.flags |= MDBG_FLAG_PREFILTER;                      /* main.rs --bf, order-free: the counting pre-filter in front of the node table */
         else if (!strcmp(argv[i], "--bf-cells") && i + 1 < argc) p.prefilter_cells = strtoull(argv[++i], NULL, 10);   /* its number of 2-bit cells (default 2^32) */
         else if (!strcmp(argv[i], "--skiphpc")) p.reads_already_hpc = 1;                         /* main.rs:490 */
@@ -252,9 +330,9 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--bf [--bf-cells N]] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--bf [--bf-cells N]] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--gaf] [--query FILE] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
-    if (simplify || components || read_paths || junctions || transits) contigs = 1;
+    if (simplify || components || read_paths || junctions || transits || gaf || query) contigs = 1;
     if (!contigs) keep_reads = 0;
     if (!write_sequences) seq_kept = 0;
     if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
@@ -277,6 +355,7 @@ int main(int argc, char** argv) {
     /* the batch buffers come from the GPU library: page-locked by the first ingest call that sees them, so a batch crosses PCIe as one DMA */
     { const int rc = mdbg_reader_set_allocator(rd, mdbg_host_alloc, mdbg_host_free); if (rc) die(NULL, "mdbg_reader_set_allocator", rc); }
     uint64_t n_reads = 0, n_bases = 0, first = 0;
+    uint64_t* read_lens = NULL; uint64_t lens_cap = 0;              /* --gaf: the raw length of every read, from the batch offsets */
     double t_wait = 0, t_gpu = 0;                                   /* --timing: where the ingest loop spends its time */
     if (threads > 1) {                                              /* any input: the streaming reader (.gz, .lz4) packs on the reader thread */
         /* reader thread one batch ahead; this thread packs to 2 bits per base and ingests */
@@ -294,6 +373,7 @@ int main(int argc, char** argv) {
             rc = mdbg_ingest_batch_packed(ctx, &pb, first);
             if (rc) die(ctx, "mdbg_ingest_batch_packed", rc);
             t_gpu += now_s() - ta;
+            if (gaf) read_lens = note_lengths(read_lens, &lens_cap, first, pb.offsets, pb.n_reads);
             first += pb.n_reads; n_reads += pb.n_reads; n_bases += pb.offsets[pb.n_reads];
         }
         pthread_join(th, NULL);
@@ -304,6 +384,7 @@ int main(int argc, char** argv) {
         if (!n) break;
         rc = mdbg_ingest_batch(ctx, bases, offs, n, first);          /* process_read_aux over the batch */
         if (rc) die(ctx, "mdbg_ingest_batch", rc);
+        if (gaf) read_lens = note_lengths(read_lens, &lens_cap, first, offs, n);
         first += n; n_reads += n; n_bases += offs[n];
     }
     mdbg_reader_close(rd);
@@ -378,6 +459,8 @@ int main(int argc, char** argv) {
         /* n_entries == rows of the node table - total_nodes_removed + copies (mdbg_hip.h); no read is placed on a list with copies: no .msimpl.transits.tsv then */
         if (repeat_steps) printf("simplify: %llu entries copied\n", (unsigned long long)(sl.n_entries ? sl.n_entries + ss.total_nodes_removed - nodes.n : 0));
         if (transits && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl.transits.tsv", prefix); write_transits(ctx, &sl, path, transits, " (simplified)"); }
+        if (gaf && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl.gaf", prefix); write_gaf(ctx, &sl, path, read_lens, " (simplified)"); }
+        if (query && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl", prefix); write_query(ctx, &sl, path, query, reference, " (simplified)"); }
         sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
         if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
         if (keep_reads) {                                           /* the sequences from the device store instead of the second pass */
@@ -441,6 +524,8 @@ int main(int argc, char** argv) {
                    (unsigned long long)unsupported, (unsigned long long)crossings, (unsigned long long)missing);
         }
         if (transits) { snprintf(path, sizeof path, "%s.unitigs.transits.tsv", prefix); write_transits(ctx, &ul, path, transits, ""); }
+        if (gaf) { snprintf(path, sizeof path, "%s.unitigs.gaf", prefix); write_gaf(ctx, &ul, path, read_lens, ""); }
+        if (query) { snprintf(path, sizeof path, "%s.unitigs", prefix); write_query(ctx, &ul, path, query, reference, ""); }
         if (keep_reads) {
             mdbg_contig_seqs cs;
             rc = mdbg_graph_contigs(ctx, 0, &cs);
@@ -502,6 +587,7 @@ int main(int argc, char** argv) {
         if (rc) die(NULL, "mdbg_emit_contigs_write_fasta", rc);
         mdbg_emit_contigs_close(sctg);
     }
+    free(read_lens);
     mdbg_destroy(ctx);
     return 0;
 }

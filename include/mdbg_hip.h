@@ -807,6 +807,8 @@ int mdbg_graph_transits(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, 
 int mdbg_graph_transits_device(mdbg_ctx* ctx, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out);
 int mdbg_transits_ms(mdbg_ctx* ctx, double* ms);
 
+/* ---- alignments: the steps of the read paths chained over edge records, with base coordinates; queries that are not resident; GAF lines: include/mdbg_align.h ---- */
+
 /* ---- multi-GPU, second mode: replicated sketches, partitioned table ----------------------------------------
  * Within one node the sketch is much more compact than the k-min-mers cut from it (every minimizer sits in k windows),
  * so the ranks may exchange SKETCHES instead (one all-gather), each rank then windows the global sketch but inserts only

@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from . import align as _align
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -108,6 +110,10 @@ class ReadPathList(C.Structure):       # mdbg_read_path_list
 # (field, dtype, what it has one element of: "read", "step" or "unitig")
 READ_PATH_FIELDS = (("ordinal", np.uint64, "read"), ("read_windows", np.uint32, "read"), ("first_window", np.uint32, "step"), ("step_windows", np.uint32, "step"), ("unitig", np.uint32, "step"),
                     ("first_entry", np.uint32, "step"), ("strand", np.uint8, "step"), ("support_windows", np.uint64, "unitig"), ("support_steps", np.uint64, "unitig"))
+
+
+# the columns of Mdbg.graph_alignments / align_batch (include/mdbg_align.h), in the style of READ_PATH_FIELDS: (field, dtype, "read" / "step" / "alignment")
+ALIGNMENT_FIELDS, ALIGNMENT_OFFSETS, ALIGNMENT_COUNTS = _align.ALIGNMENT_FIELDS, _align.ALIGNMENT_OFFSETS, _align.ALIGNMENT_COUNTS
 
 
 def read_path_text(rp, circular):
@@ -455,6 +461,7 @@ def load_library():
               "mdbg_ingest_sketch", "mdbg_finalize_begin", "mdbg_finalize_end", "mdbg_ingest_batch_packed",
               "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device"):
         getattr(L, f).restype = C.c_int
+    _align.declare_hip(L)                                  # include/mdbg_align.h
     _LIB = L
     return L
 
@@ -876,6 +883,39 @@ class Mdbg:
         ms = C.c_double()
         self._chk(self.L.mdbg_transits_ms(self.h, C.byref(ms)))
         return float(ms.value)
+
+    def graph_alignments(self, first_read=0, max_reads=0):
+        """the resident reads [first_read, first_read + max_reads) (0: to the end) aligned to the current unitig list on the GPU: the steps of graph_read_paths chained
+        over the list's edge records into alignments, with base coordinates on the read and on the path of unitigs (mdbg_graph_alignments, include/mdbg_align.h).  The
+        call is the read-path call of the range too; it leaves the list and every other result as they are.
+        -> dict(first_read, n_reads, n_windows, n_placed, n_steps, n_chained, n_alignments, n_wraps, n_unitigs; per read ordinal, read_windows, step_offsets[n_reads + 1],
+        aln_offsets[n_reads + 1]; per step first_window, step_windows, unitig, first_entry, strand, step_record; aln_step_offsets[n_alignments + 1]; per alignment
+        aln_windows, query_begin, query_end, path_length, path_begin, path_end)"""
+        al = _align.AlignmentList()
+        self._chk(self.L.mdbg_graph_alignments(self.h, first_read, max_reads, C.byref(al)))
+        return _align.alignment_dict(al)
+
+    def graph_alignments_device(self, first_read=0, max_reads=0):
+        """-> AlignmentList with DEVICE pointers (valid until the next alignment call; its step columns until the next read-path call)"""
+        al = _align.AlignmentList()
+        self._chk(self.L.mdbg_graph_alignments_device(self.h, first_read, max_reads, C.byref(al)))
+        return al
+
+    def alignments_ms(self):
+        """device time of the last graph_alignments* / align_batch call, in milliseconds"""
+        ms = C.c_double()
+        self._chk(self.L.mdbg_alignments_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def align_batch(self, bases, offsets):
+        """sequences that are NOT resident (genes, a reference, contigs) aligned to the current unitig list: the batch is sketched behind the store, aligned as
+        graph_alignments aligns resident reads, and the store rolled back; nothing but the alignment and the read-path result changes (mdbg_graph_align_batch,
+        include/mdbg_align.h).  -> the dict of graph_alignments; read q is query q, ordinal[q] == q"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        al = _align.AlignmentList()
+        self._chk(self.L.mdbg_graph_align_batch(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(al)))
+        return _align.alignment_dict(al)
 
     def kept_reads(self):
         """the resident read store of a keep_reads context -> dict(n_reads, n_bases, bytes); bytes = n_bases / 4 + 8 per read + 9 per exception, up to the

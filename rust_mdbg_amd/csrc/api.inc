@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mdbg_hip.h"
+#include "../../include/mdbg_align.h"
 #include "edges.h"
 #include "unitigs.h"
 #include "simplify.h"
@@ -24,6 +25,7 @@
 #include "read_paths.h"
 #include "junctions.h"
 #include "transits.h"
+#include "alignments.h"
 
 #include "blocks.inc"
 #include "results.inc"      // the derived graph results and which of them are current

@@ -448,3 +448,88 @@ static int transits_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, u
 int mdbg_graph_transits(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out) { return transits_impl(c, first_read, max_reads, min_support, out, true); }
 int mdbg_graph_transits_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint64_t min_support, mdbg_transit_list* out) { return transits_impl(c, first_read, max_reads, min_support, out, false); }
 int mdbg_transits_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.transits.ms : nullptr, ms); }
+
+// ---- alignments: the steps chained over edge records, with base coordinates (alignments.hip; include/mdbg_align.h) ------
+// The stage over the range of `pw`, and the hand-over of both results it fills: the read paths' (whose step columns the list shares) and its own.
+static int alignments_over(mdbg_ctx* c, PlaceWindows& pw, mdbg_alignment_list* out, bool to_host) {
+    Results& R = c->res;
+    auto& P = R.rpaths; auto& A = R.alns;
+    const FinArgs& F = pw.F;
+    AlignmentNodes nd; nd.index = F.o_index; nd.src_start = F.o_src_start; nd.src_end = F.o_src_end; nd.n_rows = R.n_rows(); nd.positions = c->mpos.as<u32>(); nd.l = c->P.l;
+    ReadPathResult rp; AlignmentResult r;
+    const hipError_t he = alignments_run(A.buf.get(), P.buf.get(), R.placement.buf.get(), R.unitigs.last, nd, pw.rg, WindowPlacer{place_windows, &pw}, c->stream, &rp, &r);
+    if (he != hipSuccess) return fail_hip(c, "alignments_run", he);
+    A.ms = P.ms = r.ms;
+    if (r.defect & AL_DEFECT_RECORD) return fail(c, MDBG_E_DEVICE, "a record an alignment needs is absent or outside the list (the closing record of a ring a step wraps), or a window reaches past its range");
+    if (r.defect) return stage_defect(c, r.defect);
+    const u64 nr = rp.n_reads, ns = rp.n_steps, na = r.n_alignments;
+    out->n_reads = nr; out->n_windows = rp.n_windows; out->n_placed = rp.n_placed; out->n_steps = ns; out->n_chained = r.n_chained; out->n_alignments = na; out->n_wraps = r.n_wraps;
+    out->n_unitigs = rp.n_unitigs;
+    HandOver ho{c, "host copy of the alignments", to_host};
+    ho.col(rp.ordinal, nr, P.ord, &out->ordinal);
+    ho.col(rp.read_windows, nr, P.rw, &out->read_windows);
+    ho.col(rp.step_offsets, nr + 1, P.off, &out->step_offsets);
+    ho.col(rp.first_window, ns, P.fw, &out->first_window);
+    ho.col(rp.step_windows, ns, P.nw, &out->step_windows);
+    ho.col(rp.unitig, ns, P.unitig, &out->unitig);
+    ho.col(rp.first_entry, ns, P.fe, &out->first_entry);
+    ho.col(rp.strand, ns, P.strand, &out->strand);
+    ho.col(r.step_record, ns, A.srec, &out->step_record);
+    ho.col(r.aln_offsets, nr + 1, A.aoff, &out->aln_offsets);
+    ho.col(r.aln_step_offsets, na + 1, A.asoff, &out->aln_step_offsets);
+    ho.col(r.aln_windows, na, A.awin, &out->aln_windows);
+    ho.col(r.query_begin, na, A.qbeg, &out->query_begin);
+    ho.col(r.query_end, na, A.qend, &out->query_end);
+    ho.col(r.path_length, na, A.plen, &out->path_length);
+    ho.col(r.path_begin, na, A.pbeg, &out->path_begin);
+    ho.col(r.path_end, na, A.pend, &out->path_end);
+    return ho.err;
+}
+static int alignments_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_alignment_list* out, bool to_host) {
+    MDBG_ENTER(c, out);
+    memset(out, 0, sizeof *out);
+    out->first_read = first_read;
+    PlaceWindows pw; bool empty;
+    c->res.rpaths.ms = 0;
+    const int e = stage_prologue(c, "alignments are", first_read, max_reads, true, &c->res.alns.ms, &pw, &empty);
+    if (e || empty) return e;
+    return alignments_over(c, pw, out, to_host);
+}
+int mdbg_graph_alignments(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_alignment_list* out) { return alignments_impl(c, first_read, max_reads, out, true); }
+int mdbg_graph_alignments_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, mdbg_alignment_list* out) { return alignments_impl(c, first_read, max_reads, out, false); }
+int mdbg_alignments_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.alns.ms : nullptr, ms); }
+
+// a batch that is not resident: sketched behind the store as mdbg_query_batch does it, aligned, and the store rolled back (StoreRollback, store.inc)
+static int align_batch_impl(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out, bool to_host) {
+    if (!c || !out) return MDBG_E_PARAM;
+    u64 nb = 0;
+    StageHold hold;
+    if (n_reads) { int e = stage_host_batch(c, bases, offsets, n_reads, &nb, hold); if (e) return e; }
+    MDBG_LOCK(c);
+    (void)hipSetDevice(c->dev);
+    if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
+    memset(out, 0, sizeof *out);
+    Results& R = c->res;
+    R.rpaths.ms = 0; R.alns.ms = 0;
+    int e;
+    if ((e = refuse_multi_gpu(c, "alignments are")) || (e = refuse_without_unitig_list(c))) return e;
+    if (R.unitig_list_copies()) return fail(c, MDBG_E_STATE, "the current unitig list holds copies made by a REPEATS or NESTED step: no read can be placed on it");
+    if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
+    if (n_reads == 0) return MDBG_OK;
+    const auto held = R.held();                      // the sketch ends the unitig list (an ingest); the rollback below makes the store what the list was built on again
+    struct Restore { Results& R; decltype(held) h; ~Restore() { R.still_holds(h); } } restore{R, held};
+    // sketch into the resident store behind everything that is there, align exactly that batch; the store is rolled back on every way out of this block
+    const StoreRollback tmp(c);
+    e = sketch_device_impl(c, hold.g->bases.as<u8>(), hold.g->off.as<u64>(), n_reads, nb, 0);
+    if (e) { if (e == MDBG_E_ALPHABET) c->poisoned = 0; return e; }          // a bad byte in a query does not poison the node table; a device error does
+    R.still_holds(held);                             // (the stage below asks whether the list is current)
+    const Batch b = c->batches.back();
+    const UnitigResult& ul = R.unitigs.last;
+    PlaceWindows pw; bool empty;
+    if ((e = store_range(c, ul.n_unitigs, ul.n_entries, b.slot0, 0, &pw, &empty)) || empty) return e;
+    if ((e = refuse_too_many_records(c, ul.edges.n))) return e;
+    pw.rg.by_slot0 = nullptr; pw.rg.by_slot_first = nullptr; pw.rg.n_batches = 0;      // the temporary batch is in no batch table: ordinal[q] = q (reads_kernel)
+    return alignments_over(c, pw, out, to_host);
+}
+int mdbg_graph_align_batch(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out) { return align_batch_impl(c, bases, offsets, n_reads, out, true); }
+int mdbg_graph_align_batch_device(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out) { return align_batch_impl(c, bases, offsets, n_reads, out, false); }

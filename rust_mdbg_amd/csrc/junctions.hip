@@ -48,17 +48,12 @@ __global__ __launch_bounds__(256) void cross_kernel(JxArgs a) {
     if (t < a.n_idx) {
         u64 missing = JX_NO_KEY;
         const u32 c = a.code[t];
-        u32 pc;
-        if (adjacent_in_read(a.code, a.roff, a.mread, a.i0, t, c, &pc)) {
-            cnt[0] = 1;
-            if (is_link_of_codes(pc, c, a.unitig_of_entry)) cnt[1] = 1;
-            else {
-                const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
-                const u64 p = lower_bound(a.rkey_sorted, a.R, key);
-                if (p < a.R && a.rkey_sorted[p] == key) { atomicAdd((unsigned long long*)(a.slot + p), 1ull); cnt[2] = 1; }
-                else { missing = key; cnt[3] = 1; }
-            }
-        }
+        u64 key = 0, p = 0;
+        const PairKind kind = classify_pair(a.code, a.roff, a.mread, a.i0, t, c, a.unitig_of_entry, a.rkey_sorted, a.R, &key, &p);
+        if (kind != PAIR_NONE) cnt[0] = 1;
+        if (kind == PAIR_LINK) cnt[1] = 1;
+        else if (kind == PAIR_EXPLAINED) { atomicAdd((unsigned long long*)(a.slot + p), 1ull); cnt[2] = 1; }
+        else if (kind == PAIR_MISSING) { missing = key; cnt[3] = 1; }
         a.mkey[t] = missing;
     }
     block_add<4>(cnt, a.counters, JX_C_ADJACENT);

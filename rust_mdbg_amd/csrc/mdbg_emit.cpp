@@ -30,6 +30,7 @@
 #include <zlib.h>
 
 #include "../../include/mdbg_emit.h"
+#include "../../include/mdbg_align.h"
 #include "gz_inflate.h"
 
 namespace {
@@ -1529,5 +1530,45 @@ int mdbg_emit_contigs_get(const mdbg_contigs* h, uint64_t i, const char** seq, u
 }
 
 void mdbg_emit_contigs_close(mdbg_contigs* h) { delete h; }
+
+// ---- GAF: one line per alignment of an alignment list (include/mdbg_align.h) ------------------------------------------------
+int mdbg_gaf_append(const char* path, int truncate, const mdbg_alignment_list* a, const mdbg_unitig_list* ul, const uint64_t* read_lengths) {
+    if (!path || !a || !ul) return MDBG_E_PARAM;
+    if (a->n_reads && (!read_lengths || !a->ordinal || !a->aln_offsets)) return MDBG_E_PARAM;
+    if (a->n_alignments && (!a->aln_step_offsets || !a->unitig || !a->first_entry || !a->step_windows || !a->strand || !ul->offsets || !ul->circular)) return MDBG_E_PARAM;
+    FILE* f = fopen(path, truncate ? "wb" : "ab");
+    if (!f) return MDBG_E_IO;
+    bool ok = true, bad = false;
+    try {
+        std::string b;
+        char num[160];
+        for (u64 q = 0; q < a->n_reads && ok && !bad; ++q) {
+            for (u64 i = a->aln_offsets[q]; i < a->aln_offsets[q + 1] && ok && !bad; ++i) {
+                const u64 qb = a->query_begin[i], qe = a->query_end[i], pb = a->path_begin[i], pe = a->path_end[i];
+                snprintf(num, sizeof num, "%llu\t%llu\t%llu\t%llu\t+\t", (unsigned long long)a->ordinal[q], (unsigned long long)read_lengths[q], (unsigned long long)qb, (unsigned long long)qe);
+                b += num;
+                const u64 p0 = a->aln_step_offsets[i], p1 = a->aln_step_offsets[i + 1];
+                for (u64 p = p0; p < p1; ++p) {
+                    const u64 u = a->unitig[p];
+                    if (u >= ul->n_unitigs) { bad = true; break; }
+                    const u64 m = ul->offsets[u + 1] - ul->offsets[u], j = a->first_entry[p], n = a->step_windows[p];
+                    const bool circ = ul->circular[u] != 0, rev = a->strand[p] != 0;
+                    if (m == 0 || j >= m || n == 0) { bad = true; break; }
+                    const u64 wraps = circ ? ((rev ? m - 1 - j : j) + n - 1) / m : 0;      // the ring closures inside the step
+                    const std::string name = unitig_name(u, circ);
+                    for (u64 w = 0; w <= wraps; ++w) { b += rev ? '<' : '>'; b += name; }
+                }
+                const u64 ql = qe - qb, pl = pe - pb;
+                snprintf(num, sizeof num, "\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tnw:i:%u\tns:i:%llu\n", (unsigned long long)a->path_length[i], (unsigned long long)pb, (unsigned long long)pe,
+                         (unsigned long long)std::min(ql, pl), (unsigned long long)std::max(ql, pl), a->aln_windows[i], (unsigned long long)(p1 - p0));
+                b += num;
+                if (b.size() >= (4u << 20)) { ok = write_all(f, b); b.clear(); }
+            }
+        }
+        ok = ok && write_all(f, b);
+    } catch (const std::bad_alloc&) { fclose(f); return MDBG_E_NOMEM; }
+    if (fclose(f) != 0) ok = false;
+    return bad ? MDBG_E_PARAM : ok ? MDBG_OK : MDBG_E_IO;
+}
 
 }  // extern "C"

@@ -35,7 +35,7 @@ constexpr uint32_t JX_DEFECT_EDGE = 8;            // beside RP_DEFECT_*: an edge
 // the reads [first_read, first_read + n_reads) of the store and the minimizer indices [i0, i1) they cover
 struct ReadPathRange {
     const uint64_t* roff; const uint32_t* mread; uint32_t first_read, n_reads, k; uint64_t i0, i1;
-    const uint32_t* by_slot0; const uint64_t* by_slot_first; uint32_t n_batches;      // the batches in slot order: first slot, first ordinal
+    const uint32_t* by_slot0; const uint64_t* by_slot_first; uint32_t n_batches;      // the batches in slot order: first slot, first ordinal; n_batches == 0: a range that is in no batch table (a temporary batch), ordinal = the read's number in the range
 };
 // what place_windows_kernel reads and writes beside the table and the store
 struct ReadPathPlan {

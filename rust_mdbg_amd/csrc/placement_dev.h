@@ -39,6 +39,19 @@ __device__ inline bool is_link_of_codes(u32 pc, u32 c, const u32* unitig_of_entr
     const u32 e = c & ~RP_STRAND, pe = pc & ~RP_STRAND;
     return !((pc ^ c) & RP_STRAND) && unitig_of_entry[e] == unitig_of_entry[pe] && (c & RP_STRAND ? pe == e + 1 : e == pe + 1);
 }
+// What the pair code[t - 1] -> code[t] is, for every stage that asks (junctions.hip, transits.hip, alignments.hip): PAIR_NONE no adjacent pair (adjacent_in_read),
+// PAIR_LINK a link, PAIR_EXPLAINED a crossing whose key is some record's key, PAIR_MISSING a crossing on no record.  A crossing leaves its key in *key and, explained,
+// in *at the first position of the key's run in rkey_sorted[0, R): the key's counter slot, and rec_sorted[*at] its smallest record.
+enum PairKind : u32 { PAIR_NONE = 0, PAIR_LINK, PAIR_EXPLAINED, PAIR_MISSING };
+__device__ inline PairKind classify_pair(const u32* code, const u64* roff, const u32* mread, u64 i0, u64 t, u32 c, const u32* unitig_of_entry, const u64* rkey_sorted, u64 R,
+                                         u64* key, u64* at) {
+    u32 pc;
+    if (!adjacent_in_read(code, roff, mread, i0, t, c, &pc)) return PAIR_NONE;
+    if (is_link_of_codes(pc, c, unitig_of_entry)) return PAIR_LINK;
+    *key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
+    *at = lower_bound(rkey_sorted, R, *key);
+    return *at < R && rkey_sorted[*at] == *key ? PAIR_EXPLAINED : PAIR_MISSING;
+}
 __device__ inline void set_defect(u64* counters, u32 what) { atomicOr((unsigned long long*)(counters + RP_C_DEFECT), (unsigned long long)what); }
 // the workgroup's counts (256 threads, NC of them per thread): one atomic each on counters[first .. first + NC).  cnt[] is reduced IN PLACE: on return the first
 // lane of every wave holds its wave's sums (the other lanes partial ones).  resolve_kernel (placement.hip) relies on that for a second counter; keep it

@@ -16,5 +16,14 @@ struct ReadPathResult {            // device pointers into ReadPathBuffers, vali
 };
 // One call: grows every buffer, queues the zeroing, the placement (placement_queue, which calls the placer) and the rest (head flags, one scan, the steps, the
 // sums), reads the counters back and waits ONCE.  Every launch count is fixed.
+// The three parts of that call, for a stage that goes on from the steps on the device (alignments.hip): read_paths_reserve grows every buffer (the placement's
+// included, with or without records); read_paths_queue queues the zeroing, the placement and the read-path kernels and fills *out's pointers and n_reads / n_unitigs,
+// *view and the scratch the steps were numbered with (flag[t] = 1 iff index t starts a step, pos = its exclusive scan), and waits for nothing; read_paths_counts
+// fills the counts and the defect mask from the counter block once the caller has read it back.  The caller owns the timer and the one wait.
+struct ReadPathScratch { const uint8_t* flag; const uint32_t* pos; };
+hipError_t read_paths_reserve(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, uint64_t n_rows, const ReadPathRange& rg, bool with_records);
+hipError_t read_paths_queue(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, const ReadPathRange& rg, bool with_records,
+                            uint32_t n_counters, const WindowPlacer& placer, hipStream_t s, PlacementView* view, ReadPathResult* out, ReadPathScratch* scratch);
+void read_paths_counts(const uint64_t* counters, ReadPathResult* out);
 hipError_t read_paths_run(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
                           hipStream_t s, ReadPathResult* out);

@@ -98,6 +98,7 @@ __global__ __launch_bounds__(256) void reads_kernel(RpArgs a) {
     if (q == a.nr) return;
     const u64 n_min = a.roff[a.r0 + q + 1] - a.roff[a.r0 + q];
     a.read_windows[q] = n_min > a.k ? (u32)(n_min - a.k + 1) : 0u;      // src/main.rs:756-759
+    if (a.n_batches == 0) { a.ordinal[q] = q; return; }   // a range without a batch table (a temporary batch, mdbg_graph_align_batch): the read's number in the range
     const u32 slot = a.r0 + (u32)q;
     u32 lo = 0, hi = a.n_batches - 1;                      // as rep_ordinal (finalize.hip): the last batch whose first slot is <= slot
     while (lo < hi) { const u32 mid = lo + ((hi - lo + 1) >> 1); if (a.by_slot0[mid] <= slot) lo = mid; else hi = mid - 1; }
@@ -120,22 +121,24 @@ RpArgs args_of(ReadPathBuffers* B, const PlacementView& V, const UnitigResult& u
 ReadPathBuffers* read_path_buffers_create() { return new ReadPathBuffers(); }
 void read_path_buffers_destroy(ReadPathBuffers* b) { delete b; }
 
-hipError_t read_paths_run(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
-                          hipStream_t s, ReadPathResult* out) {
-    memset(out, 0, sizeof *out);
+hipError_t read_paths_reserve(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, u64 n_rows, const ReadPathRange& rg, bool with_records) {
     const u64 U = ul.n_unitigs, n_idx = rg.i1 - rg.i0, nr = rg.n_reads;
-    // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
-    GHIP(placement_reserve(P, ul, n_rows, rg, false));
+    GHIP(placement_reserve(P, ul, n_rows, rg, with_records));
     GHIP(B->flag.ensure(n_idx + 4)); GHIP(B->pos.ensure(n_idx * 4 + 4));
     GHIP(B->ordinal.ensure(nr * 8 + 8)); GHIP(B->read_windows.ensure(nr * 4 + 4)); GHIP(B->step_offsets.ensure((nr + 1) * 8));
     GHIP(B->first_window.ensure(n_idx * 4 + 4)); GHIP(B->step_windows.ensure(n_idx * 4 + 4)); GHIP(B->unitig.ensure(n_idx * 4 + 4)); GHIP(B->first_entry.ensure(n_idx * 4 + 4));
     GHIP(B->strand.ensure(n_idx + 4)); GHIP(B->sup_w.ensure(U * 8)); GHIP(B->sup_s.ensure(U * 8));
-    if (n_idx) { size_t tb = 0; GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), s)); GHIP(B->tmp.ensure(tb + 256)); }
-    GHIP(B->timer.start(s));
+    if (n_idx) { size_t tb = 0; GHIP(rocprim::exclusive_scan(nullptr, tb, B->flag.as<u8>(), B->pos.as<u32>(), 0u, (size_t)n_idx, rocprim::plus<u32>(), hipStream_t(nullptr))); GHIP(B->tmp.ensure(tb + 256)); }
+    return hipSuccess;
+}
+
+hipError_t read_paths_queue(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, bool with_records, u32 n_counters,
+                            const WindowPlacer& placer, hipStream_t s, PlacementView* V, ReadPathResult* out, ReadPathScratch* scratch) {
+    memset(out, 0, sizeof *out);
+    const u64 U = ul.n_unitigs;
     GHIP(hipMemsetAsync(B->sup_w.p, 0, U * 8, s)); GHIP(hipMemsetAsync(B->sup_s.p, 0, U * 8, s));
-    PlacementView V;
-    GHIP(placement_queue(P, ul, index, n_rows, rg, false, RP_C_N, placer, s, &V));
-    const RpArgs a = args_of(B, V, ul, rg);
+    GHIP(placement_queue(P, ul, index, n_rows, rg, with_records, n_counters, placer, s, V));
+    const RpArgs a = args_of(B, *V, ul, rg);
     if (a.n_idx) {
         const unsigned gi = grid_for(a.n_idx);
         hipLaunchKernelGGL(head_kernel, dim3(gi), dim3(256), 0, s, a);
@@ -145,12 +148,31 @@ hipError_t read_paths_run(ReadPathBuffers* B, PlacementBuffers* P, const UnitigR
     }
     hipLaunchKernelGGL(reads_kernel, dim3(grid_for((u64)a.nr + 1)), dim3(256), 0, s, a);
     GHIP(hipGetLastError());
-    u64 h[RP_C_N];
-    GHIP(B->timer.stop_and_read(h, a.counters, sizeof h, s, &out->ms));
-    out->defect = (u32)h[RP_C_DEFECT];
-    if (out->defect) return hipSuccess;
-    out->n_reads = a.nr; out->n_windows = h[RP_C_WINDOWS]; out->n_placed = h[RP_C_PLACED]; out->n_steps = h[RP_C_STEPS]; out->n_unitigs = a.U;
+    out->n_reads = a.nr; out->n_unitigs = a.U;
     out->ordinal = a.ordinal; out->read_windows = a.read_windows; out->step_offsets = a.step_offsets; out->first_window = a.first_window; out->step_windows = a.step_windows; out->unitig = a.unitig;
     out->first_entry = a.first_entry; out->strand = a.strand; out->support_windows = a.sup_w; out->support_steps = a.sup_s;
+    if (scratch) { scratch->flag = a.flag; scratch->pos = a.pos; }
+    return hipSuccess;
+}
+
+void read_paths_counts(const u64* h, ReadPathResult* out) {
+    out->defect = (u32)h[RP_C_DEFECT];
+    out->n_windows = h[RP_C_WINDOWS]; out->n_placed = h[RP_C_PLACED]; out->n_steps = h[RP_C_STEPS];
+}
+
+hipError_t read_paths_run(ReadPathBuffers* B, PlacementBuffers* P, const UnitigResult& ul, const u32* index, u64 n_rows, const ReadPathRange& rg, const WindowPlacer& placer,
+                          hipStream_t s, ReadPathResult* out) {
+    memset(out, 0, sizeof *out);
+    // every buffer first: growing one may wait for the device (graph_common.h), and nothing of this call is queued yet
+    GHIP(read_paths_reserve(B, P, ul, n_rows, rg, false));
+    GHIP(B->timer.start(s));
+    PlacementView V;
+    GHIP(read_paths_queue(B, P, ul, index, n_rows, rg, false, RP_C_N, placer, s, &V, out, nullptr));
+    u64 h[RP_C_N];
+    float ms = 0;
+    GHIP(B->timer.stop_and_read(h, V.counters, sizeof h, s, &ms));
+    read_paths_counts(h, out);
+    out->ms = ms;
+    if (out->defect) { const u32 d = out->defect; memset(out, 0, sizeof *out); out->defect = d; out->ms = ms; }
     return hipSuccess;
 }

@@ -1,5 +1,5 @@
 // results.inc — what a context derives from its table and keeps for the caller (the host copy of the node table, the edge list, the unitig list, components, contigs,
-// node sequences, read paths, junction support, transits) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
+// node sequences, read paths, junction support, transits, alignments) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
 namespace {
 // the buffers of one graph stage: created on first use, destroyed with the context
 template <class B, B* (*Create)(), void (*Destroy)(B*)> struct StageBuffers {
@@ -36,7 +36,10 @@ struct Results {
     struct { StageBuffers<TransitBuffers, transit_buffers_create, transit_buffers_destroy> buf;                          // its result lives until the next transit call or simplify call with a REPEATS step
              HostRaw<u64> count, passes; HostRaw<u32> unitig, iu, ie, ou, oe, irec, orec, n_in, n_out; HostRaw<u8> is, os, verdict; double ms = 0; } transits;
 
-    // ---- what is current.  ONLY the functions from here to prefix_is_summed write these members; everybody else asks the predicates below.
+    struct { StageBuffers<AlignmentBuffers, alignment_buffers_create, alignment_buffers_destroy> buf;                    // its result lives until the next alignment call; the steps it names are the read-path result's
+             HostRaw<u64> aoff, asoff, plen, pbeg, pend; HostRaw<u32> srec, awin, qbeg, qend; double ms = 0; } alns;
+
+    // ---- what is current.  ONLY the functions from here to still_holds write these members; everybody else asks the predicates below.
     struct { NodeTable table = NodeTable::NONE; u64 rows = 0;
              bool edges = false;         // edges.last belongs to the node table as it stands (unitigs.hip reads both)
              bool ulist = false;         // unitigs.last is current: no edge, finalize, ingest, rewind or reset call since
@@ -56,6 +59,10 @@ struct Results {
     void edge_list_is(const EdgeResult& r, bool current) { edges.last = r; cur.edges = current; }
     void unitig_list_is(const UnitigResult& r, u64 copies = 0) { unitigs.last = r; cur.ulist = true; cur.copies = copies; }
     void prefix_is_summed() { cur.prefix = true; }
+    // A temporary batch (mdbg_graph_align_batch) is sketched behind the store, which ends the unitig list as every sketch does, and rolled back: the store is
+    // what the list was built on again, and the list is current as it was.  held() before the sketch, still_holds() behind the rollback.
+    auto held() const { return cur; }
+    void still_holds(const decltype(cur)& before) { cur = before; }
 
     // The readers ask two DIFFERENT questions about the node table, and the answers differ on a context that holds nothing and was never finalized:
     //   table_or_empty_context  "a table with rows is current, or there is nothing to tabulate": the edge list and the read paths, which answer an empty context with

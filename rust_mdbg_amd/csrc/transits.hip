@@ -62,16 +62,11 @@ __global__ __launch_bounds__(256) void event_kernel(TxArgs a) {
     if (t < a.n_idx) {
         u8 kind = K_BREAK;
         const u32 c = a.code[t];
-        u32 pc;
-        if (adjacent_in_read(a.code, a.roff, a.mread, a.i0, t, c, &pc)) {
-            cnt[0] = 1;
-            if (is_link_of_codes(pc, c, a.unitig_of_entry)) { cnt[1] = 1; kind = K_LINK; }
-            else {
-                const u64 key = key_of_pair(vertex_of_code(pc), vertex_of_code(c));
-                const u64 p = lower_bound(a.rkey_sorted, a.R, key);
-                if (p < a.R && a.rkey_sorted[p] == key) { cnt[2] = 1; kind = K_CROSS; }
-            }
-        }
+        u64 key = 0, p = 0;
+        const PairKind pair = classify_pair(a.code, a.roff, a.mread, a.i0, t, c, a.unitig_of_entry, a.rkey_sorted, a.R, &key, &p);
+        if (pair != PAIR_NONE) cnt[0] = 1;
+        if (pair == PAIR_LINK) { cnt[1] = 1; kind = K_LINK; }
+        else if (pair == PAIR_EXPLAINED) { cnt[2] = 1; kind = K_CROSS; }
         a.kind[t] = kind;
         a.ev[t] = kind == K_LINK ? 0u : (u32)t + 1u;
     }

@@ -55,6 +55,8 @@ def load_library():
         L.mdbg_emit_contigs_get.argtypes = [vp, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
         L.mdbg_emit_contigs_close.argtypes = [vp]
         L.mdbg_emit_contigs_close.restype = None
+        from . import align
+        align.declare_emit(L)                              # the GAF writer (include/mdbg_align.h)
         _LIB = L
     return _LIB
 

@@ -7,7 +7,10 @@ import queue
 import threading
 import time
 
+import numpy as np
+
 from .api import MAGIC_SIMPLIFY_STEPS, MDBG_SIMPLIFY_NESTED, MDBG_SIMPLIFY_REPEATS, Mdbg, edge_columns, junction_text, merge_junctions, merge_transits, read_path_text, transit_self_flags, transit_text, unitig_name
+from .align import gaf_append
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions / graph_transits call of run_file
@@ -24,7 +27,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
              threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False, transits=0,
-             prefilter=False, prefilter_cells=0):
+             prefilter=False, prefilter_cells=0, gaf=False, query=None):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -49,6 +52,13 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     end, with its count, then one U line per unitig with two or more entrances and exits saying whether the pairs seen N times or more match them one to one
     (Mdbg.graph_transits; api.transit_text gives the format), and with simplify <prefix>.msimpl.transits.tsv for the simplified list.  Adds n_transits, n_passes,
     n_repeats and n_resolved (and their _simplified twins).  The other files are unchanged.
+    gaf (with contigs): also write <prefix>.unitigs.gaf: the reads aligned to the unitig list, one GAF line per alignment (Mdbg.graph_alignments, written by
+    libmdbg_emit's mdbg_gaf_append: include/mdbg_align.h gives the columns; qname is the read's ordinal, the reader hands out no names), in the bounded read ranges
+    of the read-path writer, and with simplify <prefix>.msimpl.gaf for the simplified list.  Adds n_alignments (and n_alignments_simplified).
+    query=PATH (with contigs): sequences that are NOT part of the graph (genes, a reference, contigs), read from PATH with the project's reader in batches and
+    aligned to the unitig list without changing it (Mdbg.align_batch): <prefix>.unitigs.query.gaf, and <prefix>.unitigs.query.tsv with one line
+    `ordinal<TAB>windows<TAB>placed<TAB>%.2f` per query — its k-min-mers, how many of them lie on the list, and that share in percent (the columns of the
+    reference's experiments/amr/parse_hits.py); with simplify the .msimpl. pair.  Adds n_queries, n_query_alignments (and n_query_alignments_simplified).
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -121,6 +131,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     th = threading.Thread(target=produce, daemon=True)
     th.start()
     n_reads = n_bases = 0
+    read_lens = []                         # gaf: the raw length of every read, from the batch offsets
     tm = {}
     t0 = time.perf_counter()
     try:
@@ -143,6 +154,8 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 else:
                     m.ingest(payload, offs, n_reads)    # ctypes releases the GIL: the reader thread parses the next batch meanwhile
                     free.release()
+                if gaf:
+                    read_lens.append(np.diff(np.asarray(payload["offsets"] if packed else offs).astype(np.uint64)))
                 n_reads += (len(payload["offsets"]) if packed else len(offs)) - 1
                 n_bases += nb
             tm["ingest"] = time.perf_counter() - t0
@@ -208,6 +221,33 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 with open(path_, "w") as f:
                     f.write(transit_text(tr, ul.circular))
                 comp.update({f + suffix: tr[f] for f in ("n_transits", "n_passes", "n_repeats", "n_resolved")})
+            def write_gaf(ul, path_, key):               # the same ranges; the writer appends range after range
+                lens = np.concatenate(read_lens) if read_lens else np.zeros(0, np.uint64)
+                open(path_, "w").close()
+                comp[key] = 0
+                first = 0
+                while True:
+                    al = m.graph_alignments(first, READ_PATH_CHUNK)
+                    if not al["n_reads"]:
+                        break
+                    gaf_append(path_, al, ul, lens[first:first + al["n_reads"]])
+                    comp[key] += al["n_alignments"]
+                    first += al["n_reads"]
+            def write_query(ul, stem, suffix):           # the query file in the reader's batches: each aligned behind the store and forgotten again
+                open(stem + ".query.gaf", "w").close()
+                first = n_aln = 0
+                with Reader(query, strip_newlines) as qr, open(stem + ".query.tsv", "w") as f:
+                    for qb, qo in qr.batches(batch_bases):
+                        al = m.align_batch(qb, qo)
+                        al["ordinal"] = al["ordinal"] + np.uint64(first)
+                        gaf_append(stem + ".query.gaf", al, ul, np.diff(qo.astype(np.uint64)))
+                        so = al["step_offsets"].astype(np.int64)
+                        placed = np.add.reduceat(np.append(al["step_windows"].astype(np.int64), 0), so[:-1]) * (np.diff(so) > 0) if al["n_reads"] else np.zeros(0, np.int64)
+                        f.write("".join("%d\t%d\t%d\t%.2f\n" % (o, w, p, 100.0 * p / w if w else 0.0) for o, w, p in zip(al["ordinal"].tolist(), al["read_windows"].tolist(), placed.tolist())))
+                        first += al["n_reads"]
+                        n_aln += al["n_alignments"]
+                comp["n_queries"] = first
+                comp["n_query_alignments" + suffix] = n_aln
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
@@ -222,6 +262,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_junctions(sl, prefix + ".msimpl.junctions.tsv", "_simplified")
                 if transits and placeable:
                     write_transits(sl, prefix + ".msimpl.transits.tsv", "_simplified")
+                if gaf and placeable:
+                    write_gaf(sl, prefix + ".msimpl.gaf", "n_alignments_simplified")
+                if query is not None and placeable:
+                    write_query(sl, prefix + ".msimpl", "_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
@@ -237,6 +281,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_junctions(ul, prefix + ".unitigs.junctions.tsv", "")
                 if transits:
                     write_transits(ul, prefix + ".unitigs.transits.tsv", "")
+                if gaf:
+                    write_gaf(ul, prefix + ".unitigs.gaf", "n_alignments")
+                if query is not None:
+                    write_query(ul, prefix + ".unitigs", "")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
