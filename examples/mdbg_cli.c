@@ -20,6 +20,10 @@
  *   --query FILE (implies --contigs): the sequences of FILE, which are no part of the graph, aligned to the unitig list without changing it
  *   (mdbg_graph_align_batch): <prefix>.unitigs.query.gaf and <prefix>.unitigs.query.tsv (ordinal, k-min-mers, those found on the list, their share in percent;
  *   and the .msimpl. pair) and one summary line each
+ *   --chains S[,G] (implies --contigs): the alignments of a read joined across unplaced windows where the graph bridges them, at max_skew S and max_gap G (0 or
+ *   absent: no limit) (mdbg_graph_chains of mdbg_chain.h): <prefix>.unitigs.chains.gaf, one line per chain through mdbg_gaf_append_chains (and
+ *   <prefix>.msimpl.chains.gaf); with --query also <prefix>.unitigs.query.chains.gaf and .query.chains.tsv (ordinal, k-min-mers, placed, bridged, the share of
+ *   placed + bridged in percent); one summary line each
  *   --keep-reads (with --contigs / --simplify): the context keeps the reads packed on the device (MDBG_FLAG_KEEP_READS) and mdbg_graph_contigs stitches the
  *   sequences there; the same files, and with --no-basespace the input is read once
  *   --sequences-from-kept: the context keeps the reads and the .sequences files are written from that store (mdbg_graph_node_seqs in chunks ->
@@ -38,6 +42,7 @@
 #include <time.h>
 
 #include "mdbg_align.h"
+#include "mdbg_chain.h"
 #include "mdbg_emit.h"
 #include "mdbg_hip.h"
 
@@ -168,6 +173,66 @@ static void write_query(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* s
     printf("query%s: %llu sequences, %llu with a k-min-mer on the list, %llu alignments\n", what, (unsigned long long)first, (unsigned long long)n_found, (unsigned long long)n_aln);
 }
 
+/* ---- --chains: the same two writers over mdbg_graph_chains / mdbg_graph_chain_batch (mdbg_chain.h) ---- */
+static void write_chains(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* path, const uint64_t* lens, uint32_t skew, uint32_t gap, const char* what) {
+    uint64_t first = 0, n_chains = 0, n_inside = 0, n_record = 0, n_gapw = 0;
+    FILE* f = fopen(path, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    fclose(f);
+    for (;;) {
+        mdbg_chain_list ch;
+        int rc = mdbg_graph_chains(ctx, first, (uint64_t)1 << 20, skew, gap, &ch);
+        if (rc) die(ctx, "mdbg_graph_chains", rc);
+        if (!ch.alignments.n_reads) break;
+        rc = mdbg_gaf_append_chains(path, 0, &ch, ul, lens + first);
+        if (rc) die(NULL, "mdbg_gaf_append_chains", rc);
+        n_chains += ch.n_chains; n_inside += ch.n_bridges_inside; n_record += ch.n_bridges_record; n_gapw += ch.n_gap_windows; first += ch.alignments.n_reads;
+    }
+    printf("chains%s: %llu reads, %llu chains, %llu bridges inside a unitig, %llu over a record, %llu windows in bridged gaps\n", what, (unsigned long long)first,
+           (unsigned long long)n_chains, (unsigned long long)n_inside, (unsigned long long)n_record, (unsigned long long)n_gapw);
+}
+static void write_query_chains(mdbg_ctx* ctx, const mdbg_unitig_list* ul, const char* stem, const char* file, int reference, uint32_t skew, uint32_t gap, const char* what) {
+    char gaf[4096], tsv[4096];
+    int err = 0;
+    uint64_t first = 0, n_chains = 0, n_bridges = 0;
+    snprintf(gaf, sizeof gaf, "%s.query.chains.gaf", stem); snprintf(tsv, sizeof tsv, "%s.query.chains.tsv", stem);
+    FILE* f = fopen(gaf, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    fclose(f);
+    f = fopen(tsv, "wb");
+    if (!f) die(NULL, "fopen", MDBG_E_IO);
+    mdbg_reader* rd = mdbg_reader_open(file, reference, &err);
+    if (!rd) die(NULL, "mdbg_reader_open", err);
+    for (;;) {
+        const uint8_t* bases; const uint64_t* offs; uint64_t n;
+        int rc = mdbg_reader_next(rd, 256u << 20, &bases, &offs, &n);
+        if (rc) die(NULL, "mdbg_reader_next", rc);
+        if (!n) break;
+        mdbg_chain_list ch;
+        rc = mdbg_graph_chain_batch(ctx, bases, offs, n, skew, gap, &ch);
+        if (rc) die(ctx, "mdbg_graph_chain_batch", rc);
+        uint64_t* lens = (uint64_t*)malloc(2 * n * sizeof *lens);    /* the lengths, and the ordinals in the FILE: the call numbers a batch from 0 */
+        if (!lens) die(NULL, "malloc", MDBG_E_NOMEM);
+        uint64_t* ord = lens + n;
+        for (uint64_t q = 0; q < n; ++q) { lens[q] = offs[q + 1] - offs[q]; ord[q] = first + q; }
+        ch.alignments.ordinal = ord;
+        rc = mdbg_gaf_append_chains(gaf, 0, &ch, ul, lens);
+        if (rc) die(NULL, "mdbg_gaf_append_chains", rc);
+        for (uint64_t q = 0; q < ch.alignments.n_reads; ++q) {
+            uint64_t placed = 0, bridged = 0;
+            for (uint64_t c = ch.chain_offsets[q]; c < ch.chain_offsets[q + 1]; ++c) { placed += ch.chain_windows[c]; bridged += ch.chain_gap_windows[c]; }
+            const uint32_t w = ch.alignments.read_windows[q];
+            fprintf(f, "%llu\t%u\t%llu\t%llu\t%.2f\n", (unsigned long long)ord[q], w, (unsigned long long)placed, (unsigned long long)bridged,
+                    w ? 100.0 * (double)(placed + bridged) / (double)w : 0.0);
+        }
+        free(lens);
+        n_chains += ch.n_chains; n_bridges += ch.n_bridges; first += n;
+    }
+    mdbg_reader_close(rd);
+    if (fclose(f) != 0) die(NULL, "fclose", MDBG_E_IO);
+    printf("query chains%s: %llu sequences, %llu chains, %llu bridges\n", what, (unsigned long long)first, (unsigned long long)n_chains, (unsigned long long)n_bridges);
+}
+
 /* ---- --transits: the rows of the ranges merged by key, the verdict rule of mdbg_graph_transits on the merged counts, the .transits.tsv ---- */
 typedef struct trow_t { uint32_t u, pu, pj, ps, qu, qj, qs; uint64_t count; } trow_t;
 static int trow_cmp(const void* a, const void* b) {
@@ -238,7 +303,7 @@ int main(int argc, char** argv) {
     mdbg_params p; memset(&p, 0, sizeof p);
     p.k = 10; p.l = 12; p.density = 0.1; p.min_abundance = 2; p.device = -1;       /* the reference's defaults (main.rs:430-450) */
     float presimp = 0.01f;
-    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0, gaf = 0; uint64_t transits = 0; const char* query = NULL;
+    const char* input = NULL; const char* prefix = "graph"; int write_sequences = 1, threads = 1, reference = 0, timing = 0, contigs = 0, keep_reads = 0, seq_kept = 0, components = 0, read_paths = 0, junctions = 0, gaf = 0, chains = 0; uint64_t transits = 0; const char* query = NULL; unsigned chain_skew = 0, chain_gap = 0;
     const char* lmer_counts = NULL; uint32_t lc_min = 2, lc_max = 100000;          /* main.rs:447-448 */
     int syncmer_s_given = 0;
     /* the first `gfatools asm` line of utils/magic_simplify as steps (--simplify); -t N,L / -b L / -c N,L / -e N / -r N / -R N / -B N,L append steps of their own, in command-line order */
@@ -321,6 +386,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--junctions")) junctions = 1;
         else if (!strcmp(argv[i], "--transits") && i + 1 < argc) { transits = strtoull(argv[++i], NULL, 10); if (!transits) { fprintf(stderr, "--transits takes a min_support >= 1\n"); return 2; } }
         else if (!strcmp(argv[i], "--gaf")) gaf = 1;
+        else if (!strcmp(argv[i], "--chains") && i + 1 < argc) { chains = 1; chain_gap = 0; if (sscanf(argv[++i], "%u,%u", &chain_skew, &chain_gap) < 1) { fprintf(stderr, "--chains S[,G]\n"); return 2; } }
         else if (!strcmp(argv[i], "--query") && i + 1 < argc) query = argv[++i];
         else if (!strcmp(argv[i], "--bf")) p.flags |= MDBG_FLAG_PREFILTER;                      /* main.rs --bf, order-free: the counting pre-filter in front of the node table */
         else if (!strcmp(argv[i], "--bf-cells") && i + 1 < argc) p.prefilter_cells = strtoull(argv[++i], NULL, 10);   /* its number of 2-bit cells (default 2^32) */
@@ -330,9 +396,9 @@ int main(int argc, char** argv) {
         else if (argv[i][0] != '-') input = argv[i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--bf [--bf-cells N]] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--gaf] [--query FILE] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
+    if (!input) { fprintf(stderr, "usage: mdbg_cli reads.fa[.gz] [-k K] [-l L] [--density D] [--minabund A] [--presimp P] [--prefix PFX] [--no-basespace] [--threads N] [--reference] [--skiphpc] [--bf [--bf-cells N]] [--syncmers [-s S]] [--lmer-counts FILE [--lmer_counts_min A] [--lmer_counts_max B]] [--contigs] [--simplify] [-t N,L] [-b L] [-c N,L] [-e N] [-r N] [-R N] [-B N,L] [--components] [--read-paths] [--junctions] [--transits N] [--gaf] [--chains S[,G]] [--query FILE] [--keep-reads] [--sequences-from-kept] [--timing]\n"); return 2; }
     if (threads < 1) threads = 1;
-    if (simplify || components || read_paths || junctions || transits || gaf || query) contigs = 1;
+    if (simplify || components || read_paths || junctions || transits || gaf || chains || query) contigs = 1;
     if (!contigs) keep_reads = 0;
     if (!write_sequences) seq_kept = 0;
     if (keep_reads || seq_kept) p.flags |= MDBG_FLAG_KEEP_READS;      /* (--sequences-from-kept keeps the reads by itself; the contigs come from the store only with --keep-reads) */
@@ -373,7 +439,7 @@ int main(int argc, char** argv) {
             rc = mdbg_ingest_batch_packed(ctx, &pb, first);
             if (rc) die(ctx, "mdbg_ingest_batch_packed", rc);
             t_gpu += now_s() - ta;
-            if (gaf) read_lens = note_lengths(read_lens, &lens_cap, first, pb.offsets, pb.n_reads);
+            if (gaf || chains) read_lens = note_lengths(read_lens, &lens_cap, first, pb.offsets, pb.n_reads);
             first += pb.n_reads; n_reads += pb.n_reads; n_bases += pb.offsets[pb.n_reads];
         }
         pthread_join(th, NULL);
@@ -384,7 +450,7 @@ int main(int argc, char** argv) {
         if (!n) break;
         rc = mdbg_ingest_batch(ctx, bases, offs, n, first);          /* process_read_aux over the batch */
         if (rc) die(ctx, "mdbg_ingest_batch", rc);
-        if (gaf) read_lens = note_lengths(read_lens, &lens_cap, first, offs, n);
+        if (gaf || chains) read_lens = note_lengths(read_lens, &lens_cap, first, offs, n);
         first += n; n_reads += n; n_bases += offs[n];
     }
     mdbg_reader_close(rd);
@@ -461,6 +527,10 @@ int main(int argc, char** argv) {
         if (transits && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl.transits.tsv", prefix); write_transits(ctx, &sl, path, transits, " (simplified)"); }
         if (gaf && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl.gaf", prefix); write_gaf(ctx, &sl, path, read_lens, " (simplified)"); }
         if (query && !repeat_steps) { snprintf(path, sizeof path, "%s.msimpl", prefix); write_query(ctx, &sl, path, query, reference, " (simplified)"); }
+        if (chains && !repeat_steps) {
+            snprintf(path, sizeof path, "%s.msimpl.chains.gaf", prefix); write_chains(ctx, &sl, path, read_lens, chain_skew, chain_gap, " (simplified)");
+            if (query) { snprintf(path, sizeof path, "%s.msimpl", prefix); write_query_chains(ctx, &sl, path, query, reference, chain_skew, chain_gap, " (simplified)"); }
+        }
         sctg = mdbg_emit_contigs_open(&sl, NULL, &err);             /* (no node table: the list covers the surviving nodes only) */
         if (!sctg) die(NULL, "mdbg_emit_contigs_open", err);
         if (keep_reads) {                                           /* the sequences from the device store instead of the second pass */
@@ -526,6 +596,10 @@ int main(int argc, char** argv) {
         if (transits) { snprintf(path, sizeof path, "%s.unitigs.transits.tsv", prefix); write_transits(ctx, &ul, path, transits, ""); }
         if (gaf) { snprintf(path, sizeof path, "%s.unitigs.gaf", prefix); write_gaf(ctx, &ul, path, read_lens, ""); }
         if (query) { snprintf(path, sizeof path, "%s.unitigs", prefix); write_query(ctx, &ul, path, query, reference, ""); }
+        if (chains) {
+            snprintf(path, sizeof path, "%s.unitigs.chains.gaf", prefix); write_chains(ctx, &ul, path, read_lens, chain_skew, chain_gap, "");
+            if (query) { snprintf(path, sizeof path, "%s.unitigs", prefix); write_query_chains(ctx, &ul, path, query, reference, chain_skew, chain_gap, ""); }
+        }
         if (keep_reads) {
             mdbg_contig_seqs cs;
             rc = mdbg_graph_contigs(ctx, 0, &cs);

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import align as _align
+from . import chains as _chains
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -462,6 +463,7 @@ def load_library():
               "mdbg_ingest_batch_packed_device", "mdbg_sketch_packed_device", "mdbg_pack_device"):
         getattr(L, f).restype = C.c_int
     _align.declare_hip(L)                                  # include/mdbg_align.h
+    _chains.declare_hip(L)                                 # include/mdbg_chain.h
     _LIB = L
     return L
 
@@ -916,6 +918,36 @@ class Mdbg:
         al = _align.AlignmentList()
         self._chk(self.L.mdbg_graph_align_batch(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(al)))
         return _align.alignment_dict(al)
+
+    def graph_chains(self, first_read=0, max_reads=0, max_skew=0, max_gap=0):
+        """graph_alignments over the same range, and consecutive alignments of a read joined where the graph bridges the unplaced windows between them: inside one
+        unitig or over one edge record, with the entries of the bridge at most max_skew away from the windows of the gap and the gap at most max_gap windows
+        (0: no limit) (mdbg_graph_chains, include/mdbg_chain.h).  -> dict(n_bridges, n_bridges_inside, n_bridges_record, n_chains, n_gap_windows; per alignment
+        bridge_record, bridge_entries; chain_offsets[n_reads + 1], chain_aln_offsets[n_chains + 1]; per chain chain_windows, chain_gap_windows, query_begin,
+        query_end, path_length, path_begin, path_end; alignments = the dict of graph_alignments)"""
+        ch = _chains.ChainList()
+        self._chk(self.L.mdbg_graph_chains(self.h, first_read, max_reads, max_skew, max_gap, C.byref(ch)))
+        return _chains.chain_dict(ch)
+
+    def graph_chains_device(self, first_read=0, max_reads=0, max_skew=0, max_gap=0):
+        """-> ChainList with DEVICE pointers (valid until the next chain call; its alignment columns until the next alignment call)"""
+        ch = _chains.ChainList()
+        self._chk(self.L.mdbg_graph_chains_device(self.h, first_read, max_reads, max_skew, max_gap, C.byref(ch)))
+        return ch
+
+    def chains_ms(self):
+        """device time of the last graph_chains* / chain_batch call, the alignment stage inside it included, in milliseconds"""
+        ms = C.c_double(0)
+        self._chk(self.L.mdbg_chains_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def chain_batch(self, bases, offsets, max_skew=0, max_gap=0):
+        """align_batch with the chain stage behind it (mdbg_graph_chain_batch, include/mdbg_chain.h) -> the dict of graph_chains; read q is query q"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ch = _chains.ChainList()
+        self._chk(self.L.mdbg_graph_chain_batch(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, max_skew, max_gap, C.byref(ch)))
+        return _chains.chain_dict(ch)
 
     def kept_reads(self):
         """the resident read store of a keep_reads context -> dict(n_reads, n_bases, bytes); bytes = n_bases / 4 + 8 per read + 9 per exception, up to the

@@ -15,6 +15,7 @@
 
 #include "../../include/mdbg_hip.h"
 #include "../../include/mdbg_align.h"
+#include "../../include/mdbg_chain.h"
 #include "edges.h"
 #include "unitigs.h"
 #include "simplify.h"
@@ -26,6 +27,7 @@
 #include "junctions.h"
 #include "transits.h"
 #include "alignments.h"
+#include "chains.h"
 
 #include "blocks.inc"
 #include "results.inc"      // the derived graph results and which of them are current

@@ -451,7 +451,8 @@ int mdbg_transits_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.tr
 
 // ---- alignments: the steps chained over edge records, with base coordinates (alignments.hip; include/mdbg_align.h) ------
 // The stage over the range of `pw`, and the hand-over of both results it fills: the read paths' (whose step columns the list shares) and its own.
-static int alignments_over(mdbg_ctx* c, PlaceWindows& pw, mdbg_alignment_list* out, bool to_host) {
+// *dev_rp / *dev_al (optional) <- the two device results, for a stage that goes on from them on the device (the chains below).
+static int alignments_over(mdbg_ctx* c, PlaceWindows& pw, mdbg_alignment_list* out, bool to_host, ReadPathResult* dev_rp = nullptr, AlignmentResult* dev_al = nullptr) {
     Results& R = c->res;
     auto& P = R.rpaths; auto& A = R.alns;
     const FinArgs& F = pw.F;
@@ -462,6 +463,8 @@ static int alignments_over(mdbg_ctx* c, PlaceWindows& pw, mdbg_alignment_list* o
     A.ms = P.ms = r.ms;
     if (r.defect & AL_DEFECT_RECORD) return fail(c, MDBG_E_DEVICE, "a record an alignment needs is absent or outside the list (the closing record of a ring a step wraps), or a window reaches past its range");
     if (r.defect) return stage_defect(c, r.defect);
+    if (dev_rp) *dev_rp = rp;
+    if (dev_al) *dev_al = r;
     const u64 nr = rp.n_reads, ns = rp.n_steps, na = r.n_alignments;
     out->n_reads = nr; out->n_windows = rp.n_windows; out->n_placed = rp.n_placed; out->n_steps = ns; out->n_chained = r.n_chained; out->n_alignments = na; out->n_wraps = r.n_wraps;
     out->n_unitigs = rp.n_unitigs;
@@ -500,7 +503,10 @@ int mdbg_graph_alignments_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_
 int mdbg_alignments_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.alns.ms : nullptr, ms); }
 
 // a batch that is not resident: sketched behind the store as mdbg_query_batch does it, aligned, and the store rolled back (StoreRollback, store.inc)
-static int align_batch_impl(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out, bool to_host) {
+// chain != null: the chain stage behind it (mdbg_graph_chain_batch); out is then chain->out's alignment list
+struct ChainCall { uint32_t max_skew, max_gap; mdbg_chain_list* out; };
+static int chains_behind(mdbg_ctx* c, PlaceWindows& pw, const ChainCall& cc, bool to_host);
+static int align_batch_impl(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out, bool to_host, const ChainCall* chain = nullptr) {
     if (!c || !out) return MDBG_E_PARAM;
     u64 nb = 0;
     StageHold hold;
@@ -508,11 +514,11 @@ static int align_batch_impl(mdbg_ctx* c, const uint8_t* bases, const uint64_t* o
     MDBG_LOCK(c);
     (void)hipSetDevice(c->dev);
     if (c->poisoned) return fail(c, MDBG_E_STATE, "context is in an error state");
-    memset(out, 0, sizeof *out);
+    if (chain) { memset(chain->out, 0, sizeof *chain->out); c->res.chains.ms = 0; } else memset(out, 0, sizeof *out);
     Results& R = c->res;
     R.rpaths.ms = 0; R.alns.ms = 0;
     int e;
-    if ((e = refuse_multi_gpu(c, "alignments are")) || (e = refuse_without_unitig_list(c))) return e;
+    if ((e = refuse_multi_gpu(c, chain ? "chains are" : "alignments are")) || (e = refuse_without_unitig_list(c))) return e;
     if (R.unitig_list_copies()) return fail(c, MDBG_E_STATE, "the current unitig list holds copies made by a REPEATS or NESTED step: no read can be placed on it");
     if (!R.table_or_empty_context(nothing_resident(c))) return fail(c, MDBG_E_STATE, "the node table the unitig list was built from is not current");
     if (n_reads == 0) return MDBG_OK;
@@ -529,7 +535,60 @@ static int align_batch_impl(mdbg_ctx* c, const uint8_t* bases, const uint64_t* o
     if ((e = store_range(c, ul.n_unitigs, ul.n_entries, b.slot0, 0, &pw, &empty)) || empty) return e;
     if ((e = refuse_too_many_records(c, ul.edges.n))) return e;
     pw.rg.by_slot0 = nullptr; pw.rg.by_slot_first = nullptr; pw.rg.n_batches = 0;      // the temporary batch is in no batch table: ordinal[q] = q (reads_kernel)
-    return alignments_over(c, pw, out, to_host);
+    return chain ? chains_behind(c, pw, *chain, to_host) : alignments_over(c, pw, out, to_host);
 }
 int mdbg_graph_align_batch(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out) { return align_batch_impl(c, bases, offsets, n_reads, out, true); }
 int mdbg_graph_align_batch_device(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, mdbg_alignment_list* out) { return align_batch_impl(c, bases, offsets, n_reads, out, false); }
+
+// ---- chains: consecutive alignments of a read joined over a bridge (chains.hip; include/mdbg_chain.h) ------
+// The alignment stage over the range of `pw`, the chain stage behind it on what that left on the device, and the hand-over of the three results.
+static int chains_behind(mdbg_ctx* c, PlaceWindows& pw, const ChainCall& cc, bool to_host) {
+    Results& R = c->res;
+    auto& K = R.chains;
+    mdbg_chain_list* out = cc.out;
+    ReadPathResult rp; AlignmentResult al;
+    const int e = alignments_over(c, pw, &out->alignments, to_host, &rp, &al);
+    if (e) return e;
+    ChainResult r;
+    const hipError_t he = chains_run(K.buf.get(), R.placement.buf.get(), R.unitigs.last, rp, al, c->P.l, cc.max_skew, cc.max_gap, c->stream, &r);
+    if (he != hipSuccess) return fail_hip(c, "chains_run", he);
+    K.ms = R.alns.ms + r.ms;
+    if (r.defect) return fail(c, MDBG_E_DEVICE, "an alignment names a step, a unitig or a record outside its list");
+    const u64 nr = rp.n_reads, na = al.n_alignments, nc = r.n_chains;
+    out->n_bridges_inside = r.n_bridges_inside; out->n_bridges_record = r.n_bridges_record; out->n_bridges = r.n_bridges_inside + r.n_bridges_record;
+    out->n_chains = nc; out->n_gap_windows = r.n_gap_windows;
+    HandOver ho{c, "host copy of the chains", to_host};
+    ho.col(r.bridge_record, na, K.brec, &out->bridge_record);
+    ho.col(r.bridge_entries, na, K.bent, &out->bridge_entries);
+    ho.col(r.chain_offsets, nr + 1, K.coff, &out->chain_offsets);
+    ho.col(r.chain_aln_offsets, nc + 1, K.caoff, &out->chain_aln_offsets);
+    ho.col(r.chain_windows, nc, K.cwin, &out->chain_windows);
+    ho.col(r.chain_gap_windows, nc, K.cgap, &out->chain_gap_windows);
+    ho.col(r.query_begin, nc, K.qbeg, &out->query_begin);
+    ho.col(r.query_end, nc, K.qend, &out->query_end);
+    ho.col(r.path_length, nc, K.plen, &out->path_length);
+    ho.col(r.path_begin, nc, K.pbeg, &out->path_begin);
+    ho.col(r.path_end, nc, K.pend, &out->path_end);
+    return ho.err;
+}
+static int chains_impl(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint32_t max_skew, uint32_t max_gap, mdbg_chain_list* out, bool to_host) {
+    MDBG_ENTER(c, out);
+    memset(out, 0, sizeof *out);
+    out->alignments.first_read = first_read;
+    PlaceWindows pw; bool empty;
+    c->res.rpaths.ms = 0; c->res.chains.ms = 0;
+    const int e = stage_prologue(c, "chains are", first_read, max_reads, true, &c->res.alns.ms, &pw, &empty);
+    if (e || empty) return e;
+    return chains_behind(c, pw, ChainCall{max_skew, max_gap, out}, to_host);
+}
+int mdbg_graph_chains(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint32_t max_skew, uint32_t max_gap, mdbg_chain_list* out) { return chains_impl(c, first_read, max_reads, max_skew, max_gap, out, true); }
+int mdbg_graph_chains_device(mdbg_ctx* c, uint64_t first_read, uint64_t max_reads, uint32_t max_skew, uint32_t max_gap, mdbg_chain_list* out) { return chains_impl(c, first_read, max_reads, max_skew, max_gap, out, false); }
+int mdbg_chains_ms(mdbg_ctx* c, double* ms) { return last_ms(c, c ? &c->res.chains.ms : nullptr, ms); }
+int mdbg_graph_chain_batch(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t max_skew, uint32_t max_gap, mdbg_chain_list* out) {
+    const ChainCall cc{max_skew, max_gap, out};
+    return out ? align_batch_impl(c, bases, offsets, n_reads, &out->alignments, true, &cc) : MDBG_E_PARAM;
+}
+int mdbg_graph_chain_batch_device(mdbg_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t max_skew, uint32_t max_gap, mdbg_chain_list* out) {
+    const ChainCall cc{max_skew, max_gap, out};
+    return out ? align_batch_impl(c, bases, offsets, n_reads, &out->alignments, false, &cc) : MDBG_E_PARAM;
+}

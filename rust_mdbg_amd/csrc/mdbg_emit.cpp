@@ -31,6 +31,7 @@
 
 #include "../../include/mdbg_emit.h"
 #include "../../include/mdbg_align.h"
+#include "../../include/mdbg_chain.h"
 #include "gz_inflate.h"
 
 namespace {
@@ -1561,6 +1562,62 @@ int mdbg_gaf_append(const char* path, int truncate, const mdbg_alignment_list* a
                 const u64 ql = qe - qb, pl = pe - pb;
                 snprintf(num, sizeof num, "\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tnw:i:%u\tns:i:%llu\n", (unsigned long long)a->path_length[i], (unsigned long long)pb, (unsigned long long)pe,
                          (unsigned long long)std::min(ql, pl), (unsigned long long)std::max(ql, pl), a->aln_windows[i], (unsigned long long)(p1 - p0));
+                b += num;
+                if (b.size() >= (4u << 20)) { ok = write_all(f, b); b.clear(); }
+            }
+        }
+        ok = ok && write_all(f, b);
+    } catch (const std::bad_alloc&) { fclose(f); return MDBG_E_NOMEM; }
+    if (fclose(f) != 0) ok = false;
+    return bad ? MDBG_E_PARAM : ok ? MDBG_OK : MDBG_E_IO;
+}
+
+// ---- GAF: one line per chain of a chain list (include/mdbg_chain.h) ------------------------------------------------------------
+int mdbg_gaf_append_chains(const char* path, int truncate, const mdbg_chain_list* ch, const mdbg_unitig_list* ul, const uint64_t* read_lengths) {
+    if (!path || !ch || !ul) return MDBG_E_PARAM;
+    const mdbg_alignment_list* a = &ch->alignments;
+    if (a->n_reads && (!read_lengths || !a->ordinal || !ch->chain_offsets)) return MDBG_E_PARAM;
+    if (ch->n_chains && (!ch->chain_aln_offsets || !ch->bridge_record || !ch->chain_windows || !ch->chain_gap_windows || !ch->query_begin || !ch->query_end || !ch->path_length ||
+                         !ch->path_begin || !ch->path_end || !a->aln_step_offsets || !a->unitig || !a->first_entry || !a->step_windows || !a->strand || !ul->offsets || !ul->circular))
+        return MDBG_E_PARAM;
+    if (a->n_reads && ch->chain_offsets[a->n_reads] != ch->n_chains) return MDBG_E_PARAM;                                     // the three offset columns end where their lists do
+    if (ch->n_chains && (ch->chain_aln_offsets[ch->n_chains] != a->n_alignments || a->aln_step_offsets[a->n_alignments] != a->n_steps)) return MDBG_E_PARAM;
+    FILE* f = fopen(path, truncate ? "wb" : "ab");
+    if (!f) return MDBG_E_IO;
+    bool ok = true, bad = false;
+    try {
+        std::string b;
+        char num[200];
+        for (u64 q = 0; q < a->n_reads && ok && !bad; ++q) {
+            if (ch->chain_offsets[q + 1] > ch->n_chains) { bad = true; break; }
+            for (u64 c = ch->chain_offsets[q]; c < ch->chain_offsets[q + 1] && ok && !bad; ++c) {
+                const u64 qb = ch->query_begin[c], qe = ch->query_end[c], pb = ch->path_begin[c], pe = ch->path_end[c];
+                snprintf(num, sizeof num, "%llu\t%llu\t%llu\t%llu\t+\t", (unsigned long long)a->ordinal[q], (unsigned long long)read_lengths[q], (unsigned long long)qb, (unsigned long long)qe);
+                b += num;
+                const u64 a0 = ch->chain_aln_offsets[c], a1 = ch->chain_aln_offsets[c + 1];
+                if (a0 >= a1 || a1 > a->n_alignments) { bad = true; break; }
+                u64 n_steps = 0;
+                for (u64 i = a0; i < a1 && !bad; ++i) {
+                    const u64 p0 = a->aln_step_offsets[i], p1 = a->aln_step_offsets[i + 1];
+                    if (p0 > p1 || p1 > a->n_steps) { bad = true; break; }
+                    n_steps += p1 - p0;
+                    for (u64 p = p0; p < p1; ++p) {
+                        const u64 u = a->unitig[p];
+                        if (u >= ul->n_unitigs) { bad = true; break; }
+                        const u64 m = ul->offsets[u + 1] - ul->offsets[u], j = a->first_entry[p], n = a->step_windows[p];
+                        const bool circ = ul->circular[u] != 0, rev = a->strand[p] != 0;
+                        if (m == 0 || j >= m || n == 0) { bad = true; break; }
+                        const u64 wraps = circ ? ((rev ? m - 1 - j : j) + n - 1) / m : 0;
+                        const std::string name = unitig_name(u, circ);
+                        // an INSIDE bridge merges the first occurrence behind it into the last in front of it
+                        const u64 first = i > a0 && p == p0 && ch->bridge_record[i] == MDBG_BRIDGE_INSIDE ? 1 : 0;
+                        for (u64 w = first; w <= wraps; ++w) { b += rev ? '<' : '>'; b += name; }
+                    }
+                }
+                const u64 ql = qe - qb, pl = pe - pb;
+                snprintf(num, sizeof num, "\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tnw:i:%u\tns:i:%llu\tng:i:%llu\tgw:i:%u\n", (unsigned long long)ch->path_length[c], (unsigned long long)pb,
+                         (unsigned long long)pe, (unsigned long long)std::min(ql, pl), (unsigned long long)std::max(ql, pl), ch->chain_windows[c], (unsigned long long)n_steps,
+                         (unsigned long long)(a1 - a0 - 1), ch->chain_gap_windows[c]);
                 b += num;
                 if (b.size() >= (4u << 20)) { ok = write_all(f, b); b.clear(); }
             }

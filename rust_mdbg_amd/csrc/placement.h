@@ -64,3 +64,6 @@ struct PlacementView {
 hipError_t placement_reserve(PlacementBuffers* P, const UnitigResult& ul, uint64_t n_rows, const ReadPathRange& rg, bool with_records, const OriginMap& om = NO_COPIES);
 hipError_t placement_queue(PlacementBuffers* P, const UnitigResult& ul, const uint32_t* index, uint64_t n_rows, const ReadPathRange& rg, bool with_records, uint32_t n_counters,
                            const WindowPlacer& placer, hipStream_t s, PlacementView* view, const OriginMap& om = NO_COPIES);
+// the record keys in key order as the last placement_queue WITH records left them, for a stage that runs behind another stage's call and reads what it left on the
+// device (chains.hip behind alignments_run); R is the list's edges.n.  Valid until the next call of any stage.
+void placement_records(const PlacementBuffers* P, const uint64_t** rkey_sorted, const uint32_t** rec_sorted);

@@ -151,6 +151,7 @@ __global__ __launch_bounds__(256) void record_key_kernel(RecordKeyArgs a) {
 
 PlacementBuffers* placement_buffers_create() { return new PlacementBuffers(); }
 void placement_buffers_destroy(PlacementBuffers* b) { delete b; }
+void placement_records(const PlacementBuffers* P, const u64** rkey_sorted, const u32** rec_sorted) { *rkey_sorted = P->rkey_sorted.as<u64>(); *rec_sorted = P->rec_sorted.as<u32>(); }
 
 hipError_t placement_reserve(PlacementBuffers* P, const UnitigResult& ul, u64 n_rows, const ReadPathRange& rg, bool with_records, const OriginMap& om) {
     const u64 U = ul.n_unitigs, N = ul.n_entries, R = with_records ? ul.edges.n : 0, n_idx = rg.i1 - rg.i0;

@@ -1,5 +1,5 @@
 // results.inc — what a context derives from its table and keeps for the caller (the host copy of the node table, the edge list, the unitig list, components, contigs,
-// node sequences, read paths, junction support, transits, alignments) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
+// node sequences, read paths, junction support, transits, alignments, chains) and which of it is current.  Knows nothing of the context: included by api.inc in front of context.inc, whose mdbg_ctx holds one Results.
 namespace {
 // the buffers of one graph stage: created on first use, destroyed with the context
 template <class B, B* (*Create)(), void (*Destroy)(B*)> struct StageBuffers {
@@ -38,6 +38,8 @@ struct Results {
 
     struct { StageBuffers<AlignmentBuffers, alignment_buffers_create, alignment_buffers_destroy> buf;                    // its result lives until the next alignment call; the steps it names are the read-path result's
              HostRaw<u64> aoff, asoff, plen, pbeg, pend; HostRaw<u32> srec, awin, qbeg, qend; double ms = 0; } alns;
+    struct { StageBuffers<ChainBuffers, chain_buffers_create, chain_buffers_destroy> buf;                                // its result lives until the next chain call; the alignments it names are the alignment result's
+             HostRaw<u64> bent, coff, caoff, plen, pbeg, pend; HostRaw<u32> brec, cwin, cgap, qbeg, qend; double ms = 0; } chains;
 
     // ---- what is current.  ONLY the functions from here to still_holds write these members; everybody else asks the predicates below.
     struct { NodeTable table = NodeTable::NONE; u64 rows = 0;

@@ -57,6 +57,8 @@ def load_library():
         L.mdbg_emit_contigs_close.restype = None
         from . import align
         align.declare_emit(L)                              # the GAF writer (include/mdbg_align.h)
+        from . import chains
+        chains.declare_emit(L)                             # and the one of the chains (include/mdbg_chain.h)
         _LIB = L
     return _LIB
 

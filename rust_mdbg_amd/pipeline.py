@@ -11,6 +11,7 @@ import numpy as np
 
 from .api import MAGIC_SIMPLIFY_STEPS, MDBG_SIMPLIFY_NESTED, MDBG_SIMPLIFY_REPEATS, Mdbg, edge_columns, junction_text, merge_junctions, merge_transits, read_path_text, transit_self_flags, transit_text, unitig_name
 from .align import gaf_append
+from .chains import gaf_append_chains
 from .emit import Contigs, Emitter, Reader, lmer_filter_from_counts
 
 READ_PATH_CHUNK = 1 << 20      # reads per Mdbg.graph_read_paths / graph_junctions / graph_transits call of run_file
@@ -27,7 +28,7 @@ def apply_lmer_counts(m, lmer_counts, l, density, lmer_counts_min, lmer_counts_m
 def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=False, presimp=0.01, batch_bases=256 << 20,
              strip_newlines=False, device=-1, write_sequences=True, lmer_counts=None, lmer_counts_min=2, lmer_counts_max=100000,
              threads=1, packed=None, contigs=False, simplify=None, keep_reads=False, sequences_from_kept=False, components=False, read_paths=False, junctions=False, transits=0,
-             prefilter=False, prefilter_cells=0, gaf=False, query=None):
+             prefilter=False, prefilter_cells=0, gaf=False, query=None, chains=None):
     """-> dict of counters (what the reference prints: reads, nodes before/after filter, edges, presimp removals).
     contigs: also write <prefix>.unitigs.gfa (sequences in the S lines) and <prefix>.unitigs.fa — the unitigs of the graph, compacted on the GPU
     (Mdbg.graph_unitigs) and stitched from the reads in one more pass over the input (shared with the .sequences pass); this is `gfatools asm -u` +
@@ -59,6 +60,12 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
     aligned to the unitig list without changing it (Mdbg.align_batch): <prefix>.unitigs.query.gaf, and <prefix>.unitigs.query.tsv with one line
     `ordinal<TAB>windows<TAB>placed<TAB>%.2f` per query — its k-min-mers, how many of them lie on the list, and that share in percent (the columns of the
     reference's experiments/amr/parse_hits.py); with simplify the .msimpl. pair.  Adds n_queries, n_query_alignments (and n_query_alignments_simplified).
+    chains=(max_skew, max_gap) (with contigs): also write <prefix>.unitigs.chains.gaf: one GAF line per CHAIN, the alignments of a read joined across unplaced windows
+    where the graph bridges them (Mdbg.graph_chains, written by libmdbg_emit's mdbg_gaf_append_chains: include/mdbg_chain.h gives the rule, the columns and the tags),
+    in the same read ranges, and with simplify <prefix>.msimpl.chains.gaf.  With query= also <prefix>.unitigs.query.chains.gaf and <prefix>.unitigs.query.chains.tsv
+    with one line `ordinal<TAB>windows<TAB>placed<TAB>bridged<TAB>%.2f` per query: its k-min-mers, how many lie on the list, how many unplaced ones lie in bridged
+    gaps, and the share of (placed + bridged) in percent.  Adds n_chains, n_bridges, n_query_chains, n_query_bridges (and their _simplified twins).  Without it
+    every file and every key is what it is without the option.
     keep_reads (with contigs): the context keeps the reads it ingests, packed, on the device (Mdbg(keep_reads=True)) and the contigs' sequences are stitched
     there (Mdbg.graph_contigs) instead of on the host in a second pass: the same files, and without .sequences output the input is read ONCE.
     Adds kept_reads (the store's size) to the counters.
@@ -154,7 +161,7 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                 else:
                     m.ingest(payload, offs, n_reads)    # ctypes releases the GIL: the reader thread parses the next batch meanwhile
                     free.release()
-                if gaf:
+                if gaf or chains is not None:
                     read_lens.append(np.diff(np.asarray(payload["offsets"] if packed else offs).astype(np.uint64)))
                 n_reads += (len(payload["offsets"]) if packed else len(offs)) - 1
                 n_bases += nb
@@ -248,6 +255,39 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                         n_aln += al["n_alignments"]
                 comp["n_queries"] = first
                 comp["n_query_alignments" + suffix] = n_aln
+            def write_chains(ul, path_, suffix):         # the same ranges, one line per chain
+                lens = np.concatenate(read_lens) if read_lens else np.zeros(0, np.uint64)
+                open(path_, "w").close()
+                comp["n_chains" + suffix] = comp["n_bridges" + suffix] = 0
+                first = 0
+                while True:
+                    ch = m.graph_chains(first, READ_PATH_CHUNK, chains[0], chains[1])
+                    n = ch["alignments"]["n_reads"]
+                    if not n:
+                        break
+                    gaf_append_chains(path_, ch, ul, lens[first:first + n])
+                    comp["n_chains" + suffix] += ch["n_chains"]
+                    comp["n_bridges" + suffix] += ch["n_bridges"]
+                    first += n
+            def write_query_chains(ul, stem, suffix):    # the query file once more, chained
+                open(stem + ".query.chains.gaf", "w").close()
+                first = n_chains = n_bridges = 0
+                with Reader(query, strip_newlines) as qr, open(stem + ".query.chains.tsv", "w") as f:
+                    for qb, qo in qr.batches(batch_bases):
+                        ch = m.chain_batch(qb, qo, chains[0], chains[1])
+                        al = ch["alignments"]
+                        al["ordinal"] = al["ordinal"] + np.uint64(first)
+                        gaf_append_chains(stem + ".query.chains.gaf", ch, ul, np.diff(qo.astype(np.uint64)))
+                        co = ch["chain_offsets"].astype(np.int64)
+                        per_read = lambda col: (np.add.reduceat(np.append(col.astype(np.int64), 0), co[:-1]) * (np.diff(co) > 0)) if al["n_reads"] else np.zeros(0, np.int64)
+                        placed, bridged = per_read(ch["chain_windows"]), per_read(ch["chain_gap_windows"])
+                        f.write("".join("%d\t%d\t%d\t%d\t%.2f\n" % (o, w, p, g, 100.0 * (p + g) / w if w else 0.0)
+                                        for o, w, p, g in zip(al["ordinal"].tolist(), al["read_windows"].tolist(), placed.tolist(), bridged.tolist())))
+                        first += al["n_reads"]
+                        n_chains += ch["n_chains"]
+                        n_bridges += ch["n_bridges"]
+                comp["n_query_chains" + suffix] = n_chains
+                comp["n_query_bridges" + suffix] = n_bridges
             if contigs and simplify is not None:         # (before the plain list: the handle copies the plan, and graph_unitigs then reuses the buffers)
                 sl, sstats = m.graph_simplify(simplify, raw=True)
                 sctg = Contigs(sl)
@@ -266,6 +306,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_gaf(sl, prefix + ".msimpl.gaf", "n_alignments_simplified")
                 if query is not None and placeable:
                     write_query(sl, prefix + ".msimpl", "_simplified")
+                if chains is not None and placeable:
+                    write_chains(sl, prefix + ".msimpl.chains.gaf", "_simplified")
+                    if query is not None:
+                        write_query_chains(sl, prefix + ".msimpl", "_simplified")
                 if stitched:
                     g = m.graph_contigs(0)
                     sctg.set_sequences(g["bases"], g["offsets"])
@@ -285,6 +329,10 @@ def run_file(path, prefix, k, l, density, min_abundance=2, reads_already_hpc=Fal
                     write_gaf(ul, prefix + ".unitigs.gaf", "n_alignments")
                 if query is not None:
                     write_query(ul, prefix + ".unitigs", "")
+                if chains is not None:
+                    write_chains(ul, prefix + ".unitigs.chains.gaf", "")
+                    if query is not None:
+                        write_query_chains(ul, prefix + ".unitigs", "")
                 if stitched:
                     g = m.graph_contigs(0)
                     ctg.set_sequences(g["bases"], g["offsets"])
